@@ -1,6 +1,6 @@
 """bench.py -- NMF multiplicative-update iterations/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 N = 1: BASELINE config 2 -- dense V 10 000 x 5 000, r = 64, Lee-Seung MU (Frobenius), fp32, V resident
 in HBM; one step = one MU iteration (error terms evaluated every 10th iteration, as in the reference's
@@ -10,7 +10,9 @@ value = iterations/s of that problem; --scaling weak: one such matrix per GPU). 
 GPU) or by itself; two transports (team: one process, a rank thread per GPU, peer reads over xGMI; rccl: a process per GPU, RCCL's
 C API), every phase under a deadline -- see "N > 1" below.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line; the figures that take runs of their own (the
+cold leg `value_driver_warmup_only`, the launch samples of `roofline`, the CPU baselines) are measured with --full only.  --dump-outputs DIR writes what the
+timed path handed back after its last timed step (single GPU: W, H and the error terms) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -96,6 +98,26 @@ def whole_iteration(roofline, step_s, floor_bytes=None, floor_flops=None, basis=
     roofline["whole_iteration_frac"] = floor_s / step_s
     roofline["whole_iteration_basis"] = basis
     return roofline
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array, float32 or float64 as computed.  Past DUMP_LIMIT_BYTES in all, every array is cut to the same share of
+    its elements (column-major order), chosen by a fixed seed, so that two runs with the same arguments write comparable files."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {name: np.asarray(a) for name, a in arrays.items()}
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+    total = sum(a.nbytes for a in arrays.values())
+    share = min(1.0, (DUMP_LIMIT_BYTES - 4096 * len(arrays)) / max(total, 1))
+    for name, a in arrays.items():
+        if share < 1.0:
+            keep = max(1, int(a.size * share))
+            a = a.ravel(order="F")[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 _ENGINE_STREAM = []
@@ -296,7 +318,8 @@ def run_child(cmd, env, what: str, timeout: float):
 def worker_argv(args, role: str):
     argv = [sys.executable, os.path.abspath(__file__), role, "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--workload", args.workload,
             "--scaling", args.scaling, "--shard-mode", str(args.shard_mode), "--event-stride", str(args.event_stride), "--setup-iterations", str(args.setup_iterations)]
-    for flag, on in (("--no-cpu-baseline", args.no_cpu_baseline), ("--no-kernel-events", args.no_kernel_events), ("--allow-shared-device", args.allow_shared_device)):
+    for flag, on in (("--no-cpu-baseline", args.no_cpu_baseline), ("--no-kernel-events", args.no_kernel_events), ("--allow-shared-device", args.allow_shared_device),
+                     ("--full", args.full)):
         if on:
             argv.append(flag)
     return argv
@@ -389,6 +412,11 @@ def main():
                          "-1 (default) by message size: row blocks when the m x r panel is 8 MB or more (config 4)")
     ap.add_argument("--allow-shared-device", action="store_true",
                     help="--gpus N with fewer than N HIP devices visible: rehearse with rank threads sharing devices instead of refusing; the line says so in config.parallelism")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the cold leg (value_driver_warmup_only), the launch samples of `roofline` in an untimed replay behind "
+                         "the timed steps, and the CPU baselines (--no-kernel-events / --no-cpu-baseline still leave parts out).  Off: the line's headline figures only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (W, H, the error terms) as DIR/<name>.npy (single GPU)")
     ap.add_argument("--team-worker", action="store_true", help=argparse.SUPPRESS)      # (internal: the child process that runs the N rank threads)
     args = ap.parse_args()
     if args.event_stride <= 0:
@@ -399,12 +427,16 @@ def main():
     set_cpu_threads(args.cpu_threads)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if os.environ.get("NMFAMD_BENCH_DUMP_AFTER"):
         # debugging aid: where is every thread after N seconds (a rank that waits for its peers says nothing otherwise)
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["NMFAMD_BENCH_DUMP_AFTER"]), exit=False)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 or world > 1:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs is a single-GPU option (--gpus 1)")
         if args.workload not in ("c2", "c4"):
             raise SystemExit(f"--workload {args.workload} is a single-GPU workload (BASELINE: 1 x MI355X)")
         if args.team_worker:
@@ -445,9 +477,9 @@ def main():
         eng.upload(V)
         eng.set_factors(W, H)
         # First leg (round 6): the K steps right behind the driver's W warm-up steps and NOTHING else -- what `--warmup W` means taken literally; reported as
-        # value_driver_warmup_only / ms_per_step_driver_warmup_only beside the line's value, so that rounds stay comparable whatever the set-up phase below does.
+        # value_driver_warmup_only / ms_per_step_driver_warmup_only beside the line's value, so that rounds stay comparable whatever the set-up phase below does (--full).
         cold_elapsed = None
-        if SETUP_ITERATIONS > 0:
+        if args.full and SETUP_ITERATIONS > 0:
             eng.iterate(Wm, first_iteration=1, error_every=10)
             eng.synchronize()
             barrier()
@@ -469,7 +501,9 @@ def main():
         eng.iterate(K, first_iteration=Wm + 1, error_every=10)
         barrier()
         elapsed = time.perf_counter() - t0
-        if not args.no_kernel_events:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dict(zip(("W", "H"), eng.get_factors()), frobenius=np.array([eng.frobenius])))
+        if args.full and not args.no_kernel_events:
             # the launch samples of `roofline` come from an UNTIMED replay right behind the timed steps (iterations Wm + K + 1 ..., same stream, same engine, the device
             # still warm): a sampled iteration costs the stream ~23 us of waits around its two timed launches, which round 4 paid inside the timed region
             replay = replay_iterations(K, False)
@@ -497,7 +531,9 @@ def main():
         drv.run(K, first_iteration=Wm + 1, error_every=10)
         barrier()
         elapsed = time.perf_counter() - t0
-        if not args.no_kernel_events:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dict(zip(("W", "H"), shard.factors()), frobenius=np.array([drv.frobenius])))
+        if args.full and not args.no_kernel_events:
             replay = replay_iterations(K, False)
             shard.engine.kernel_timing(max(1, replay // REPLAY_SAMPLES))
             drv.run(replay, first_iteration=Wm + K + 1, error_every=10)
@@ -561,8 +597,8 @@ def main():
             "value": world * K / elapsed,
             "unit": "iterations/s" if world == 1 else "shard-iterations/s (one 10000x5000 column shard per GPU)",
             "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": elapsed / K * 1e3,
-            # the same K steps timed right behind the driver's W warm-up steps, before the set-up phase ran (same process, same engine; null when --setup-iterations 0
-            # makes `value` itself that figure)
+            # the same K steps timed right behind the driver's W warm-up steps, before the set-up phase ran (same process, same engine; --full only, and null when
+            # --setup-iterations 0 makes `value` itself that figure)
             "value_driver_warmup_only": (world * K / cold_elapsed) if cold_elapsed else None,
             "ms_per_step_driver_warmup_only": (cold_elapsed / K * 1e3) if cold_elapsed else None,
             # (N = 1 is the first point of north_star's 1/2/4/8 series of the ONE 10000 x 5000 problem, which `--gpus N` column-shards: strong scaling)
@@ -584,7 +620,7 @@ def main():
         }
         if roofline_mfma is not None:
             out["roofline_mfma"] = roofline_mfma
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(V, W, H, algorithm=algorithm, **alg_kw)
             if algorithm == "mu":
                 out["cpu_baseline_blas"] = cpu_baseline_blas(V, W, H, out["cpu_baseline"]["cores"])
@@ -646,7 +682,7 @@ def multi_line(args, pb, world, elapsed, kernel, frob, transport: str, shared_de
                       "setup_iterations": SETUP_ITERATIONS // 3 if pb["c4"] else SETUP_ITERATIONS, "parallelism": parallelism},
            "frobenius_last": frob,
            "roofline": whole_iteration(roofline, elapsed / K, floor_bytes=2.0 * bytes_per_launch, basis="rank 0's two passes over its image of V per iteration at the HBM peak")}
-    if not args.no_cpu_baseline and pb["full"] is not None:
+    if args.full and not args.no_cpu_baseline and pb["full"] is not None:
         phase("cpu baseline")
         Vf, Wf, Hf = pb["full"]
         out["cpu_baseline"] = (cpu_baseline(Vf, Wf, Hf, budget_s=12.0, algorithm="nsnmf", theta=C4["theta"]) if c4 else cpu_baseline(Vf, Wf, Hf))
@@ -710,7 +746,7 @@ def team_worker(args):
             torch.cuda.synchronize()
             gate.wait()
             kernel = (0.0, 0, 0.0)
-            if not args.no_kernel_events:
+            if args.full and not args.no_kernel_events:
                 # untimed replay behind the timed steps (every rank runs it: the iteration holds a rendezvous); rank 0's product launches are sampled there
                 phase(f"team: rank {g} untimed replay (launch samples)")
                 replay = replay_iterations(K, pb["c4"])
@@ -858,7 +894,7 @@ def rccl_ranks(args):
     elapsed = time.perf_counter() - t0
     barrier()
     kernel = (0.0, 0, 0.0)
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         # untimed replay behind the timed steps (a collective: every rank runs it); this rank's product launches are sampled there
         phase("RCCL: untimed replay (launch samples)")
         replay = replay_iterations(K, pb["c4"])
@@ -922,8 +958,10 @@ def main_f64(args):
     eng.iterate(K, first_iteration=Wm + 1, error_every=10)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(("W", "H"), eng.get_factors()), frobenius=np.array([eng.frobenius])))
     kernel_ms, kernel_launches, pair_overhead_ms = 0.0, 0, 0.0
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         replay = replay_iterations(K, False)
         eng.kernel_timing(max(1, replay // REPLAY_SAMPLES))
         eng.iterate(replay, first_iteration=Wm + K + 1, error_every=10)
@@ -959,7 +997,7 @@ def main_f64(args):
                       "gram_passenger_k_slices": [eng.geometry()["gram_ride_slices_h"], eng.geometry()["gram_ride_slices_w"]]},
            "frobenius_last": frob, "iter_flops": iter_flops, "achieved_tflops_whole_iteration": iter_flops * (K / elapsed) / 1e12,
            "roofline": whole_iteration(roofline, elapsed / K, floor_flops=2.0 * flops_per_launch, basis="the two products against V at the fp64 MFMA peak")}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(V, W, H, budget_s=15.0, algorithm=alg, **kw)
     print(json.dumps(out), flush=True)
 
@@ -989,8 +1027,10 @@ def main_c3(args):
     eng.iterate(K, first_iteration=Wm + 1, error_every=10)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(("W", "H"), eng.get_factors()), frobenius=np.array([eng.frobenius]), kl_divergence=np.array([eng.kl_divergence])))
     kernel_ms, kernel_launches, pair_overhead_ms = 0.0, 0, 0.0
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         replay = max(10, min(K, 30))       # untimed replay behind the timed steps: the launch samples of `roofline`
         eng.kernel_timing(max(1, replay // 5))
         eng.iterate(replay, first_iteration=Wm + K + 1, error_every=10)
@@ -1024,7 +1064,7 @@ def main_c3(args):
     if roofline is not None:
         roofline["whole_iteration_frac"] = (2.0 * gather_bytes / (PEAK_L2_GATHER_GBS * 1e9)) / (elapsed / K)
         roofline["whole_iteration_basis"] = "two gather passes over the stored entries (one 512-byte factor row each) at the L2 row-gather rate"
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle
         Wc, Hc = W.copy(order="F"), H.copy(order="F")
         t0 = time.perf_counter()
@@ -1068,8 +1108,10 @@ def main_c4(args):
     drv.run(K, first_iteration=Wm + 1, error_every=10)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(("W", "H"), shard.factors()), frobenius=np.array([drv.frobenius])))
     kernel_ms, kernel_launches, pair_overhead_ms = 0.0, 0, 0.0
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         replay = replay_iterations(K, True)       # untimed replay behind the timed steps: the launch samples of `roofline`
         shard.engine.kernel_timing(max(1, replay // REPLAY_SAMPLES))
         drv.run(replay, first_iteration=Wm + K + 1, error_every=10)
@@ -1098,7 +1140,7 @@ def main_c4(args):
             "frobenius_last": drv.frobenius, "iter_flops": iter_flops,
             "achieved_tflops_whole_iteration": iter_flops * (K / elapsed) / 1e12,
             "roofline": whole_iteration(roofline, elapsed / K, floor_bytes=2.0 * bytes_per_launch, basis="two passes over the bf16 image of the shard per iteration (2 x 625 MB) at the HBM peak"),
-            **({} if args.no_cpu_baseline else {"cpu_baseline": cpu_baseline(V, W, H, budget_s=12.0, algorithm="nsnmf", theta=theta)})}), flush=True)
+            **({} if args.no_cpu_baseline or not args.full else {"cpu_baseline": cpu_baseline(V, W, H, budget_s=12.0, algorithm="nsnmf", theta=theta)})}), flush=True)
 
 
 if __name__ == "__main__":

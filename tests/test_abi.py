@@ -156,8 +156,10 @@ def test_no_packed_fp32_instruction_reads_a_scalar_register():
     halves in lanes 48..63 whenever another kernel's waves shared the SIMD.  The build refuses such code (nmfgpu_amd/build.py);
     this re-checks the objects the loaded library was linked from, and that the check itself still sees the offending form."""
     from nmfgpu_amd import build as b
-    objs = [os.path.join(b.OBJDIR, os.path.splitext(s)[0] + ".o") for s in b.SOURCES if s.endswith(".hip")]
-    assert len(objs) >= 10 and all(os.path.exists(o) for o in objs)
+    # the shipped library's objects, and the measurement-only sources where the measurement build compiles them (obj_diag/)
+    objs = [os.path.join(os.path.join(b.LIBDIR, "obj_diag") if s in b.DIAG_ONLY else b.OBJDIR, os.path.splitext(s)[0] + ".o")
+            for s in b.SOURCES if s.endswith(".hip")]
+    assert len(objs) >= 10 and all(os.path.exists(o) for o in objs), [o for o in objs if not os.path.exists(o)]
     for o in objs:
         assert b.packed_scalar_sources(o) == [], o
     assert "-fno-slp-vectorize" in b.DEVICE_FLAGS

@@ -1,5 +1,6 @@
-"""bench.py's one-line JSON contract, on the GPU: a short default run must print exactly one JSON object with the metric,
-the whole-job value, the roofline object of the dominant kernel (live HIP-event timing) and the CPU baseline."""
+"""bench.py's one-line JSON contract, on the GPU: a short --full run must print exactly one JSON object with the metric,
+the whole-job value, the roofline object of the dominant kernel (live HIP-event timing) and the CPU baseline; a plain run the
+headline figures only, and --dump-outputs the factors its timed steps computed."""
 import json
 import os
 import subprocess
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_default_bench_line_has_the_contract_fields():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "10"], cwd=ROOT, capture_output=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "10", "--full"], cwd=ROOT, capture_output=True,
                          text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -55,6 +56,30 @@ def test_default_bench_line_has_the_contract_fields():
     assert 2000 < d["frobenius_last"] < 2100
 
 
+def test_plain_bench_line_is_lean_and_dumps_what_the_timed_steps_computed(tmp_path):
+    """Without --full: the headline fields and nothing that takes a run of its own; --dump-outputs: W, H and the error of the last timed step, the factors
+    those of the fp64 oracle after the same warmup + steps iterations from the same seeded W0, H0."""
+    import numpy as np
+    import bench
+    from oracle import oracle
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "4", "--dump-outputs", str(dump)], cwd=ROOT,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("NMF MU iterations/sec") and d["unit"] == "iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 6 and d["warmup"] == 4 and d["value"] == pytest.approx(1e3 / d["ms_per_step"], rel=1e-6)
+    assert "cpu_baseline" not in d and "roofline_mfma" not in d and d["roofline"] is None and d["value_driver_warmup_only"] is None
+    W, H, frob = (np.load(dump / f"{name}.npy") for name in ("W", "H", "frobenius"))
+    assert W.shape == (10000, 64) and H.shape == (64, 5000) and W.dtype == H.dtype == np.float32 and frob.dtype == np.float64
+    assert frob[0] == d["frobenius_last"]
+    V, W0, H0 = bench.make_problem(0)
+    V64, W64, H64 = (np.asfortranarray(x.astype(np.float64)) for x in (V, W0, H0))
+    oracle.run("mu", V64, W64, H64, 10)
+    assert np.linalg.norm(W - W64) / np.linalg.norm(W64) < 1e-4 and np.linalg.norm(H - H64) / np.linalg.norm(H64) < 1e-4
+
 
 def test_gpus_n_without_torchrun_refuses_or_rehearses():
     """`python bench.py --gpus 2` outside torchrun on a box with ONE device: no line at all and a non-zero exit (never an n_gpus = 1
@@ -67,7 +92,7 @@ def test_gpus_n_without_torchrun_refuses_or_rehearses():
     out = subprocess.run(base, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode != 0 and not [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert "--gpus 2" in out.stderr and "1 HIP device" in out.stderr
-    out = subprocess.run(base + ["--allow-shared-device"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    out = subprocess.run(base + ["--allow-shared-device", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
