@@ -39,8 +39,9 @@ enum {
 	                            MFMA instructions).  nmfgpu::compute and the Python Engine do that by themselves. */
 };
 
-/* algorithm ids = nmfgpu::NmfAlgorithm (include/nmfgpu.h:107-114) */
-enum { NMFAMD_MU = 0, NMFAMD_GDCLS = 1, NMFAMD_ALS = 2, NMFAMD_ACLS = 3, NMFAMD_AHCLS = 4, NMFAMD_NSNMF = 5 };
+/* algorithm ids = nmfgpu::NmfAlgorithm (include/nmfgpu.h:107-114; NMFAMD_HALS is an extension: coordinate descent, docs/HALS.md -- no
+   parameters, no three-phase / sharded form) */
+enum { NMFAMD_MU = 0, NMFAMD_GDCLS = 1, NMFAMD_ALS = 2, NMFAMD_ACLS = 3, NMFAMD_AHCLS = 4, NMFAMD_NSNMF = 5, NMFAMD_HALS = 6 };
 
 /* sparse formats = nmfgpu::StorageFormat (include/nmfgpu.h:177-186) */
 enum { NMFAMD_DENSE = 0, NMFAMD_CSR = 1, NMFAMD_CSC = 2, NMFAMD_COO = 3 };

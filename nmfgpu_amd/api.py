@@ -49,6 +49,7 @@ class NmfAlgorithm(enum.IntEnum):  # ref :107-114
     ACLS = 3
     AHCLS = 4
     nsNMF = 5
+    HALS = 6  # extension: coordinate descent (docs/HALS.md)
 
 
 class Verbosity(enum.IntEnum):  # ref :117-126

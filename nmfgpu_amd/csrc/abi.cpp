@@ -131,6 +131,7 @@ const char* algorithm_name(NmfAlgorithm a) {
 	case NmfAlgorithm::ACLS: return "Alternating Constrained Least Squares";
 	case NmfAlgorithm::AHCLS: return "Alternating Hoyer Constrained Least Squares";
 	case NmfAlgorithm::nsNMF: return "non-smooth NMF";
+	case NmfAlgorithm::HALS: return "HALS";
 	}
 	return "?";
 }
@@ -170,7 +171,7 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		return true;
 	};
 	switch (d.algorithm) {
-	case NmfAlgorithm::Multiplicative: case NmfAlgorithm::ALS: break;
+	case NmfAlgorithm::Multiplicative: case NmfAlgorithm::ALS: case NmfAlgorithm::HALS: break;
 	case NmfAlgorithm::ACLS:
 		if (!need("lambdaW", prm.lambdaW, "ACLS") || !need("lambdaH", prm.lambdaH, "ACLS")) return ResultType::ErrorInvalidArgument;
 		break;
@@ -238,6 +239,10 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		if (idx >= 0) num_gpus = (int)d.parameters[idx].value;
 		idx = parameter_index(d.parameters, d.numParameters, "shardMode");
 		if (idx >= 0) shard_mode = d.parameters[idx].value != 0 ? nmfamd::SHARD_REPLICATED : nmfamd::SHARD_ROW_BLOCKS;
+		if (num_gpus > 1 && d.algorithm == NmfAlgorithm::HALS) {
+			log_error("[ERROR] 'numGpus' > 1 is not available for the HALS algorithm!");
+			return ResultType::ErrorInvalidArgument;
+		}
 		if (num_gpus > 1) {
 			const bool mult = d.algorithm == NmfAlgorithm::Multiplicative || d.algorithm == NmfAlgorithm::nsNMF;
 			if (num_gpus > 16 || (unsigned)num_gpus > d.inputMatrix.columns) {
@@ -275,8 +280,8 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 	const double thresholdValue = d.thresholdValue;
 	const UserInterruptCallback interrupt = d.callbackUserInterrupt;
 	const bool constW = d.useConstantBasisVectors;
-	// only W is initialised for the LS algorithms (their first step solves for H)
-	const bool want_h = d.algorithm == NmfAlgorithm::Multiplicative || d.algorithm == NmfAlgorithm::nsNMF;
+	// only W is initialised for the LS algorithms (their first step solves for H); HALS sweeps from the old H
+	const bool want_h = d.algorithm == NmfAlgorithm::Multiplicative || d.algorithm == NmfAlgorithm::nsNMF || d.algorithm == NmfAlgorithm::HALS;
 
 	// IAlgorithm's seed stream: constructed from the caller's seed, one draw per run
 	std::mt19937 seed_stream(d.seed);

@@ -175,7 +175,8 @@ Engine<T>::~Engine() {
 
 template <typename T>
 Status Engine<T>::allocate() {
-	if (m_ <= 0 || n_ <= 0 || r_ <= 0 || alg_ < 0 || alg_ > ALG_NSNMF) return ST_INVALID;
+	if (m_ <= 0 || n_ <= 0 || r_ <= 0 || alg_ < 0 || alg_ > ALG_HALS) return ST_INVALID;
+	if (alg_ == ALG_HALS && !panel_sweep_hals_available(RP_, sizeof(T))) { last_error_ = "HALS: no sweep kernel for this padded rank (fp32: 64 ... 512, fp64: multiples of 64 up to 512)"; return ST_INVALID; }
 	int dev = 0;
 	HIPX(hipGetDevice(&dev));
 	hipDeviceProp_t prop;
@@ -363,7 +364,8 @@ Status Engine<T>::allocate() {
 	HIPX(dalloc(&HHt_, rr));
 	HIPX(dalloc(&Qinv_, rr));
 	HIPX(dalloc(&gram_part_, rr * gram_parts_));
-	HIPX(dalloc(&sumsq_part_, ((long)std::max(panel_update_parts(RP_, sizeof(T), (int)mpad_), (int)(mpad_ / panel_update_rows(RP_, sizeof(T)))) + 16) * RP_));
+	HIPX(dalloc(&sumsq_part_, ((long)std::max({panel_update_parts(RP_, sizeof(T), (int)mpad_), (int)(mpad_ / panel_update_rows(RP_, sizeof(T))),
+	                                           alg_ == ALG_HALS ? panel_sweep_hals_parts(RP_, sizeof(T), (int)mpad_) : 0}) + 16) * RP_));
 	// the two error-term vectors share one allocation (and one pinned landing buffer): ONE device-to-host copy per error iteration
 	ps_stride_ = std::max<long>(npad_, RP_);
 	HIPX(dalloc(&psN_, ps_stride_ + RP_));
@@ -1113,6 +1115,7 @@ Status Engine<T>::h_step(bool compute_error) {
 	// first call of an iteration in the sharded form: decides whether this iteration's products are timed
 	timing_now_ = timing_ && (timing_iter_++ % timing_stride_ == 0);
 	if (prm_.divergence != 0) { kl_err_iter_ = compute_error; return kl_h_step(); }
+	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	return h_step_impl(compute_error);
 }
 
@@ -1176,6 +1179,14 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 	if (!(gram_w_ready_ && F == Wt_)) HIPX(launch_gram<T>(F, RP_, m_, gram_parts_, gram_part_, G_, stream_));
 	gram_w_ready_ = false;      // consumed (the inverse passenger / update below read G_; W changes in the W step)
 	const int S = planH_.splits;
+	if (alg_ == ALG_HALS) {
+		// coordinate sweep over every column of H against G = W^T W and the summed slabs of W^T V; ps: the per-column terms of tr(H^T W^T V), as PANEL_MU
+		// writes them.  No split image of the new H: the next product packs its operand itself.
+		if (Status s = product_h(F, nullptr, x3_ && wx3_valid_ && F == Wt_)) return s;
+		HIPX(launch_panel_sweep_hals<T>(H_, slabs_, S, slab_stride_, G_, RP_, r_, (int)npad_, n_, compute_error ? psN_ : nullptr, nullptr, stream_));
+		hx3_valid_ = false;
+		return ST_OK;
+	}
 	if (alg_ == ALG_MU || alg_ == ALG_NSNMF) {
 		if (Status s = product_h(F, nullptr, x3_ && wx3_valid_ && F == Wt_)) return s;
 		const bool emit = x3_ && alg_ == ALG_MU && panel_update_delivers_gram(RP_, sizeof(T));   // nsNMF's W step consumes the smoothed panel
@@ -1222,6 +1233,7 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 template <typename T>
 Status Engine<T>::w_products(T* exchange) {
 	if (prm_.divergence != 0) return kl_w_products(exchange, kl_err_iter_);      // (sparse Frobenius compute shards through the code below: its two products are SpMMs over the shard's images)
+	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	T* ex_hht = exchange + (long)RP_ * mpad_;
 	if constexpr (std::is_same<T, float>::value) {
 		if (fused_capable()) {
@@ -1270,6 +1282,7 @@ Status Engine<T>::w_products(T* exchange) {
 template <typename T>
 Status Engine<T>::w_finish(const T* exchange, bool compute_error) {
 	if (prm_.divergence != 0) return kl_w_finish(exchange, compute_error);
+	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	const T eps = std::numeric_limits<T>::epsilon();
 	const T* ex_hht = exchange + (long)RP_ * mpad_;
 	if (alg_ != ALG_MU && alg_ != ALG_NSNMF) {
@@ -1945,7 +1958,7 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				if (tri_) wtw = reinterpret_cast<const T*>(Gw_raw_);
 				else if (fused_capable()) wtw = G_;             // (rank 64: the H step's passengers took it from the unsmoothed image, pending scale applied)
 				else { HIPX(launch_gram<T>(Wt_, RP_, m_, gram_parts_, gram_part_, G2_, stream_)); wtw = G2_; }
-			} else if (alg_ != ALG_MU) wtw = G2_;               // LS algorithms: copy saved before the regulariser
+			} else if (alg_ != ALG_MU && alg_ != ALG_HALS) wtw = G2_;      // LS algorithms: copy saved before the regulariser (MU, HALS: W^T W of this H step)
 			HIPX(launch_trace_small<T>(HHt_, wtw, RP_, r_, psR_, stream_, tri_trace_scale()));
 		}
 		if (!constant_w) {
@@ -1981,7 +1994,14 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				// (rank 256, H H^T rode in that launch: the error term's trace of H H^T against the unsmoothed W^T W of this iteration's H step, AlgorithmNonSmoothNMF.h:201-202)
 				if (compute_error && tri_ride.tri_frags != nullptr) HIPX(launch_trace_small<T>(HHt_, reinterpret_cast<const T*>(Gw_raw_), RP_, r_, psR_, stream_, tri_trace_scale()));
 			}
-			if (!ls_family) {
+			if (alg_ == ALG_HALS) {
+				// coordinate sweep over every row of W against H H^T and the summed slabs of V H^T, then the column normalisation that keeps W H:
+				// W(:, c) / d(c), H(c, :) d(c) -- applied to H at once, no pending scale
+				wx3_valid_ = false;
+				gram_w_ready_ = false;
+				HIPX(launch_panel_sweep_hals<T>(Wt_, slabs_, S, slab_stride_, HHt_, RP_, r_, (int)mpad_, m_, nullptr, sumsq_part_, stream_));
+				HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, panel_sweep_hals_parts(RP_, sizeof(T), (int)mpad_), stream_));
+			} else if (!ls_family) {
 				const bool gd_err = alg_ == ALG_GDCLS && compute_error;
 				T* wpart = nullptr;
 				if constexpr (std::is_same<T, float>::value) { if (gram_from_update()) wpart = gramW_part_; }
@@ -2013,7 +2033,7 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				}
 				if (Status s = normalize_w(wpart != nullptr, norm_parts)) return s;
 			}
-		} else if (compute_error && alg_ != ALG_MU && alg_ != ALG_NSNMF) {
+		} else if (compute_error && alg_ != ALG_MU && alg_ != ALG_NSNMF && alg_ != ALG_HALS) {
 			// constant basis vectors, LS algorithms: the reference's trace reads W against itself
 			// (ALS/ACLS/AHCLS :199-205 with W never overwritten) or a stale buffer (GDCLS); here:
 			// ALS family as the reference, GDCLS the product the formula names.

@@ -15,7 +15,8 @@
 
 namespace nmfamd {
 
-enum Algorithm { ALG_MU = 0, ALG_GDCLS = 1, ALG_ALS = 2, ALG_ACLS = 3, ALG_AHCLS = 4, ALG_NSNMF = 5 };
+// ALG_HALS: coordinate descent (kernels_hals.hip, docs/HALS.md) -- the generic launch sequence only, single-engine runs only (no three-phase / sharded form)
+enum Algorithm { ALG_MU = 0, ALG_GDCLS = 1, ALG_ALS = 2, ALG_ACLS = 3, ALG_AHCLS = 4, ALG_NSNMF = 5, ALG_HALS = 6 };
 
 struct AlgorithmParams {
 	double lambda = 0, lambdaW = 0, lambdaH = 0, alphaW = 0, alphaH = 0, theta = 0;
@@ -157,7 +158,8 @@ public:
 	int rp() const { return RP_; }
 	// GDCLS and the ALS family evaluate tr(H^T W^T V) as r terms (one per factor row, from the reduced sums: identical on every rank of a
 	// column-sharded run); the multiplicative algorithms as one term per column of V
-	bool error_terms_per_factor_row() const { return alg_ != ALG_MU && alg_ != ALG_NSNMF; }
+	bool error_terms_per_factor_row() const { return alg_ != ALG_MU && alg_ != ALG_NSNMF && alg_ != ALG_HALS; }
+	int algorithm() const { return alg_; }
 	long mpad() const { return mpad_; }
 	long npad() const { return npad_; }
 	int slabs_h() const { return planH_.splits; }

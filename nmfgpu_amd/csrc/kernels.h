@@ -265,6 +265,19 @@ hipError_t launch_panel_update(int mode, T* P, const T* slabs, int S, long slab_
                                void* q_split = nullptr,                  // scratch for the split image of Q (wide fp32 panels, see launch_panel_update_wide_f32)
                                const PanelTriExtras* tri = nullptr);     // fp32, padded rank 256 only
 
+// HALS (kernels_hals.hip): Gauss-Seidel sweep over the r coordinates of every panel column, P(:, y) <- the clamped coordinate-descent update
+// against G (r x r Gram matrix) and the summed slabs; ps / sumsq_part (optional) as launch_panel_update's, with panel_sweep_hals_parts() partials.
+// Padded ranks: fp32 64, 128, 256, 384, 512; fp64 multiples of 64 up to 512.
+bool panel_sweep_hals_available(int RP, size_t elem);
+int panel_sweep_hals_parts(int RP, size_t elem, int len_pad);
+template <typename T>
+hipError_t launch_panel_sweep_hals(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part,
+                                   hipStream_t stream);
+// W(:, c) <- W(:, c) / d(c), H(c, :) <- H(c, :) d(c) where d(c) = ||W(:, c)|| > 0, d from `parts` vectors of partial sums of squares (W H unchanged);
+// sumsq_part needs RP elements of scratch behind the partials
+template <typename T>
+hipError_t launch_hals_normalize(T* Wt, int RP, int mpad, T* H, int npad, T* sumsq_part, int parts, hipStream_t stream);
+
 // sumsq_part: parts * RP partial sums followed by 16 * RP elements of scratch
 template <typename T>
 hipError_t launch_normalize_panel(T* P, int RP, int len_pad, T* sumsq_part, int parts, hipStream_t stream);
