@@ -317,6 +317,20 @@ NMFAMD_API int nmfamd_op_factor_passes_f32(const float* P, long ldp, int r, int 
 NMFAMD_API int nmfamd_op_tri_update_f32(const float* P, const float* num, const float* Q, int r, int len, const float* old_colsq, int transform_num,
                                         const float* num_colsq, float theta, float frag_theta, int transform_den, float* P_out, float* pack_out,
                                         float* scale_out, float* gram_out, float* gram_raw_out, float* gram_image_out, float* diag_out);
+/* One launch of the HALS sweep (kernels_hals.hip) on host arrays in panel layout, for tests: P [len_pad][RP] (updated in place), S slabs of
+ * [len_pad][RP] at slab_stride >= len_pad * RP elements (the gaps between them are not read), G [RP][RP]; coordinates k >= r and columns
+ * y >= len_valid are padding.  ps (len_pad values) and sumsq_part ((len_pad / 16) * RP values, enough for every rank) may be NULL; both are copied
+ * to the device before the launch and back after it, so entries the kernel does not write keep what the caller put there.  *parts: the rows of
+ * sumsq_part the sweep writes.  NMFAMD_INVALID_ARGUMENT wherever the launcher refuses (RP not instantiated, r outside 1 .. RP,
+ * len_pad % 128 != 0, len_valid > len_pad). */
+NMFAMD_API int nmfamd_op_hals_sweep_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid,
+                                        float* ps, float* sumsq_part, int* parts);
+NMFAMD_API int nmfamd_op_hals_sweep_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid,
+                                        double* ps, double* sumsq_part, int* parts);
+/* The HALS column normalisation on host panels Wt [mpad][RP] and H [npad][RP] (both updated in place) from parts x RP partial sums of squares:
+ * d(c) = sqrt(sum of the parts); where d(c) > 0, Wt(:, c) / d(c) and H(:, c) * d(c). */
+NMFAMD_API int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad, const float* sumsq_part, int parts);
+NMFAMD_API int nmfamd_op_hals_normalize_f64(double* Wt, int RP, int mpad, double* H, int npad, const double* sumsq_part, int parts);
 /* Test access to an engine's device intermediates in panel layout: which = 0 Wt, 1 H, 2 W^T W,
  * 3 H H^T, 4 slabs, 5 inverse, 6 V, 7 Vt; rank-256 fp32 engines also 8 W^T W as last reduced, 9 staged column sums of squares,
  * 10 / 11 the bf16 fragments of W / H as 4-byte words. */

@@ -817,3 +817,68 @@ int nmfamd_op_factor_passes_f32(const float* P, long ldp, int r, int len, const 
 }
 
 } // extern "C"
+
+// Test entries of kernels_hals.hip: one launch of the sweep or of the normalisation on caller-supplied padded arrays, so that tests can put what
+// they like into the padding.  No argument checks beyond the buffer sizes: the launchers decide what they accept.
+namespace {
+template <typename T>
+int op_hals_sweep(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part, int* parts) {
+	if (!P || !slabs || !G || !parts || S < 1 || RP < 1 || RP > 4096 || len_pad < 1 || slab_stride < (long)len_pad * RP) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const int np = panel_sweep_hals_parts(RP, sizeof(T), len_pad);
+	const size_t panel = sizeof(T) * (size_t)len_pad * RP, all_slabs = sizeof(T) * (size_t)(((long)S - 1) * slab_stride + (long)len_pad * RP);
+	DevBuf dP, dS, dG, dPs, dSq;
+	if (dP.alloc(panel) != hipSuccess || dS.alloc(all_slabs) != hipSuccess || dG.alloc(sizeof(T) * (size_t)RP * RP) != hipSuccess ||
+	    dPs.alloc(sizeof(T) * (size_t)len_pad) != hipSuccess || dSq.alloc(sizeof(T) * (size_t)(np > 0 ? np : 1) * RP) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+	if (hipMemcpy(dP.p, P, panel, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dS.p, slabs, all_slabs, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(dG.p, G, sizeof(T) * (size_t)RP * RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (ps && hipMemcpy(dPs.p, ps, sizeof(T) * (size_t)len_pad, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (sumsq_part && np > 0 && hipMemcpy(dSq.p, sumsq_part, sizeof(T) * (size_t)np * RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	const hipError_t err = launch_panel_sweep_hals<T>((T*)dP.p, (const T*)dS.p, S, slab_stride, (const T*)dG.p, RP, r, len_pad, len_valid,
+	                                                  ps ? (T*)dPs.p : nullptr, sumsq_part ? (T*)dSq.p : nullptr, nullptr);
+	if (err == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
+	if (err != hipSuccess || hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (hipMemcpy(P, dP.p, panel, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (ps && hipMemcpy(ps, dPs.p, sizeof(T) * (size_t)len_pad, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (sumsq_part && hipMemcpy(sumsq_part, dSq.p, sizeof(T) * (size_t)np * RP, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	*parts = np;
+	return NMFAMD_OK;
+}
+
+template <typename T>
+int op_hals_normalize(T* Wt, int RP, int mpad, T* H, int npad, const T* sumsq_part, int parts) {
+	if (!Wt || !H || !sumsq_part || RP < 4 || RP % 4 != 0 || mpad < 1 || npad < 1 || parts < 1) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const size_t w = sizeof(T) * (size_t)mpad * RP, h = sizeof(T) * (size_t)npad * RP;
+	DevBuf dW, dH, dSq;
+	// (parts + 16) * RP: the launcher reduces into the scratch behind the partials, as the engine sizes its buffer
+	if (dW.alloc(w) != hipSuccess || dH.alloc(h) != hipSuccess || dSq.alloc(sizeof(T) * ((size_t)parts + 16) * RP) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+	if (hipMemcpy(dW.p, Wt, w, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dH.p, H, h, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(dSq.p, sumsq_part, sizeof(T) * (size_t)parts * RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (launch_hals_normalize<T>((T*)dW.p, RP, mpad, (T*)dH.p, npad, (T*)dSq.p, parts, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (hipMemcpy(Wt, dW.p, w, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(H, dH.p, h, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
+}
+
+extern "C" {
+
+int nmfamd_op_hals_sweep_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid, float* ps,
+                             float* sumsq_part, int* parts) {
+	return op_hals_sweep<float>(P, slabs, S, slab_stride, G, RP, r, len_pad, len_valid, ps, sumsq_part, parts);
+}
+
+int nmfamd_op_hals_sweep_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid, double* ps,
+                             double* sumsq_part, int* parts) {
+	return op_hals_sweep<double>(P, slabs, S, slab_stride, G, RP, r, len_pad, len_valid, ps, sumsq_part, parts);
+}
+
+int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad, const float* sumsq_part, int parts) {
+	return op_hals_normalize<float>(Wt, RP, mpad, H, npad, sumsq_part, parts);
+}
+
+int nmfamd_op_hals_normalize_f64(double* Wt, int RP, int mpad, double* H, int npad, const double* sumsq_part, int parts) {
+	return op_hals_normalize<double>(Wt, RP, mpad, H, npad, sumsq_part, parts);
+}
+
+} // extern "C"

@@ -4,7 +4,8 @@
 // Panel layout of the engine: column y of H (or row y of W) is RP contiguous elements at P[y * RP].  For each column, with
 // a = sum of the split-K slabs (W^T V, or (V H^T)^T) and the r x r Gram matrix G (W^T W, or H H^T):
 //   for k = 0 .. r - 1, skipping k where G(k, k) <= 0:   p(k) <- max(0, p(k) - (G(k, :) . p - a(k)) / G(k, k))
-// with the entries l < k already updated (Gauss-Seidel).  Coordinates k >= r and columns y >= len_valid are written as 0.
+// with the entries l < k already updated (Gauss-Seidel).  Coordinates k >= r and columns y >= len_valid are written as 0, whatever the padding of P,
+// the slabs and G holds, and add nothing to ps or sumsq_part (an invalid column is swept like the others and masked when it is written).
 //
 // Mapping: L lanes per column, lane j holds the entries l = e * L + j (e = 0 .. E - 1, E = RP / L) of the column and of a in registers; a
 // workgroup of 256 threads takes 256 / L groups times C columns.  At step k every lane forms its part of G(k, :) . p from the row k of G
@@ -105,6 +106,10 @@ __global__ __launch_bounds__(HALS_THREADS) void k_sweep_hals(T* __restrict__ P, 
 	for (int c = 0; c < C; ++c) {
 		const long y = y0 + c * GROUPS + grp;
 		const long base = y * RP;
+		if (y >= len_valid) {                        // (the slabs of a padding column need not be 0: its sweep is discarded)
+#pragma unroll
+			for (int e = 0; e < E; ++e) h[c][e] = T(0);
+		}
 #pragma unroll
 		for (int e = 0; e < E; ++e) P[base + e * L + lane] = h[c][e];
 		if (ps != nullptr) {

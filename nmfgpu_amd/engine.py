@@ -537,6 +537,59 @@ def op_tri_update(P: np.ndarray, num: np.ndarray, Q: np.ndarray, *, old_colsq: O
     return out
 
 
+def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_valid: int, *, ps: Optional[np.ndarray] = None,
+                  sumsq_part: Optional[np.ndarray] = None):
+    """One launch of the HALS sweep (nmfamd_op_hals_sweep_*) on padded arrays: P (len_pad, RP) panel columns, slabs (S, slab_stride) with
+    slab_stride >= len_pad * RP (slab s is the first len_pad * RP values of row s; the rest of the row is a gap the kernel must not read), G (RP, RP).
+    ps (len_pad values) and sumsq_part ((len_pad // 16) * RP values), when given, are copied in before the launch, so entries the kernel leaves
+    alone keep the caller's sentinels.  Returns a dict: `P` (the new panel), `ps`, `sumsq_part` (parts x RP) and `parts`."""
+    dt = np.dtype(P.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("float32 or float64")
+    P = np.array(P, dtype=dt, order="C")
+    slabs = np.ascontiguousarray(slabs, dtype=dt); G = np.ascontiguousarray(G, dtype=dt)
+    len_pad, RP = P.shape
+    S, stride = slabs.shape
+    if G.shape != (RP, RP) or stride < len_pad * RP:
+        raise ValueError("shapes: P (len_pad, RP); slabs (S, >= len_pad * RP); G (RP, RP)")
+    if ps is not None:
+        ps = np.array(ps, dtype=dt).reshape(-1)
+        if ps.size != len_pad:
+            raise ValueError("ps must hold len_pad values")
+    if sumsq_part is not None:
+        sumsq_part = np.array(sumsq_part, dtype=dt).reshape(-1)
+        if sumsq_part.size < (len_pad // 16) * RP:
+            raise ValueError("sumsq_part must hold (len_pad // 16) * RP values")
+    parts = C.c_int(0)
+    fn = library().nmfamd_op_hals_sweep_f32 if dt == np.float32 else library().nmfamd_op_hals_sweep_f64
+    st = fn(C.c_void_p(P.ctypes.data), C.c_void_p(slabs.ctypes.data), S, C.c_long(stride), C.c_void_p(G.ctypes.data), RP, int(r), len_pad,
+            int(len_valid), C.c_void_p(ps.ctypes.data) if ps is not None else None,
+            C.c_void_p(sumsq_part.ctypes.data) if sumsq_part is not None else None, C.byref(parts))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_hals_sweep")
+    k = parts.value
+    return {"P": P, "ps": ps, "sumsq_part": None if sumsq_part is None else sumsq_part[:k * RP].reshape(k, RP), "parts": k}
+
+
+def op_hals_normalize(Wt: np.ndarray, H: np.ndarray, sumsq_part: np.ndarray):
+    """The HALS column normalisation (nmfamd_op_hals_normalize_*): Wt (mpad, RP) and H (npad, RP) panels, sumsq_part (parts, RP) partial
+    sums of squares.  Returns a dict: `Wt`, `H` (new arrays; the inputs are not changed)."""
+    dt = np.dtype(Wt.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("float32 or float64")
+    Wt = np.array(Wt, dtype=dt, order="C"); H = np.array(H, dtype=dt, order="C")
+    sq = np.ascontiguousarray(sumsq_part, dtype=dt)
+    mpad, RP = Wt.shape
+    npad = H.shape[0]
+    if H.shape[1] != RP or sq.ndim != 2 or sq.shape[1] != RP:
+        raise ValueError("shapes: Wt (mpad, RP); H (npad, RP); sumsq_part (parts, RP)")
+    fn = library().nmfamd_op_hals_normalize_f32 if dt == np.float32 else library().nmfamd_op_hals_normalize_f64
+    st = fn(C.c_void_p(Wt.ctypes.data), RP, mpad, C.c_void_p(H.ctypes.data), npad, C.c_void_p(sq.ctypes.data), sq.shape[0])
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_hals_normalize")
+    return {"Wt": Wt, "H": H}
+
+
 def host_kmeans(data: np.ndarray, k: int, *, seed: int = 0, iterations: int = 100, threshold: float = 0.005):
     """The host-side Lloyd k-means behind computeKMeans and the KMeans*/EInNMF initialisers, without a
     device or context (nmfamd_host_kmeans_*).  Returns (clusters m x k, membership, passes)."""

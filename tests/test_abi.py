@@ -36,6 +36,12 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} is declared but not exported"
 
 
+def test_hals_test_entries_are_exported():
+    lib = na.library()
+    for name in ("nmfamd_op_hals_sweep_f32", "nmfamd_op_hals_sweep_f64", "nmfamd_op_hals_normalize_f32", "nmfamd_op_hals_normalize_f64"):
+        assert name in _declared_c_symbols("nmfgpu_amd.h") and hasattr(lib, name), name
+
+
 def test_struct_layout_matches_reference_table():
     # SURVEY.md section 8b, measured on the reference header with offsetof
     assert C.sizeof(na.MatrixDescription) == 44

@@ -75,6 +75,9 @@ PARITY = [
     (500, 300, 7, np.float64), (1000, 777, 64, np.float64), (1000, 777, 100, np.float64), (1000, 777, 150, np.float64),
     (1000, 777, 450, np.float64),
     (40000, 300, 64, np.float32),
+    # the sweep instantiations no case above reaches: fp32 RP 384, fp64 RP 256, 320, 384, 512
+    (1000, 777, 300, np.float32),
+    (600, 500, 200, np.float64), (600, 500, 300, np.float64), (600, 500, 350, np.float64), (1000, 777, 500, np.float64),
 ]
 
 
@@ -268,3 +271,159 @@ def test_compute_refusals(params):
     V, W, H = problem(300, 200, 8, np.float32)
     res = na.compute(V, W, H, algorithm=na.NmfAlgorithm.HALS, iterations=10, parameters=params)
     assert res == na.ResultType.ErrorInvalidArgument
+
+
+# ------------------------------------------------------------------ one step from a drifted state
+
+def per_column(got, want, tol, what):
+    """Every column within tol relative, with an absolute floor of 1 % of the RMS column norm (clamped columns near zero); a wrong tile or row block
+    is off by O(1)."""
+    got, want = got.astype(np.float64), want.astype(np.float64)
+    floor = 1e-2 * np.linalg.norm(want) / np.sqrt(want.shape[1])
+    err = np.linalg.norm(got - want, axis=0)
+    lim = tol * np.maximum(np.linalg.norm(want, axis=0), floor)
+    assert (err <= lim).all(), (what, int(np.argmax(err / lim)), float((err / lim).max()))
+
+
+@pytest.mark.parametrize("m,n,r,dtype", [(1000, 777, 450, np.float32), (1000, 777, 300, np.float32), (1000, 777, 500, np.float64)])
+def test_one_step_from_a_drifted_state(m, n, r, dtype):
+    """After 20 iterations on random V (where fp32 trajectories drift apart), one engine iteration and one fp64 restatement iteration from the
+    same downloaded state: per column of W and H 1e-3 (fp32; 5e-8 in the global norm was measured) or 1e-9 (fp64), the global norms at 2e-4 /
+    1e-9, and the reported error at 1e-5 / 1e-9 -- the check the 20-iteration fp32 test at r = 450 has to skip."""
+    tol_c, tol_f, tol_e = (1e-3, 2e-4, 1e-5) if dtype == np.float32 else (1e-9, 1e-9, 1e-9)
+    V, W, H = problem(m, n, r, dtype, seed=m + n + r + 1)
+    eng = engine(V, W, H)
+    eng.iterate(20, error_every=0, last_iteration=20)
+    W0, H0 = eng.get_factors()
+    eng.iterate(1, first_iteration=21, error_every=0, last_iteration=21)
+    Wg, Hg = eng.get_factors()
+    reported = eng.frobenius
+    W64, H64, err = ref.iteration(V, W0, H0)
+    check_padding(eng)
+    eng.close()
+    per_column(Wg, W64, tol_c, "W")
+    per_column(Hg, H64, tol_c, "H")
+    assert rel(Wg, W64) < tol_f and rel(Hg, H64) < tol_f, (rel(Wg, W64), rel(Hg, H64))
+    assert abs(reported - err) <= tol_e * err, (reported, err)
+
+
+# ------------------------------------------------------------------ ragged shapes at every rank boundary
+
+def _ragged_cases():
+    out = []
+    for dtype, rps in ((np.float32, [64, 128, 256, 384, 512]), (np.float64, [64, 128, 192, 256, 320, 384, 448, 512])):
+        rs = [1] + [q for RP in rps[:-1] for q in (RP, RP + 1)] + [512]
+        for seed in range(24):
+            rng = np.random.default_rng(1000 * (dtype == np.float64) + seed)
+            r = rs[seed % len(rs)] if seed < len(rs) else int(rng.choice(rs))
+            pick = lambda: int(rng.choice([1, 2, 127, 128, 129, int(rng.integers(3, 300)), r + int(rng.integers(0, 40))]))
+            m, n = pick(), pick()
+            out.append(pytest.param(m, n, r, dtype, seed, id=f"{np.dtype(dtype).name}-{m}x{n}-r{r}-s{seed}"))
+    return out
+
+
+@pytest.mark.parametrize("m,n,r,dtype,seed", _ragged_cases())
+def test_seeded_ragged_sweep(m, n, r, dtype, seed):
+    """m, n in {1, 2, 127, 128, 129, ...}, often below r, with r on both sides of every padded-rank boundary: fp64 3 iterations at 1e-9; fp32 one
+    iteration at 2e-4.  The padding stays exactly 0 throughout.
+    Where m or n is below r, G (or H H^T) is singular: once a sweep has brought the residual to rounding level, later steps divide that noise by
+    diagonal entries that can be tiny (n = 1: H H^T(k, k) = h_k^2), and the result is set by rounding, in fp64 too (2 x 127 at r = 193: a numpy
+    restatement with the dot products over reversed coordinates lands 0.59 away from the forward one in W).  There each bound is the larger
+    of the one above and 10 x the distance of such a restatement (ref.iteration_in, in the engine's dtype, reversed order) from the fp64 one:
+    derived from the problem, never from GPU output."""
+    V, W, H = problem(m, n, r, dtype, seed=seed)
+    eng = engine(V, W, H)
+    iters = 3 if dtype == np.float64 else 1
+    eng.iterate(iters, error_every=0, last_iteration=iters)
+    Wg, Hg = eng.get_factors()
+    check_padding(eng)
+    eng.close()
+    W64, H64, _ = ref.run(V, W, H, iters)
+    tol_w = tol_h = 1e-9 if dtype == np.float64 else 2e-4
+    if min(m, n) < r:
+        Wx, Hx = W, H
+        for _ in range(iters):
+            Wx, Hx = ref.iteration_in(V, Wx, Hx, dtype, reverse=True)
+        tol_w, tol_h = max(tol_w, 10 * rel(Wx, W64)), max(tol_h, 10 * rel(Hx, H64))
+    assert rel(Wg, W64) < tol_w and rel(Hg, H64) < tol_h, (rel(Wg, W64), tol_w, rel(Hg, H64), tol_h)
+
+
+# ------------------------------------------------------------------ degenerate columns
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_zero_column_and_row_stay_zero(dtype):
+    """W(:, k) = 0 with H(k, :) = 0: G(k, k) = 0 skips row k of H, H H^T(k, k) = 0 skips column k of W, and the d = 0 guard leaves it: exact zeros."""
+    tol = 2e-4 if dtype == np.float32 else 1e-9
+    V, W, H = problem(300, 200, 12, dtype, seed=41)
+    W[:, 5] = 0.0
+    H[5, :] = 0.0
+    eng = engine(V, W, H)
+    eng.iterate(3, error_every=0, last_iteration=3)
+    Wg, Hg = eng.get_factors()
+    check_padding(eng)
+    eng.close()
+    assert (Wg[:, 5] == 0).all() and (Hg[5, :] == 0).all()
+    W64, H64, _ = ref.run(V, W, H, 3)
+    assert rel(Wg, W64) < tol and rel(Hg, H64) < tol, (rel(Wg, W64), rel(Hg, H64))
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_zero_column_alone(dtype):
+    """W(:, k) = 0 alone: row k of H is skipped in the H step (it keeps its values), then column k of W is updated from them."""
+    tol = 2e-4 if dtype == np.float32 else 1e-9
+    V, W, H = problem(300, 200, 12, dtype, seed=43)
+    W[:, 7] = 0.0
+    eng = engine(V, W, H)
+    eng.iterate(1, error_every=0, last_iteration=1)
+    Wg, Hg = eng.get_factors()
+    check_padding(eng)
+    eng.close()
+    W64, H64, _ = ref.run(V, W, H, 1)
+    assert np.abs(W64[:, 7]).max() > 0                      # (the restatement updates it: the case is not vacuous)
+    assert rel(Wg, W64) < tol and rel(Hg, H64) < tol, (rel(Wg, W64), rel(Hg, H64))
+
+
+# ------------------------------------------------------------------ padding after every product mode
+
+@pytest.mark.parametrize("dtype,precision,valu", [
+    (np.float32, "native", False), (np.float32, "fp32_mfma", False), (np.float32, "bf16", False), (np.float32, "native", True),
+    (np.float64, "native", False), (np.float64, "native", True)])
+def test_padding_after_every_product_mode(dtype, precision, valu, monkeypatch):
+    """Ragged m and n (mpad 384 != npad 256): every product mode leaves the padded panels exactly 0 after the sweep and the normalisation."""
+    if valu:
+        monkeypatch.setenv("NMFAMD_FORCE_VALU", "1")
+    V, W, H = problem(301, 130, 20, dtype, seed=47)
+    eng = engine(V, W, H, precision=precision)
+    g = eng.geometry()
+    assert g["padded_m"] != g["padded_n"]
+    if valu:
+        assert g["product_kernel"] == 4
+    eng.iterate(3, error_every=1)
+    check_padding(eng)
+    Wg, Hg = eng.get_factors()
+    eng.close()
+    assert np.isfinite(Wg).all() and np.isfinite(Hg).all() and np.isfinite(eng.frobenius)
+
+
+# ------------------------------------------------------------------ through nmfgpu::compute in double, and the rank limit
+
+def test_compute_copy_existing_double():
+    V, W, H = problem(800, 600, 12, np.float64, seed=23)
+    W64, H64, errs = ref.run(V, W, H, 30)
+    s = na.Summary()
+    res = na.compute(V, W, H, algorithm=na.NmfAlgorithm.HALS, iterations=30, summary=s)
+    assert res == na.ResultType.Success, res
+    assert rel(W, W64) < 1e-9 and rel(H, H64) < 1e-9, (rel(W, W64), rel(H, H64))
+    rec = s.record(0)
+    assert abs(rec.frobenius - errs[-1]) <= 1e-9 * errs[-1], (rec.frobenius, errs[-1])
+    assert rec.numIterations == 30
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_rank_513_is_refused(dtype):
+    V, W, H = problem(600, 600, 513, dtype)
+    with pytest.raises(na.EngineError) as info:
+        na.Engine(600, 600, 513, "hals", dtype=dtype)
+    assert info.value.status == 1
+    res = na.compute(V, W, H, algorithm=na.NmfAlgorithm.HALS, iterations=2)
+    assert res != na.ResultType.Success, res

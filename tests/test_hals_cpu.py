@@ -4,6 +4,7 @@ import subprocess
 import tempfile
 
 import numpy as np
+import pytest
 
 from tests import hals_reference as ref
 
@@ -96,3 +97,68 @@ def test_restatement_is_gauss_seidel():
     gs = ref.h_step(V, W, H)
     assert np.allclose(gs[0], jacobi[0])                    # row 0 sees no updated rows
     assert not np.allclose(gs[1:], jacobi[1:])
+
+
+# ------------------------------------------------------------------ the sweep yardstick of tests/test_gpu_hals_sweep.py
+
+def _bound(P, slabs, G, r, len_valid, u):
+    return ref.sweep_bound(P[:len_valid].T, slabs[:, :len_valid].transpose(0, 2, 1), G, r, u).T
+
+
+def test_sweep_is_the_restatement_step():
+    """h_step and w_step are one sweep each; the sweep leaves rows >= r alone."""
+    rng = np.random.default_rng(2)
+    V, W, H = rng.random((25, 18)), rng.random((25, 4)), rng.random((4, 18))
+    H1 = ref.h_step(V, W, H)
+    G, A = W.T @ W, W.T @ V
+    assert np.array_equal(H1, ref.sweep(H, A, G))
+    P = np.vstack([H, rng.random((2, 18))])
+    out = ref.sweep(P, np.vstack([A, np.zeros((2, 18))]), np.pad(G, ((0, 2), (0, 2))), r=4)
+    assert np.array_equal(out[:4], H1) and np.array_equal(out[4:], P[4:])
+
+
+@pytest.mark.parametrize("RP", [64, 128, 256, 384, 512])
+def test_float32_sweeps_stay_inside_the_bound(RP):
+    u = 2.0 ** -24
+    rng = np.random.default_rng(RP)
+    for r, S in ((RP, 1), (RP - 1, 3), (RP // 2 + 1, 2)):
+        P, slabs, G = ref.dominant_case(RP, r, 128, 12, S, rng, np.float32)
+        want = ref.panel_sweep(P, slabs, G, r, 12)
+        b = _bound(P, slabs, G, r, 12, u)
+        for order in ("sequential", "reversed"):
+            got = ref.sweep_f32(P, slabs, G, r, 12, order)
+            assert (np.abs(got - want) <= b).all(), (order, r, (np.abs(got - want) / b).max())
+        # (not vacuous: on a diagonally dominant G the bound stays a small multiple of the local error)
+        assert b.max() < 1e-3, b.max()
+
+
+@pytest.mark.parametrize("variant", ["jacobi", "drop_last_slab", "next_row"])
+def test_wrong_sweeps_fall_outside_the_bound(variant):
+    u = 2.0 ** -24
+    rng = np.random.default_rng(17)
+    for RP, r in ((64, 64), (256, 200), (512, 511)):
+        P, slabs, G = ref.dominant_case(RP, r, 128, 12, 3, rng, np.float32)
+        want = ref.panel_sweep(P, slabs, G, r, 12)
+        b = _bound(P, slabs, G, r, 12, u)
+        got = ref.sweep_f32(P, slabs, G, r, 12, variant=variant)
+        assert (np.abs(got - want) > b).any(), (variant, RP, r)
+
+
+@pytest.mark.parametrize("case", ["layout_case", "order_case"])
+def test_exact_constructions_are_exact_in_float32(case):
+    rng = np.random.default_rng(23)
+    make = getattr(ref, case)
+    for RP, r, lv, S in ((64, 1, 1, 1), (64, 64, 63, 3), (384, 295, 255, 3), (320, 276, 17, 1), (512, 512, 255, 3)):
+        P, slabs, G = make(RP, r, 256, lv, S, rng, np.float32)
+        want = ref.panel_sweep(P, slabs, G, r, lv)
+        for order in ("sequential", "reversed"):
+            assert np.array_equal(ref.sweep_f32(P, slabs, G, r, lv, order), want), (case, RP, r, order)
+        if case == "layout_case":
+            k = np.arange(r)
+            a = slabs.astype(np.float64).sum(axis=0)[:lv, :r]
+            assert np.array_equal(want, np.maximum(0.0, a / G[k, k].astype(np.float64)))
+            assert len(np.unique(a)) == a.size and np.abs(a).max() <= 2 ** 16
+        else:
+            # the Gauss-Seidel order is visible: the Jacobi form of the same step differs somewhere (r > 1)
+            if r > 1:
+                assert not np.array_equal(ref.sweep_f32(P, slabs, G, r, lv, variant="jacobi"), want)
