@@ -46,7 +46,8 @@ enum { NMFAMD_MU = 0, NMFAMD_GDCLS = 1, NMFAMD_ALS = 2, NMFAMD_ACLS = 3, NMFAMD_
 /* sparse formats = nmfgpu::StorageFormat (include/nmfgpu.h:177-186) */
 enum { NMFAMD_DENSE = 0, NMFAMD_CSR = 1, NMFAMD_CSC = 2, NMFAMD_COO = 3 };
 
-/* Algorithm parameters, the reference's name/value list (Interface.cpp:41-49, 249-326) as a struct. */
+/* Algorithm parameters, the reference's name/value list (Interface.cpp:41-49, 249-326) as a struct.  Fields are only ever added at the END:
+ * callers build the struct from this header (a struct declared by hand from an older copy is shorter than what the library reads). */
 typedef struct nmfamd_params {
 	double lambda;   /* GDCLS  "lambda"  */
 	double lambdaW;  /* ACLS / AHCLS "lambdaW" */
@@ -60,6 +61,10 @@ typedef struct nmfamd_params {
 	double precision;       /* Parameter "precision", float engines only.  0 = fp32 accuracy: products on the bf16 matrix pipe with every
 	                           operand split exactly into three bf16 terms (kernels_x3.hip); -1 = native fp32 MFMA instructions;
 	                           1 = operands rounded to bf16 (reduced precision, half the bytes of V per pass) */
+	double missing_values;  /* Parameter "missingValues".  1 = fit the observed entries only (docs/MISSING.md): the stored entries of a sparse V, the
+	                           non-NaN entries of a dense V (zeros included); Multiplicative with divergence 0 only, implies sparse_compute.  Such an
+	                           engine has no three-phase / sharded form: nmfamd_engine_h_step / _w_products / _w_finish and nmfamd_sharded_create return
+	                           NMFAMD_INVALID_ARGUMENT; nmfamd_engine_frobenius / _rmsd report the error over the observed entries */
 } nmfamd_params;
 
 typedef struct nmfamd_engine nmfamd_engine;  /* opaque; owns every device buffer of one factorisation */

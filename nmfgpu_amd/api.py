@@ -258,7 +258,11 @@ def compute(V, W: np.ndarray, H: np.ndarray, *, algorithm: NmfAlgorithm = NmfAlg
             interrupt=None, description_out: Optional[list] = None) -> ResultType:
     """nmfgpu::compute (ref include/nmfgpu.h:298-299).  V: Fortran ndarray or a MatrixDescription
     (sparse); W (m x r) and H (r x n) are Fortran arrays that provide the start values for
-    CopyExisting and receive the result."""
+    CopyExisting and receive the result.
+
+    ``parameters={"missingValues": 1}`` fits the observed entries only (docs/MISSING.md): the stored entries of a sparse V
+    (explicit zeros included), the non-NaN entries of a dense V.  Multiplicative algorithm, CopyExisting or AllRandomValues
+    start, one GPU, at most 256 features; the reported Frobenius error / RMSD are those over the observed entries."""
     if W.dtype != H.dtype:
         raise TypeError("W and H must share a dtype")
     d = NmfDescription()

@@ -222,6 +222,55 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 			return ResultType::ErrorInvalidArgument;
 		}
 	}
+	{
+		// "missingValues" = 1 (docs/MISSING.md): the objective over the observed entries only -- the stored entries of a sparse V, the non-NaN entries of a dense
+		// one.  Multiplicative with the Frobenius objective, one GPU, padded rank <= 256 (the sparse kernels), and a start that does not read V as if a missing
+		// entry were a zero (the host-side k-means, mean-column, EInNMF and NNDSVD starts do)
+		const int idx = parameter_index(d.parameters, d.numParameters, "missingValues");
+		if (idx >= 0) {
+			const double v = d.parameters[idx].value;
+			if (!(v == 0.0 || v == 1.0)) {
+				log_error("[ERROR] Parameter 'missingValues' has to be 0 or 1!");
+				return ResultType::ErrorInvalidArgument;
+			}
+			prm.missing_values = v;
+		}
+		if (prm.missing_values != 0) {
+			if (d.algorithm != NmfAlgorithm::Multiplicative) {
+				log_error("[ERROR] 'missingValues' is only available for the Multiplicative algorithm!");
+				return ResultType::ErrorInvalidArgument;
+			}
+			if (prm.divergence != 0) {
+				log_error("[ERROR] 'missingValues' does not combine with 'divergence' (no masked KL update)!");
+				return ResultType::ErrorInvalidArgument;
+			}
+			if ((d.initMethod != NmfInitializationMethod::CopyExisting && d.initMethod != NmfInitializationMethod::AllRandomValues) ||
+			    hostinit::nndsvd_variant(d.parameters, d.numParameters) >= 0) {
+				log_error("[ERROR] 'missingValues' needs the CopyExisting or AllRandomValues start (the other starts read missing entries as zeros)!");
+				return ResultType::ErrorInvalidArgument;
+			}
+			if (nmfamd::padded_rank((int)d.features, 4) > 256) {
+				log_error("[ERROR] 'missingValues' supports at most 256 features!");
+				return ResultType::ErrorInvalidArgument;
+			}
+			const MatrixDescription<T>& V = d.inputMatrix;
+			bool observed = false;
+			switch (V.format) {
+			case StorageFormat::Dense:
+				for (unsigned j = 0; j < V.columns && !observed && V.dense.values != nullptr; ++j)
+					for (unsigned i = 0; i < V.rows && !observed; ++i) observed = !std::isnan(V.dense.values[(size_t)j * V.dense.leadingDimension + i]);
+				break;
+			case StorageFormat::CSR: observed = V.csr.nnz > 0; break;
+			case StorageFormat::CSC: observed = V.csc.nnz > 0; break;
+			case StorageFormat::COO: observed = V.coo.nnz > 0; break;
+			}
+			if (!observed) {
+				log_error("[ERROR] 'missingValues': the input matrix has no observed entry!");
+				return ResultType::ErrorInvalidArgument;
+			}
+			prm.sparse_compute = 1;
+		}
+	}
 	if (d.inputMatrix.rows == 0 || d.inputMatrix.columns == 0 || d.features == 0 ||
 	    d.outputMatrixW.format != StorageFormat::Dense || d.outputMatrixH.format != StorageFormat::Dense) {
 		log_error("[ERROR] Empty problem or non-dense output matrices!");
@@ -239,6 +288,10 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		if (idx >= 0) num_gpus = (int)d.parameters[idx].value;
 		idx = parameter_index(d.parameters, d.numParameters, "shardMode");
 		if (idx >= 0) shard_mode = d.parameters[idx].value != 0 ? nmfamd::SHARD_REPLICATED : nmfamd::SHARD_ROW_BLOCKS;
+		if (num_gpus > 1 && prm.missing_values != 0) {
+			log_error("[ERROR] 'numGpus' > 1 is not available with 'missingValues'!");
+			return ResultType::ErrorInvalidArgument;
+		}
 		if (num_gpus > 1 && d.algorithm == NmfAlgorithm::HALS) {
 			log_error("[ERROR] 'numGpus' > 1 is not available for the HALS algorithm!");
 			return ResultType::ErrorInvalidArgument;

@@ -97,7 +97,7 @@ static size_t memory_side_cache_bytes(const hipDeviceProp_t& prop) {
 
 template <typename T>
 Engine<T>::Engine(int m, int n, int r, int algorithm, const AlgorithmParams& params)
-	: m_(m), n_(n), r_(r), RP_(padded_rank(r, (params.sparse_compute != 0 || params.divergence != 0) ? 4 : sizeof(T))), alg_(algorithm), prm_(params), mpad_(pad128(m)), npad_(pad128(n)) {}
+	: m_(m), n_(n), r_(r), RP_(padded_rank(r, (params.sparse_compute != 0 || params.divergence != 0 || params.is_masked()) ? 4 : sizeof(T))), alg_(algorithm), prm_(params), mpad_(pad128(m)), npad_(pad128(n)) {}
 
 template <typename T>
 Status Engine<T>::hip_fail(hipError_t e, const char* what) {
@@ -140,7 +140,7 @@ Engine<T>::~Engine() {
 	if (inv_work_) (void)hipFree(inv_work_);
 	if (range_flag_) (void)hipFree(range_flag_);
 	{
-		void* sp[] = {csr_ptr_, csr_idx_, csc_ptr_, csc_idx_, csc_from_csr_, csr_val_, csc_val_, q_, q2_, t_vwh_, t_kl_, rowsum_part_, sW_, sH_, kl_scale_, csr_bptr_, csc_bptr_, kl_part_, kl_tpart_};
+		void* sp[] = {csr_ptr_, csr_idx_, csc_ptr_, csc_idx_, csc_from_csr_, csr_val_, csc_val_, q_, q2_, t_vwh_, t_kl_, rowsum_part_, sW_, sH_, kl_scale_, csr_bptr_, csc_bptr_, kl_part_, kl_tpart_, msq_part_};
 		for (void* b : sp) if (b) (void)hipFree(b);
 	}
 	{ void* bb[] = {Vb_, Vtb_, Wtb_, Hb_, Wx3_, Hx3_, qx3_, gram_tri_part_, Gw_raw_, Gh_raw_, colsq_}; for (void* b : bb) if (b) (void)hipFree(b); }
@@ -192,7 +192,9 @@ Status Engine<T>::allocate() {
 	if (RP_ == 64 && r_ <= 32 && tuning_env("NMFAMD_FP_FULL_WIDTH") == nullptr) { planH_.nb = f64 ? 2 : 1; planW_.nb = planH_.nb; }      // (fp64 counts 16-column tiles)
 	if (!mfma) { planH_.splits = 1; planW_.splits = 1; planH_.th = planW_.th = 128; planH_.xtiles = (int)(pad128(n_) / 128); planW_.xtiles = (int)(pad128(m_) / 128); }
 	tiled_ = mfma;
-	sparse_ = prm_.sparse_compute != 0 || prm_.divergence != 0;      // (the SpMM / KL kernels gather RP / 64 = 1, 2 or 4 values per lane: sparse runs keep the 128-column padding in either precision, see the constructor)
+	// (the SpMM / KL / masked kernels gather RP / 64 = 1, 2 or 4 values per lane: sparse runs keep the 128-column padding in either precision, see the constructor)
+	sparse_ = prm_.sparse_compute != 0 || prm_.divergence != 0 || prm_.is_masked();
+	if (prm_.is_masked() && (alg_ != ALG_MU || prm_.divergence != 0 || RP_ > 256)) { last_error_ = "missing values: multiplicative update with the Frobenius objective, rank <= 256"; return ST_INVALID; }
 	if (sparse_) {
 		if (alg_ != ALG_MU || RP_ > 256) return ST_INVALID;   // sparse compute: multiplicative update, padded rank 64 / 128 / 256
 		tiled_ = false;
@@ -346,6 +348,7 @@ Status Engine<T>::allocate() {
 		HIPX(dalloc(&sH_, RP_));
 		HIPX(dalloc(&kl_scale_, RP_));
 		HIPX(hipHostMalloc((void**)&pin_kl_, sizeof(T) * (2 * (size_t)m_ + 3 * (size_t)RP_)));
+		if (prm_.is_masked()) HIPX(dalloc(&msq_part_, (long)(MASKED_NORM_PARTS + 16) * RP_));      // (+ 16: launch_normalize_panel's compaction scratch)
 	}
 	HIPX(dalloc(&Wt_, panelW));
 	HIPX(dalloc(&H_, panelH));
@@ -544,6 +547,19 @@ Status Engine<T>::finish_upload(T* Vcol) {
 template <typename T>
 Status Engine<T>::upload_dense(const T* V, long ld) {
 	if (!V || ld < m_) return ST_INVALID;
+	if (sparse_ && prm_.is_masked()) {
+		// missing values: every entry that is not NaN is observed -- zeros included -- and becomes a stored entry
+		std::vector<int> rows, cols; std::vector<T> vals;
+		for (int j = 0; j < n_; ++j)
+			for (int i = 0; i < m_; ++i) {
+				const T v = V[(size_t)j * ld + i];
+				if (std::isnan(v)) continue;
+				if (!std::isfinite(v)) { last_error_ = "missing values: V holds an infinite value (NaN marks a missing entry)"; return ST_INVALID; }
+				rows.push_back(i); cols.push_back(j); vals.push_back(v);
+			}
+		if (vals.empty()) { last_error_ = "missing values: V has no observed entry"; return ST_INVALID; }
+		return upload_triplets(rows, cols, vals);
+	}
 	if (sparse_) {
 		// dense input on the sparse path: the non-zero entries become the stored entries
 		std::vector<int> rows, cols; std::vector<T> vals;
@@ -570,6 +586,12 @@ Status Engine<T>::upload_dense(const T* V, long ld) {
 template <typename T>
 Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const int* b, long nnz, int base) {
 	if (format < 1 || format > 3 || nnz < 0 || (nnz > 0 && (!values || !a || !b))) return ST_INVALID;
+	if (sparse_ && prm_.is_masked()) {
+		// missing values: every stored entry is observed (stored zeros too, which both image builders keep); its value must be finite, and there must be one
+		if (nnz == 0) { last_error_ = "missing values: no stored entry"; return ST_INVALID; }
+		for (long p = 0; p < nnz; ++p)
+			if (!std::isfinite(values[p])) { last_error_ = "missing values: a stored value is not finite"; return ST_INVALID; }
+	}
 	if (sparse_) {
 		// the images are built on the device (kernels_sparse_setup.hip); what that path does not cover -- entries outside the matrix (dropped below), pointer
 		// arrays that do not ascend, a row or column longer than its LDS sort takes, no entries at all -- and NMFAMD_SPARSE_SETUP=host take the host path
@@ -588,6 +610,7 @@ Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const
 		if (format == 1) { for (int i = 0; i < m_; ++i) for (long p = (long)a[i] - base; p < (long)a[i + 1] - base && p < nnz; ++p) if (p >= 0) push(i, (long)b[p] - base, values[p]); }
 		else if (format == 2) { for (int j = 0; j < n_; ++j) for (long p = (long)a[j] - base; p < (long)a[j + 1] - base && p < nnz; ++p) if (p >= 0) push((long)b[p] - base, j, values[p]); }
 		else { for (long p = 0; p < nnz; ++p) push((long)a[p] - base, (long)b[p] - base, values[p]); }
+		if (prm_.is_masked() && vals.empty()) { last_error_ = "missing values: no stored entry inside the matrix"; return ST_INVALID; }
 		return upload_triplets(rows, cols, vals);
 	}
 	T* d_val = nullptr; int *d_a = nullptr, *d_b = nullptr;
@@ -1070,6 +1093,21 @@ long Engine<T>::error_terms_to_device(T* dst, long capacity) {
 
 template <typename T>
 void Engine<T>::finalize_error(bool resolve) {
+	if (masked_pending_) {
+		(void)hipEventSynchronize(err_event_);
+		h_psN_.assign(pin_kl_, pin_kl_ + m_);                       // per-row sums of squared residuals over the stored entries
+		masked_pending_ = false;
+		masked_unresolved_ = true;
+	}
+	if (resolve && masked_unresolved_) {
+		// a direct sum of residuals (not the trace formula), in double, row order; rmsd over the stored entries
+		double s = 0;
+		for (int i = 0; i < m_; ++i) s += (double)h_psN_[i];
+		frob2_ = s;
+		frob_ = std::sqrt(s);
+		rmsd_ = frob_ / std::sqrt((double)nnz_);
+		masked_unresolved_ = false;
+	}
 	if (kl_pending_) {
 		(void)hipEventSynchronize(err_event_);
 		h_psN_.assign(pin_kl_, pin_kl_ + m_);                       // per-row terms of tr(H^T W^T V)
@@ -1114,6 +1152,7 @@ template <typename T>
 Status Engine<T>::h_step(bool compute_error) {
 	// first call of an iteration in the sharded form: decides whether this iteration's products are timed
 	timing_now_ = timing_ && (timing_iter_++ % timing_stride_ == 0);
+	if (prm_.is_masked()) return masked_refuses("h_step");
 	if (prm_.divergence != 0) { kl_err_iter_ = compute_error; return kl_h_step(); }
 	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	return h_step_impl(compute_error);
@@ -1232,6 +1271,7 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 
 template <typename T>
 Status Engine<T>::w_products(T* exchange) {
+	if (prm_.is_masked()) return masked_refuses("w_products");
 	if (prm_.divergence != 0) return kl_w_products(exchange, kl_err_iter_);      // (sparse Frobenius compute shards through the code below: its two products are SpMMs over the shard's images)
 	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	T* ex_hht = exchange + (long)RP_ * mpad_;
@@ -1281,6 +1321,7 @@ Status Engine<T>::w_products(T* exchange) {
 
 template <typename T>
 Status Engine<T>::w_finish(const T* exchange, bool compute_error) {
+	if (prm_.is_masked()) return masked_refuses("w_finish");
 	if (prm_.divergence != 0) return kl_w_finish(exchange, compute_error);
 	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	const T eps = std::numeric_limits<T>::epsilon();
@@ -1356,6 +1397,7 @@ Status Engine<T>::w_finish(const T* exchange, bool compute_error) {
 // (one small launch; nothing to do for a team of one).  Rank-64 multiplicative update on the split-operand path only (direct_w_finish()).
 template <typename T>
 Status Engine<T>::w_finish_peers(const T* const* exchanges, int count, bool compute_error) {
+	if (prm_.is_masked()) return masked_refuses("w_finish_peers");
 	if (!direct_w_finish() || count < 1 || count > PEER_SLABS_MAX || exchanges == nullptr) return ST_INVALID;
 	if constexpr (std::is_same<T, float>::value) {
 		PeerSlabs panels = {}, hhts = {};
@@ -1375,6 +1417,7 @@ Status Engine<T>::w_finish_peers(const T* const* exchanges, int count, bool comp
 // ---- row-block form of the W step (one block per rank, see engine.h) -----------------------------------------------
 template <typename T>
 Status Engine<T>::w_update_rows(const T* num_rows, const T* hht, long row0, long rows, bool compute_error, T* colsq) {
+	if (prm_.is_masked()) return masked_refuses("w_update_rows");
 	if (alg_ != ALG_MU && alg_ != ALG_NSNMF) return ST_INVALID;
 	if (rows <= 0 || rows % 128 != 0 || row0 < 0 || row0 % 128 != 0 || row0 + rows > mpad_) return ST_INVALID;
 	const T eps = std::numeric_limits<T>::epsilon();
@@ -1406,6 +1449,7 @@ Status Engine<T>::w_update_rows(const T* num_rows, const T* hht, long row0, long
 
 template <typename T>
 Status Engine<T>::w_normalize_rows(long row0, long rows, T* colsq) {
+	if (prm_.is_masked()) return masked_refuses("w_normalize_rows");
 	if (rows <= 0 || rows % 128 != 0 || row0 < 0 || row0 + rows > mpad_) return ST_INVALID;
 	// colsq: the r sums of squares over ALL rows (one "partial"): kernel::normalizeColumns' sum > 0 ? x / sqrt(sum) : x
 	if constexpr (std::is_same<T, float>::value) {
@@ -1912,6 +1956,7 @@ template <typename T>
 Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 	const T eps = std::numeric_limits<T>::epsilon();
 	timing_now_ = timing_ && (timing_iter_++ % timing_stride_ == 0);
+	if (prm_.is_masked()) return iterate_masked(compute_error, constant_w);      // (before the KL test: a masked engine never has divergence != 0, allocate())
 	if (prm_.divergence != 0) return constant_w ? ST_INVALID : iterate_kl(compute_error);
 	if (fused_capable() && !constant_w) return iterate_mu64(compute_error);
 	if (fused64_capable() && !constant_w) return iterate_fused64(compute_error);
@@ -2257,6 +2302,44 @@ Status Engine<T>::iterate_kl(bool compute_error) {
 	if (keep_pending) kl_scale_pending_ = true;
 	else HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, norm_parts, stream_));
 	return ST_OK;
+}
+
+// Missing-value NMF (docs/MISSING.md): the multiplicative update with W H restricted to the stored entries Omega in both denominators, in the skeleton of
+// the reference's MU iteration -- H step, W step with the new H, column normalisation of W (H is not rescaled), error of the pair (W_{k-1}, H_k):
+//   H .*= (W^T V_Omega) ./ (W^T (W H)_Omega + eps)     one fused launch over the CSC image (kernels_masked.hip), H written in place
+//   W .*= (V_Omega H^T) ./ ((W H)_Omega H^T + eps)     one fused launch over the CSR image, W written in place, + per-row residual terms on error iterations
+//   normalise W                                          from the W launch's per-workgroup sums of squares (launch_normalize_panel)
+// The residual terms sum_p (v_p - W_{k-1}(i_p, :) . H_k(:, j_p))^2 per row come from the W launch's own dot products (it reads the old row of W) -- or, under
+// constant W, from the residual-only form of that launch; they travel to pinned memory and are summed in double by finalize_error().
+template <typename T>
+Status Engine<T>::iterate_masked(bool compute_error, bool constant_w) {
+	if (!sparse_ || nnz_ <= 0) { last_error_ = "missing values: no stored entry has been uploaded"; return ST_INVALID; }
+	const T eps = std::numeric_limits<T>::epsilon();
+	record_begin();
+	HIPX(launch_masked_half_step<T>(csc_ptr_, csc_idx_, csc_val_, H_, Wt_, RP_, eps, true, (T*)nullptr, (T*)nullptr, n_, stream_));
+	record_end();
+	if (!constant_w || compute_error) {
+		record_begin(1);
+		if (!constant_w) HIPX(launch_masked_half_step<T>(csr_ptr_, csr_idx_, csr_val_, Wt_, H_, RP_, eps, true, compute_error ? t_vwh_ : (T*)nullptr, msq_part_, m_, stream_));
+		else HIPX(launch_masked_half_step<T>(csr_ptr_, csr_idx_, csr_val_, Wt_, H_, RP_, eps, false, t_vwh_, (T*)nullptr, m_, stream_));
+		record_end();
+	}
+	if (compute_error) {
+		finalize_error(false);      // (the pinned buffer is about to be reused; an older copy is long complete)
+		HIPX(hipMemcpyAsync(pin_kl_, t_vwh_, sizeof(T) * m_, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipEventRecord(err_event_, stream_));
+		masked_pending_ = true;
+	}
+	if (!constant_w) HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, msq_part_, masked_norm_parts(m_), stream_));
+	return ST_OK;
+}
+
+template <typename T>
+Status Engine<T>::masked_refuses(const char* what) {
+	static thread_local char text[160];
+	std::snprintf(text, sizeof(text), "missing values: %s -- the masked update has no three-phase / sharded form", what);
+	last_error_ = text;
+	return ST_INVALID;
 }
 
 // ---- the KL update in the three phases of the column-sharded form ---------------------------------------------------------------------

@@ -24,6 +24,8 @@ struct AlgorithmParams {
 	double divergence = 0;      // 0: Frobenius objective, 1: generalised KL divergence (multiplicative update only)
 	double sparse_compute = 0;  // 1: keep V as CSR + CSC in HBM and multiply by SpMM instead of densifying
 	double precision = 0;       // 1: bf16 MFMA operands (V, W, H rounded to bf16 inside the two big products), fp32 everywhere else
+	double missing_values = 0;  // 1: fit the stored entries only (multiplicative update; implies sparse compute, kernels_masked.hip, docs/MISSING.md)
+	bool is_masked() const { return missing_values != 0; }
 };
 
 // Status codes shared with nmfgpu_amd.h (NMFAMD_*).
@@ -87,8 +89,10 @@ public:
 	bool direct_w_finish() const { return fused_capable() && gram_image_ && prm_.divergence == 0; }
 	// KL update (sparse V): the exchange also carries the row sums of the local H and, on error iterations, the per-row error terms:
 	//   [ numerator panel RP x mpad | H_g H_g^T RP x RP | rowsum(H_g) RP | tr terms mpad | KL terms mpad ]
-	long exchange_count() const { return (long)RP_ * mpad_ + (long)RP_ * RP_ + (prm_.divergence != 0 ? (long)RP_ + 2 * mpad_ : 0); }
+	// (masked engines have no three-phase form: no exchange)
+	long exchange_count() const { return prm_.is_masked() ? 0 : (long)RP_ * mpad_ + (long)RP_ * RP_ + (prm_.divergence != 0 ? (long)RP_ + 2 * mpad_ : 0); }
 	bool is_kl() const { return prm_.divergence != 0; }
+	bool is_masked() const { return prm_.is_masked(); }
 	// sharded runs: the error terms refer to the whole matrix (sorted tr(V^T V) terms of ALL columns, sum of ALL entries, total column count)
 	void set_error_globals(const std::vector<T>& vtv_sorted_all, double sum_v_all, long total_columns) { h_vtv_ = vtv_sorted_all; sum_v_ = sum_v_all; err_total_columns_ = total_columns; }
 	double sum_v() const { return sum_v_; }
@@ -202,6 +206,8 @@ private:
 	Status setup_kl_blocks();
 	bool sparse_setup_on_device_ = false;
 	Status iterate_kl(bool compute_error);            // KL-divergence multiplicative update (sparse mode)
+	Status iterate_masked(bool compute_error, bool constant_w);   // multiplicative update over the stored entries only (kernels_masked.hip)
+	Status masked_refuses(const char* what);          // ST_INVALID with last_error_ set: no three-phase / sharded form of the masked update
 	Status fetch_error_terms(int count_n);            // enqueue the copies, do not wait
 	void finalize_error(bool resolve);
 	void record_begin(int kind = 0);
@@ -267,6 +273,9 @@ private:
 	T* pin_kl_ = nullptr;
 	bool kl_pending_ = false, kl_unresolved_ = false;
 	std::vector<T> h_klrow_, h_sW_, h_sH_;
+	// masked update: per-workgroup sums of squares of the new W rows ([MASKED_NORM_PARTS + 16][RP]); the per-row residual terms travel through pin_kl_ (first m)
+	T* msq_part_ = nullptr;
+	bool masked_pending_ = false, masked_unresolved_ = false;
 	// rank-64 MU fast path: W is kept unnormalised with a pending column scale (kernels_mu64.hip)
 	float *gramW_part_ = nullptr, *gramH_part_ = nullptr, *scale_ = nullptr, *Graw64_ = nullptr;
 	bool w_col_split_ = false;       // V H^T from 128 x 32 workgroups and one slab (narrow column shards, Engine::init)

@@ -506,6 +506,18 @@ hipError_t launch_kl_update(T* P, const T* num, const T* den, int RP, int len_pa
 template <typename T>
 hipError_t launch_kl_sums(const T* sum_part, const T* sumsq_part, int parts, int RP, T* sums, hipStream_t stream, T* scale_out = nullptr);      // scale_out (optional): 1 / sqrt(sum of squares), 1 where that is 0
 
+// ---- missing-value NMF: the multiplicative update over the stored entries only (kernels_masked.hip, docs/MISSING.md) ----------------------------------------
+// One fused half-step: for every row < rows of A (RP in {64, 128, 256}), over its stored entries p (ptr / idx / val: the CSC image with A = H, B = Wt, or the CSR
+// image with A = Wt, B = H), wh_p = A(row, :) . B(idx[p], :), and in place
+//     A(row, :) <- A(row, :) .* (sum_p val[p] B(idx[p], :)) ./ (sum_p wh_p B(idx[p], :) + eps)           (update; false: the residual-only form)
+// t_res (optional): t_res[row] = sum_p (val[p] - wh_p)^2 with the old row.  sumsq_part (optional, update only): masked_norm_parts(rows) partial RP vectors of the
+// sums of squares of the new rows, for launch_normalize_panel (which needs NORM_GROUPS = 16 further RP vectors of scratch behind them).
+constexpr int MASKED_NORM_PARTS = 2048;
+int masked_norm_parts(int rows);
+template <typename T>
+hipError_t launch_masked_half_step(const int* ptr, const int* idx, const T* val, T* A, const T* B, int RP, T eps, bool update,
+                                   T* t_res, T* sumsq_part, int rows, hipStream_t stream);
+
 // ---- the CSR and CSC images of a sparse V built on the device (kernels_sparse_setup.hip) ----------------------------------------
 // flags (one int, zeroed by the caller): bit 0 = an entry outside the matrix or outside every pointer range, bit 1 = pointer array not ascending, bit 2 = the
 // entries are not in (row, column) order.  format: 1 CSR (a = rowPtr, outer = rows), 2 CSC (a = columnPtr, outer = columns), 3 COO (a = rows, b = columns)

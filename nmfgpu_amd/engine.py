@@ -20,7 +20,8 @@ class EngineError(RuntimeError):
 
 
 class _Params(C.Structure):
-    _fields_ = [(n, C.c_double) for n in ("lam", "lambdaW", "lambdaH", "alphaW", "alphaH", "theta", "divergence", "sparse_compute", "precision")]
+    _fields_ = [(n, C.c_double) for n in ("lam", "lambdaW", "lambdaH", "alphaW", "alphaH", "theta", "divergence", "sparse_compute", "precision",
+                                          "missing_values")]
 
 
 class _Geometry(C.Structure):
@@ -52,15 +53,18 @@ class Engine:
 
     def __init__(self, m: int, n: int, r: int, algorithm: str = "mu", dtype=np.float32, stream: int = 0,
                  lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence: str = "frobenius",
-                 sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1):
+                 sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False):
+        """missing_values=True: fit the observed entries only (docs/MISSING.md) -- the stored entries of upload_sparse, the non-NaN entries of
+        upload (zeros included).  Multiplicative update ("mu") with the Frobenius objective only; implies sparse_compute."""
         self._lib = library()
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise TypeError("float32 or float64")
         self.m, self.n, self.r = m, n, r
         self._ctor = dict(algorithm=algorithm, stream=stream, row_blocks=row_blocks,
-                          params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0}[divergence], float(sparse_compute),
-                                  {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision]])
+                          params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0}[divergence],
+                                  float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
+                                  float(missing_values)])
         self._h = None
         self._create()
         self._lib.nmfamd_engine_frobenius.restype = C.c_double
@@ -105,7 +109,8 @@ class Engine:
 
     def _upload(self, call, what: str):
         st = call()
-        if st == 6 and self._ctor["params"][8] == 0.0:
+        # (missing values: NaN marks a missing entry and the sparse images never see it -- no retry)
+        if st == 6 and self._ctor["params"][8] == 0.0 and self._ctor["params"][9] == 0.0:
             # NMFAMD_VALUE_RANGE: infinities, NaN, |v| > 2^126 or 0 < |v| < 2^-100 in V -- the split-operand product is not the
             # fp32 product there; recreate the engine on the native fp32 MFMA instructions, as nmfgpu::compute does.
             # The handle changes: anything created from the old one (a ShardedRun, w_panel_ptr()) is void -- upload V before
