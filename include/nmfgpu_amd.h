@@ -39,8 +39,8 @@ enum {
 	                            MFMA instructions).  nmfgpu::compute and the Python Engine do that by themselves. */
 };
 
-/* algorithm ids = nmfgpu::NmfAlgorithm (include/nmfgpu.h:107-114; NMFAMD_HALS is an extension: coordinate descent, docs/HALS.md -- no
-   parameters, no three-phase / sharded form) */
+/* algorithm ids = nmfgpu::NmfAlgorithm (include/nmfgpu.h:107-114; NMFAMD_HALS is an extension: coordinate descent, docs/HALS.md -- dense or
+   sparse compute, L1 / L2 penalties through nmfamd_engine_set_hals_penalties, no three-phase / sharded form) */
 enum { NMFAMD_MU = 0, NMFAMD_GDCLS = 1, NMFAMD_ALS = 2, NMFAMD_ACLS = 3, NMFAMD_AHCLS = 4, NMFAMD_NSNMF = 5, NMFAMD_HALS = 6 };
 
 /* sparse formats = nmfgpu::StorageFormat (include/nmfgpu.h:177-186) */
@@ -57,7 +57,8 @@ typedef struct nmfamd_params {
 	double theta;    /* nsNMF "theta" */
 	/* extensions without a reference counterpart (nmfgpu::compute: Parameter names "divergence", "sparseCompute") */
 	double divergence;      /* 0 = Frobenius objective; 1 = generalised KL divergence (Multiplicative only; implies sparse_compute) */
-	double sparse_compute;  /* 1 = keep V as CSR + CSC in HBM and use SpMM / SDDMM kernels instead of densifying (Multiplicative only) */
+	double sparse_compute;  /* 1 = keep V as CSR + CSC in HBM and use SpMM / SDDMM kernels instead of densifying (Multiplicative, and HALS with
+	                           divergence 0; rank <= 256) */
 	double precision;       /* Parameter "precision", float engines only.  0 = fp32 accuracy: products on the bf16 matrix pipe with every
 	                           operand split exactly into three bf16 terms (kernels_x3.hip); -1 = native fp32 MFMA instructions;
 	                           1 = operands rounded to bf16 (reduced precision, half the bytes of V per pass) */
@@ -72,7 +73,7 @@ typedef struct nmfamd_engine nmfamd_engine;  /* opaque; owns every device buffer
 /* Number of visible HIP devices (0 when there is none), and the library's build description. */
 NMFAMD_API int nmfamd_device_count(void);
 NMFAMD_API const char* nmfamd_build_info(void);
-/* Text of the last failed HIP call on this thread's engine (diagnostics only). */
+/* Text of the last failed HIP call on this thread's engine (diagnostics only).  e = NULL: why the last nmfamd_engine_create on this thread failed. */
 NMFAMD_API const char* nmfamd_engine_last_error(const nmfamd_engine* e);
 
 /* Creates the device state for V (m x n) ~ W (m x r) H (r x n) on the CURRENT HIP device.
@@ -106,6 +107,13 @@ NMFAMD_API int nmfamd_engine_randomize(nmfamd_engine* e, unsigned seed, int w, i
  * (nmfgpu::compute reads them after every error iteration, like the reference's dispatcher). */
 NMFAMD_API int nmfamd_engine_iterate(nmfamd_engine* e, int count, int first_iteration, int error_every, int last_iteration, int constant_w);
 NMFAMD_API int nmfamd_engine_synchronize(nmfamd_engine* e);
+/* HALS engines: the penalties of scikit-learn's coordinate descent, which then minimises
+ *   1/2 ||V - W H||^2 + l1W ||W||_1 + l1H ||H||_1 + 1/2 l2W ||W||^2 + 1/2 l2H ||H||^2     (docs/HALS.md has the mapping from alpha_W, alpha_H, l1_ratio).
+ * Valid any time between iterations (a regularisation path on one resident V); takes effect at the next nmfamd_engine_iterate.  While any of the four is
+ * non-zero the column normalisation of W is skipped; all zeros restores the unpenalised iteration.  nmfamd_engine_frobenius / _rmsd keep reporting
+ * ||V - W H||, not the penalised objective.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error) for a negative or non-finite value, and for a
+ * non-zero value on an engine of another algorithm. */
+NMFAMD_API int nmfamd_engine_set_hals_penalties(nmfamd_engine* e, double l1W, double l1H, double l2W, double l2H);
 /* Frobenius norm / RMSD of the most recent error iteration (IAlgorithm::frobeniusNorm / rmsd). */
 NMFAMD_API double nmfamd_engine_frobenius(nmfamd_engine* e);
 NMFAMD_API double nmfamd_engine_rmsd(nmfamd_engine* e);
@@ -332,6 +340,13 @@ NMFAMD_API int nmfamd_op_hals_sweep_f32(float* P, const float* slabs, int S, lon
                                         float* ps, float* sumsq_part, int* parts);
 NMFAMD_API int nmfamd_op_hals_sweep_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid,
                                         double* ps, double* sumsq_part, int* parts);
+/* The same launch with penalties l1, l2 >= 0 on the swept factor: step k divides by G(k, k) + l2 (skipped where that is <= 0) and its gradient is
+ * G(k, :) . p + l2 p(k) - a(k) + l1; ps is formed from the raw slabs.  l1 = l2 = 0 runs the unpenalised kernel.  NMFAMD_INVALID_ARGUMENT also for a negative
+ * or non-finite penalty. */
+NMFAMD_API int nmfamd_op_hals_sweep_pen_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid,
+                                            float* ps, float* sumsq_part, int* parts, float l1, float l2);
+NMFAMD_API int nmfamd_op_hals_sweep_pen_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid,
+                                            double* ps, double* sumsq_part, int* parts, double l1, double l2);
 /* The HALS column normalisation on host panels Wt [mpad][RP] and H [npad][RP] (both updated in place) from parts x RP partial sums of squares:
  * d(c) = sqrt(sum of the parts); where d(c) > 0, Wt(:, c) / d(c) and H(:, c) * d(c). */
 NMFAMD_API int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad, const float* sumsq_part, int parts);

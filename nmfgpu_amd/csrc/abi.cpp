@@ -213,12 +213,32 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		if (idx >= 0) prm.sparse_compute = d.parameters[idx].value;
 		idx = parameter_index(d.parameters, d.numParameters, "precision");
 		if (idx >= 0 && std::is_same<T, float>::value) prm.precision = d.parameters[idx].value;
-		if ((prm.divergence != 0 || prm.sparse_compute != 0) && d.algorithm != NmfAlgorithm::Multiplicative) {
-			log_error("[ERROR] 'divergence' / 'sparseCompute' are only available for the Multiplicative algorithm!");
+		// (HALS takes sparse compute with the Frobenius objective: its two products against V are the SpMM launches of the sparse multiplicative update)
+		const bool sparse_hals = d.algorithm == NmfAlgorithm::HALS && prm.divergence == 0;
+		if ((prm.divergence != 0 || prm.sparse_compute != 0) && d.algorithm != NmfAlgorithm::Multiplicative && !sparse_hals) {
+			log_error("[ERROR] 'divergence' is only available for the Multiplicative algorithm, 'sparseCompute' for Multiplicative and HALS!");
+			return ResultType::ErrorInvalidArgument;
+		}
+		if (sparse_hals && prm.sparse_compute != 0 && nmfamd::padded_rank((int)d.features, 4) > 256) {
+			log_error("[ERROR] 'sparseCompute' with the HALS algorithm supports at most 256 features!");
 			return ResultType::ErrorInvalidArgument;
 		}
 		if (prm.divergence != 0 && d.useConstantBasisVectors) {
 			log_error("[ERROR] The KL-divergence update does not support constant basis vectors!");
+			return ResultType::ErrorInvalidArgument;
+		}
+	}
+	{
+		// "l1W", "l1H", "l2W", "l2H" (docs/HALS.md): the penalties of scikit-learn's coordinate descent on the HALS sweeps; absent = 0
+		struct { const char* name; double* slot; } pen[] = {{"l1W", &prm.l1W}, {"l1H", &prm.l1H}, {"l2W", &prm.l2W}, {"l2H", &prm.l2H}};
+		for (auto& p : pen) {
+			const int idx = parameter_index(d.parameters, d.numParameters, p.name);
+			if (idx < 0) continue;
+			*p.slot = d.parameters[idx].value;
+		}
+		// (the engine's own rule, asked here so that a refusal comes before any device work)
+		if (const char* why = nmfamd::hals_penalties_fault(prm.l1W, prm.l1H, prm.l2W, prm.l2H, sizeof(T) == 4, d.algorithm == NmfAlgorithm::HALS)) {
+			log_error((std::string("[ERROR] ") + why).c_str());
 			return ResultType::ErrorInvalidArgument;
 		}
 	}

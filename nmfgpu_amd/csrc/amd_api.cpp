@@ -38,6 +38,9 @@ struct nmfamd_sharded {
 };
 
 namespace {
+// why the last nmfamd_engine_create on this thread failed (the engine that knew is gone): nmfamd_engine_last_error(NULL)
+thread_local std::string g_create_error;
+
 template <typename Fn32, typename Fn64>
 int dispatch(nmfamd_engine* e, Fn32 f32, Fn64 f64) {
 	if (!e) return NMFAMD_INVALID_ARGUMENT;
@@ -151,7 +154,7 @@ const char* nmfamd_build_info(void) {
 }
 
 const char* nmfamd_engine_last_error(const nmfamd_engine* e) {
-	if (!e) return "";
+	if (!e) return g_create_error.c_str();
 	return e->elem_bytes == 4 ? e->f->last_error() : e->d->last_error();
 }
 
@@ -162,6 +165,7 @@ int nmfamd_engine_create(int m, int n, int r, int algorithm, const nmfamd_params
 int nmfamd_engine_create_blocks(int m, int n, int r, int algorithm, const nmfamd_params* params, int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out) {
 	if (!out || (elem_bytes != 4 && elem_bytes != 8) || row_blocks < 1 || row_blocks > 64) return NMFAMD_INVALID_ARGUMENT;
 	*out = nullptr;
+	g_create_error.clear();
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	AlgorithmParams p;
 	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; }
@@ -173,7 +177,7 @@ int nmfamd_engine_create_blocks(int m, int n, int r, int algorithm, const nmfamd
 		if (elem_bytes == 4) { e->f.reset(new Engine<float>(m, n, r, algorithm, p)); e->f->set_stream((hipStream_t)stream); e->f->set_row_blocks(row_blocks); st = e->f->allocate(); }
 		else { e->d.reset(new Engine<double>(m, n, r, algorithm, p)); e->d->set_stream((hipStream_t)stream); e->d->set_row_blocks(row_blocks); st = e->d->allocate(); }
 	} catch (const std::bad_alloc&) { delete e; return NMFAMD_NO_HOST_MEMORY; }
-	if (st != ST_OK) { delete e; return (int)st; }
+	if (st != ST_OK) { g_create_error = nmfamd_engine_last_error(e); delete e; return (int)st; }
 	*out = e;
 	return NMFAMD_OK;
 }
@@ -303,6 +307,11 @@ int nmfamd_engine_iterate(nmfamd_engine* e, int count, int first_iteration, int 
 		return ST_OK;
 	};
 	return dispatch(e, run, run);
+}
+
+int nmfamd_engine_set_hals_penalties(nmfamd_engine* e, double l1W, double l1H, double l2W, double l2H) {
+	auto set = [&](auto& g) { return g.set_hals_penalties(l1W, l1H, l2W, l2H); };
+	return dispatch(e, set, set);
 }
 
 int nmfamd_engine_synchronize(nmfamd_engine* e) {
@@ -822,7 +831,7 @@ int nmfamd_op_factor_passes_f32(const float* P, long ldp, int r, int len, const 
 // they like into the padding.  No argument checks beyond the buffer sizes: the launchers decide what they accept.
 namespace {
 template <typename T>
-int op_hals_sweep(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part, int* parts) {
+int op_hals_sweep(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part, int* parts, T l1 = T(0), T l2 = T(0)) {
 	if (!P || !slabs || !G || !parts || S < 1 || RP < 1 || RP > 4096 || len_pad < 1 || slab_stride < (long)len_pad * RP) return NMFAMD_INVALID_ARGUMENT;
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	const int np = panel_sweep_hals_parts(RP, sizeof(T), len_pad);
@@ -835,7 +844,7 @@ int op_hals_sweep(T* P, const T* slabs, int S, long slab_stride, const T* G, int
 	if (ps && hipMemcpy(dPs.p, ps, sizeof(T) * (size_t)len_pad, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (sumsq_part && np > 0 && hipMemcpy(dSq.p, sumsq_part, sizeof(T) * (size_t)np * RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
 	const hipError_t err = launch_panel_sweep_hals<T>((T*)dP.p, (const T*)dS.p, S, slab_stride, (const T*)dG.p, RP, r, len_pad, len_valid,
-	                                                  ps ? (T*)dPs.p : nullptr, sumsq_part ? (T*)dSq.p : nullptr, nullptr);
+	                                                  ps ? (T*)dPs.p : nullptr, sumsq_part ? (T*)dSq.p : nullptr, nullptr, l1, l2);
 	if (err == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
 	if (err != hipSuccess || hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (hipMemcpy(P, dP.p, panel, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
@@ -871,6 +880,16 @@ int nmfamd_op_hals_sweep_f32(float* P, const float* slabs, int S, long slab_stri
 int nmfamd_op_hals_sweep_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid, double* ps,
                              double* sumsq_part, int* parts) {
 	return op_hals_sweep<double>(P, slabs, S, slab_stride, G, RP, r, len_pad, len_valid, ps, sumsq_part, parts);
+}
+
+int nmfamd_op_hals_sweep_pen_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid, float* ps,
+                                 float* sumsq_part, int* parts, float l1, float l2) {
+	return op_hals_sweep<float>(P, slabs, S, slab_stride, G, RP, r, len_pad, len_valid, ps, sumsq_part, parts, l1, l2);
+}
+
+int nmfamd_op_hals_sweep_pen_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid, double* ps,
+                                 double* sumsq_part, int* parts, double l1, double l2) {
+	return op_hals_sweep<double>(P, slabs, S, slab_stride, G, RP, r, len_pad, len_valid, ps, sumsq_part, parts, l1, l2);
 }
 
 int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad, const float* sumsq_part, int parts) {

@@ -177,6 +177,7 @@ template <typename T>
 Status Engine<T>::allocate() {
 	if (m_ <= 0 || n_ <= 0 || r_ <= 0 || alg_ < 0 || alg_ > ALG_HALS) return ST_INVALID;
 	if (alg_ == ALG_HALS && !panel_sweep_hals_available(RP_, sizeof(T))) { last_error_ = "HALS: no sweep kernel for this padded rank (fp32: 64 ... 512, fp64: multiples of 64 up to 512)"; return ST_INVALID; }
+	if (Status s = set_hals_penalties(prm_.l1W, prm_.l1H, prm_.l2W, prm_.l2H)) return s;      // (values that came with the parameters: the setter's checks, and its rounding of prm_ to T)
 	int dev = 0;
 	HIPX(hipGetDevice(&dev));
 	hipDeviceProp_t prop;
@@ -196,7 +197,12 @@ Status Engine<T>::allocate() {
 	sparse_ = prm_.sparse_compute != 0 || prm_.divergence != 0 || prm_.is_masked();
 	if (prm_.is_masked() && (alg_ != ALG_MU || prm_.divergence != 0 || RP_ > 256)) { last_error_ = "missing values: multiplicative update with the Frobenius objective, rank <= 256"; return ST_INVALID; }
 	if (sparse_) {
-		if (alg_ != ALG_MU || RP_ > 256) return ST_INVALID;   // sparse compute: multiplicative update, padded rank 64 / 128 / 256
+		// sparse compute: multiplicative update (either objective, masked or not) and HALS (Frobenius, not masked), padded rank 64 / 128 / 256
+		const char* why = nullptr;
+		if (alg_ == ALG_HALS && (prm_.divergence != 0 || prm_.is_masked())) why = "HALS: sparse compute with the Frobenius objective only (no 'divergence', no missing values)";
+		else if (alg_ != ALG_MU && alg_ != ALG_HALS) why = "sparse compute: multiplicative update and HALS only";
+		else if (RP_ > 256) why = "sparse compute needs rank <= 256 (the SpMM kernels gather 1, 2 or 4 values per lane)";
+		if (why != nullptr) { last_error_ = why; return ST_INVALID; }
 		tiled_ = false;
 		planH_.splits = planW_.splits = 1; planH_.th = planW_.th = 128;
 		planH_.xtiles = (int)(pad128(n_) / 128); planW_.xtiles = (int)(pad128(m_) / 128);
@@ -1222,7 +1228,8 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 		// coordinate sweep over every column of H against G = W^T W and the summed slabs of W^T V; ps: the per-column terms of tr(H^T W^T V), as PANEL_MU
 		// writes them.  No split image of the new H: the next product packs its operand itself.
 		if (Status s = product_h(F, nullptr, x3_ && wx3_valid_ && F == Wt_)) return s;
-		HIPX(launch_panel_sweep_hals<T>(H_, slabs_, S, slab_stride_, G_, RP_, r_, (int)npad_, n_, compute_error ? psN_ : nullptr, nullptr, stream_));
+		// (penalties: G and the slabs stay raw -- ps and the trace of the error term read them)
+		HIPX(launch_panel_sweep_hals<T>(H_, slabs_, S, slab_stride_, G_, RP_, r_, (int)npad_, n_, compute_error ? psN_ : nullptr, nullptr, stream_, (T)prm_.l1H, (T)prm_.l2H));
 		hx3_valid_ = false;
 		return ST_OK;
 	}
@@ -1953,6 +1960,15 @@ Status Engine<T>::begin_next_iteration() {
 }
 
 template <typename T>
+Status Engine<T>::set_hals_penalties(double l1W, double l1H, double l2W, double l2H) {
+	if (const char* why = hals_penalties_fault(l1W, l1H, l2W, l2H, sizeof(T) == 4, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
+	// kept rounded to T, as the sweeps take them: a value that rounds to 0 in the engine's precision is 0 for the normalisation switch too, and the
+	// (T) casts where the sweeps are launched change nothing any more
+	prm_.l1W = (double)(T)l1W; prm_.l1H = (double)(T)l1H; prm_.l2W = (double)(T)l2W; prm_.l2H = (double)(T)l2H;
+	return ST_OK;
+}
+
+template <typename T>
 Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 	const T eps = std::numeric_limits<T>::epsilon();
 	timing_now_ = timing_ && (timing_iter_++ % timing_stride_ == 0);
@@ -2041,11 +2057,16 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 			}
 			if (alg_ == ALG_HALS) {
 				// coordinate sweep over every row of W against H H^T and the summed slabs of V H^T, then the column normalisation that keeps W H:
-				// W(:, c) / d(c), H(c, :) d(c) -- applied to H at once, no pending scale
+				// W(:, c) / d(c), H(c, :) d(c) -- applied to H at once, no pending scale.  With a penalty there is no normalisation: it keeps W H but not the
+				// penalty terms, and without it one iteration is one pass of scikit-learn's coordinate descent (docs/HALS.md).
 				wx3_valid_ = false;
 				gram_w_ready_ = false;
-				HIPX(launch_panel_sweep_hals<T>(Wt_, slabs_, S, slab_stride_, HHt_, RP_, r_, (int)mpad_, m_, nullptr, sumsq_part_, stream_));
-				HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, panel_sweep_hals_parts(RP_, sizeof(T), (int)mpad_), stream_));
+				if (prm_.hals_penalised()) {
+					HIPX(launch_panel_sweep_hals<T>(Wt_, slabs_, S, slab_stride_, HHt_, RP_, r_, (int)mpad_, m_, nullptr, nullptr, stream_, (T)prm_.l1W, (T)prm_.l2W));
+				} else {
+					HIPX(launch_panel_sweep_hals<T>(Wt_, slabs_, S, slab_stride_, HHt_, RP_, r_, (int)mpad_, m_, nullptr, sumsq_part_, stream_));
+					HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, panel_sweep_hals_parts(RP_, sizeof(T), (int)mpad_), stream_));
+				}
 			} else if (!ls_family) {
 				const bool gd_err = alg_ == ALG_GDCLS && compute_error;
 				T* wpart = nullptr;

@@ -25,8 +25,26 @@ struct AlgorithmParams {
 	double sparse_compute = 0;  // 1: keep V as CSR + CSC in HBM and multiply by SpMM instead of densifying
 	double precision = 0;       // 1: bf16 MFMA operands (V, W, H rounded to bf16 inside the two big products), fp32 everywhere else
 	double missing_values = 0;  // 1: fit the stored entries only (multiplicative update; implies sparse compute, kernels_masked.hip, docs/MISSING.md)
+	// HALS only (docs/HALS.md): L1 / L2 penalties on W and on H, scikit-learn's coordinate descent; all 0: the unpenalised iteration.  Engine::set_hals_penalties
+	// changes them between iterations.
+	double l1W = 0, l1H = 0, l2W = 0, l2H = 0;
 	bool is_masked() const { return missing_values != 0; }
+	bool hals_penalised() const { return l1W != 0 || l1H != 0 || l2W != 0 || l2H != 0; }
 };
+
+// What a set of HALS penalties (l1W, l1H, l2W, l2H) must satisfy, stated once for Engine::set_hals_penalties and nmfgpu::compute: nullptr, or why not.
+// fp32: the sweeps of a float engine take the values as float, where a large double is not finite.
+inline const char* hals_penalties_fault(double l1W, double l1H, double l2W, double l2H, bool fp32, bool is_hals) {
+	const double v[4] = {l1W, l1H, l2W, l2H};
+	bool any = false;
+	for (double x : v) {
+		if (!(x >= 0) || x > 1.7976931348623157e308) return "HALS penalties: l1W, l1H, l2W and l2H must be finite and >= 0";
+		if (fp32 && x > 3.4028234663852886e38) return "HALS penalties: value out of the range of the engine's precision";
+		any = any || x != 0;
+	}
+	if (any && !is_hals) return "HALS penalties: only the HALS algorithm takes l1W / l1H / l2W / l2H";
+	return nullptr;
+}
 
 // Status codes shared with nmfgpu_amd.h (NMFAMD_*).
 // ST_VALUE_RANGE: V holds values the split-operand product is not exact for (infinities, NaN, |v| > 2^126, 0 < |v| < 2^-100):
@@ -76,6 +94,9 @@ public:
 	Status begin_next_iteration();
 	// One iteration.  With compute_error the frobenius()/rmsd() values are refreshed (host sync).
 	Status iterate(bool compute_error, bool constant_w);
+	// HALS: the penalties of the iterations that follow (>= 0 and finite; all 0: the unpenalised iteration, normalisation included).  Valid any time
+	// between iterations.  ST_INVALID with last_error() for a bad value, and for a non-zero one on an engine of another algorithm.
+	Status set_hals_penalties(double l1W, double l1H, double l2W, double l2H);
 
 	// Split form for column-sharded multi-GPU runs (exchange = device buffer of exchange_count()
 	// elements: the local (V H^T)^T panel followed by the local H H^T):

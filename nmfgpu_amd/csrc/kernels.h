@@ -268,11 +268,13 @@ hipError_t launch_panel_update(int mode, T* P, const T* slabs, int S, long slab_
 // HALS (kernels_hals.hip): Gauss-Seidel sweep over the r coordinates of every panel column, P(:, y) <- the clamped coordinate-descent update
 // against G (r x r Gram matrix) and the summed slabs; ps / sumsq_part (optional) as launch_panel_update's, with panel_sweep_hals_parts() partials.
 // Padded ranks: fp32 64, 128, 256, 384, 512; fp64 multiples of 64 up to 512.
+// l1, l2 >= 0: penalties on the swept factor (the step divides by G(k, k) + l2 and its gradient carries l2 p(k) + l1; ps keeps the raw slabs).  Both 0: the
+// plain sweep, the same instantiation as before the penalties existed.
 bool panel_sweep_hals_available(int RP, size_t elem);
 int panel_sweep_hals_parts(int RP, size_t elem, int len_pad);
 template <typename T>
 hipError_t launch_panel_sweep_hals(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part,
-                                   hipStream_t stream);
+                                   hipStream_t stream, T l1 = T(0), T l2 = T(0));
 // W(:, c) <- W(:, c) / d(c), H(c, :) <- H(c, :) d(c) where d(c) = ||W(:, c)|| > 0, d from `parts` vectors of partial sums of squares (W H unchanged);
 // sumsq_part needs RP elements of scratch behind the partials
 template <typename T>

@@ -13,10 +13,18 @@
 // and the owning lane (j = k % L, register e = k / L -- a compile-time index, the loop over e is unrolled) applies the step.  The
 // reciprocals 1 / G(k, k) live in the owner's registers.  Optional outputs as k_panel_update's: ps(y) = sum_k p_new(k) a(k) and per-workgroup
 // partial sums of squares of the new entries.
+//
+// Penalised form (PEN; scikit-learn's coordinate descent with an L1 and an L2 penalty on the swept factor, l1, l2 >= 0): with d(k) = G(k, k) + l2,
+//   skipping k where d(k) <= 0:   p(k) <- max(0, p(k) - (G(k, :) . p + l2 p(k) - a(k) + l1) / d(k))
+// G and a stay unpenalised: ps is formed from the raw a, and the engine's trace reads the raw Gram matrix.  The launcher picks the plain instantiation
+// when both penalties are 0, so that form is the same code as before the penalties existed.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
+
 #include "kernels.h"
+#include "split3.h"
 
 namespace nmfamd {
 
@@ -38,15 +46,17 @@ struct HalsGeom {
 	static_assert(COLS <= KC && 128 % COLS == 0, "the sum-of-squares staging reuses the G chunk; workgroups tile 128-column panels");
 };
 
-template <typename T, int RP>
+template <typename T, int RP, bool PEN>
 __global__ __launch_bounds__(HALS_THREADS) void k_sweep_hals(T* __restrict__ P, const T* __restrict__ slabs, int S, long slab_stride, const T* __restrict__ G,
-                                                             int r, int len_valid, T* __restrict__ ps, T* __restrict__ sumsq_part) {
+                                                             int r, int len_valid, T* __restrict__ ps, T* __restrict__ sumsq_part, T l1_arg, T l2_arg) {
 	using Gm = HalsGeom<T, RP>;
 	constexpr int L = Gm::L, C = Gm::C, E = Gm::E, GROUPS = Gm::GROUPS, COLS = Gm::COLS, KC = Gm::KC;
 	__shared__ __attribute__((aligned(16))) T sG[KC * RP];
 	const int tid = threadIdx.x, lane = tid % L, grp = tid / L;
 	const long y0 = (long)blockIdx.x * COLS;
 
+	// (VGPRs: a uniform argument meets per-lane values below, split3.h)
+	const T l1 = PEN ? in_vgpr(l1_arg) : T(0), l2 = PEN ? in_vgpr(l2_arg) : T(0);
 	T h[C][E], a[C][E], inv[E];
 #pragma unroll
 	for (int c = 0; c < C; ++c) {
@@ -65,8 +75,9 @@ __global__ __launch_bounds__(HALS_THREADS) void k_sweep_hals(T* __restrict__ P, 
 #pragma unroll
 	for (int e = 0; e < E; ++e) {
 		const int k = e * L + lane;
-		const T d = k < r ? G[(long)k * RP + k] : T(0);
-		inv[e] = d > T(0) ? T(1) / d : T(0);        // 0: the coordinate is skipped (G(k, k) <= 0, or padding)
+		T d = k < r ? G[(long)k * RP + k] : T(0);
+		if constexpr (PEN) { if (k < r) d += l2; }
+		inv[e] = d > T(0) ? T(1) / d : T(0);        // 0: the coordinate is skipped (G(k, k) [+ l2] <= 0, or padding)
 	}
 
 	int k_lo = 0, k_hi = 0;
@@ -95,7 +106,9 @@ __global__ __launch_bounds__(HALS_THREADS) void k_sweep_hals(T* __restrict__ P, 
 #pragma unroll
 				for (int off = L / 2; off > 0; off >>= 1) dot += __shfl_xor(dot, off, L);
 				if (lane == q && inv[e] > T(0)) {
-					const T v = h[c][e] - (dot - a[c][e]) * inv[e];
+					T v;
+					if constexpr (PEN) v = h[c][e] - ((dot - a[c][e]) + (l2 * h[c][e] + l1)) * inv[e];
+					else v = h[c][e] - (dot - a[c][e]) * inv[e];
 					h[c][e] = v > T(0) ? v : T(0);
 				}
 			}
@@ -136,8 +149,10 @@ __global__ __launch_bounds__(HALS_THREADS) void k_sweep_hals(T* __restrict__ P, 
 }
 
 template <typename T, int RP>
-static hipError_t sweep_at(T* P, const T* slabs, int S, long slab_stride, const T* G, int r, int len_pad, int len_valid, T* ps, T* sumsq_part, hipStream_t stream) {
-	hipLaunchKernelGGL((k_sweep_hals<T, RP>), dim3(len_pad / HalsGeom<T, RP>::COLS), dim3(HALS_THREADS), 0, stream, P, slabs, S, slab_stride, G, r, len_valid, ps, sumsq_part);
+static hipError_t sweep_at(T* P, const T* slabs, int S, long slab_stride, const T* G, int r, int len_pad, int len_valid, T* ps, T* sumsq_part, hipStream_t stream, T l1, T l2) {
+	const dim3 grid(len_pad / HalsGeom<T, RP>::COLS);
+	if (l1 != T(0) || l2 != T(0)) hipLaunchKernelGGL((k_sweep_hals<T, RP, true>), grid, dim3(HALS_THREADS), 0, stream, P, slabs, S, slab_stride, G, r, len_valid, ps, sumsq_part, l1, l2);
+	else hipLaunchKernelGGL((k_sweep_hals<T, RP, false>), grid, dim3(HALS_THREADS), 0, stream, P, slabs, S, slab_stride, G, r, len_valid, ps, sumsq_part, T(0), T(0));
 	return hipGetLastError();
 }
 
@@ -169,22 +184,23 @@ int panel_sweep_hals_parts(int RP, size_t elem, int len_pad) {
 
 template <typename T>
 hipError_t launch_panel_sweep_hals(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part,
-                                   hipStream_t stream) {
+                                   hipStream_t stream, T l1, T l2) {
 	if (!panel_sweep_hals_available(RP, sizeof(T)) || r < 1 || r > RP || len_pad % 128 != 0 || len_valid > len_pad) return hipErrorInvalidValue;
+	if (!(l1 >= T(0)) || !(l2 >= T(0)) || !std::isfinite(l1) || !std::isfinite(l2)) return hipErrorInvalidValue;
 	switch (RP) {
-	case 64: return sweep_at<T, 64>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream);
-	case 128: return sweep_at<T, 128>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream);
-	case 192: if constexpr (sizeof(T) == 8) return sweep_at<T, 192>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream); break;      // (fp64 only)
-	case 256: return sweep_at<T, 256>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream);
-	case 320: if constexpr (sizeof(T) == 8) return sweep_at<T, 320>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream); break;      // (fp64 only)
-	case 384: return sweep_at<T, 384>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream);
-	case 448: if constexpr (sizeof(T) == 8) return sweep_at<T, 448>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream); break;      // (fp64 only)
-	case 512: return sweep_at<T, 512>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream);
+	case 64: return sweep_at<T, 64>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream, l1, l2);
+	case 128: return sweep_at<T, 128>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream, l1, l2);
+	case 192: if constexpr (sizeof(T) == 8) return sweep_at<T, 192>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream, l1, l2); break;      // (fp64 only)
+	case 256: return sweep_at<T, 256>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream, l1, l2);
+	case 320: if constexpr (sizeof(T) == 8) return sweep_at<T, 320>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream, l1, l2); break;      // (fp64 only)
+	case 384: return sweep_at<T, 384>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream, l1, l2);
+	case 448: if constexpr (sizeof(T) == 8) return sweep_at<T, 448>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream, l1, l2); break;      // (fp64 only)
+	case 512: return sweep_at<T, 512>(P, slabs, S, slab_stride, G, r, len_pad, len_valid, ps, sumsq_part, stream, l1, l2);
 	}
 	return hipErrorInvalidValue;
 }
-template hipError_t launch_panel_sweep_hals<float>(float*, const float*, int, long, const float*, int, int, int, int, float*, float*, hipStream_t);
-template hipError_t launch_panel_sweep_hals<double>(double*, const double*, int, long, const double*, int, int, int, int, double*, double*, hipStream_t);
+template hipError_t launch_panel_sweep_hals<float>(float*, const float*, int, long, const float*, int, int, int, int, float*, float*, hipStream_t, float, float);
+template hipError_t launch_panel_sweep_hals<double>(double*, const double*, int, long, const double*, int, int, int, int, double*, double*, hipStream_t, double, double);
 
 // ------------------------------------------------------------------------------------------
 // Column normalisation of W that keeps W H: d(c) = ||W(:, c)|| from the summed squares; where d(c) > 0, W(:, c) <- W(:, c) / d(c) and

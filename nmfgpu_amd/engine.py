@@ -53,9 +53,13 @@ class Engine:
 
     def __init__(self, m: int, n: int, r: int, algorithm: str = "mu", dtype=np.float32, stream: int = 0,
                  lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence: str = "frobenius",
-                 sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False):
+                 sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False,
+                 l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0):
         """missing_values=True: fit the observed entries only (docs/MISSING.md) -- the stored entries of upload_sparse, the non-NaN entries of
-        upload (zeros included).  Multiplicative update ("mu") with the Frobenius objective only; implies sparse_compute."""
+        upload (zeros included).  Multiplicative update ("mu") with the Frobenius objective only; implies sparse_compute.
+
+        l1_w, l1_h, l2_w, l2_h: "hals" only (docs/HALS.md) -- the L1 / L2 penalties of scikit-learn's coordinate descent on W and H; see
+        set_penalties.  sparse_compute=True is available for "mu" and "hals" (rank <= 256)."""
         self._lib = library()
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -64,14 +68,15 @@ class Engine:
         self._ctor = dict(algorithm=algorithm, stream=stream, row_blocks=row_blocks,
                           params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0}[divergence],
                                   float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
-                                  float(missing_values)])
+                                  float(missing_values)],
+                          penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)])
         self._h = None
-        self._create()
         self._lib.nmfamd_engine_frobenius.restype = C.c_double
         self._lib.nmfamd_engine_rmsd.restype = C.c_double
         self._lib.nmfamd_engine_kl_divergence.restype = C.c_double
         self._lib.nmfamd_engine_last_error.restype = C.c_char_p
         self._lib.nmfamd_engine_error_terms.restype = C.c_long
+        self._create()
 
     def _create(self):
         c = self._ctor
@@ -81,8 +86,14 @@ class Engine:
         st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p), self.dtype.itemsize,
                                                    C.c_void_p(c["stream"]), int(c["row_blocks"]), C.byref(h))
         if st != 0:
-            raise EngineError(st, "nmfamd_engine_create")
+            raise EngineError(st, "nmfamd_engine_create", (self._lib.nmfamd_engine_last_error(None) or b"").decode())
         self._h = h
+        # (the penalties are engine state, not part of nmfamd_params: an engine recreated by _upload gets them again)
+        try:
+            self.set_penalties(*c["penalties"])
+        except EngineError:
+            self.close()
+            raise
 
     def _check(self, st: int, what: str):
         if st != 0:
@@ -157,6 +168,14 @@ class Engine:
 
     def synchronize(self):
         self._check(self._lib.nmfamd_engine_synchronize(self._h), "synchronize")
+
+    def set_penalties(self, l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0):
+        """HALS: the iterations that follow minimise 1/2 ||V - W H||^2 + l1_w ||W||_1 + l1_h ||H||_1 + 1/2 l2_w ||W||^2 + 1/2 l2_h ||H||^2
+        (nmfamd_engine_set_hals_penalties; docs/HALS.md has the mapping from scikit-learn's alpha_W, alpha_H, l1_ratio).  Valid between
+        iterations; all zeros restores the unpenalised iteration.  frobenius / rmsd keep reporting ||V - W H||."""
+        vals = [float(l1_w), float(l1_h), float(l2_w), float(l2_h)]
+        self._check(self._lib.nmfamd_engine_set_hals_penalties(self._h, *(C.c_double(v) for v in vals)), "set_hals_penalties")
+        self._ctor["penalties"] = vals
 
     @property
     def frobenius(self) -> float:
@@ -543,8 +562,8 @@ def op_tri_update(P: np.ndarray, num: np.ndarray, Q: np.ndarray, *, old_colsq: O
 
 
 def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_valid: int, *, ps: Optional[np.ndarray] = None,
-                  sumsq_part: Optional[np.ndarray] = None):
-    """One launch of the HALS sweep (nmfamd_op_hals_sweep_*) on padded arrays: P (len_pad, RP) panel columns, slabs (S, slab_stride) with
+                  sumsq_part: Optional[np.ndarray] = None, penalties: Optional[tuple] = None):
+    """One launch of the HALS sweep (nmfamd_op_hals_sweep_*; with penalties = (l1, l2) through nmfamd_op_hals_sweep_pen_*, zeros included) on padded arrays: P (len_pad, RP) panel columns, slabs (S, slab_stride) with
     slab_stride >= len_pad * RP (slab s is the first len_pad * RP values of row s; the rest of the row is a gap the kernel must not read), G (RP, RP).
     ps (len_pad values) and sumsq_part ((len_pad // 16) * RP values), when given, are copied in before the launch, so entries the kernel leaves
     alone keep the caller's sentinels.  Returns a dict: `P` (the new panel), `ps`, `sumsq_part` (parts x RP) and `parts`."""
@@ -566,10 +585,14 @@ def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_v
         if sumsq_part.size < (len_pad // 16) * RP:
             raise ValueError("sumsq_part must hold (len_pad // 16) * RP values")
     parts = C.c_int(0)
-    fn = library().nmfamd_op_hals_sweep_f32 if dt == np.float32 else library().nmfamd_op_hals_sweep_f64
+    lib, real = library(), (C.c_float if dt == np.float32 else C.c_double)
+    if penalties is None:
+        fn, extra = (lib.nmfamd_op_hals_sweep_f32 if dt == np.float32 else lib.nmfamd_op_hals_sweep_f64), ()
+    else:
+        fn, extra = (lib.nmfamd_op_hals_sweep_pen_f32 if dt == np.float32 else lib.nmfamd_op_hals_sweep_pen_f64), (real(penalties[0]), real(penalties[1]))
     st = fn(C.c_void_p(P.ctypes.data), C.c_void_p(slabs.ctypes.data), S, C.c_long(stride), C.c_void_p(G.ctypes.data), RP, int(r), len_pad,
             int(len_valid), C.c_void_p(ps.ctypes.data) if ps is not None else None,
-            C.c_void_p(sumsq_part.ctypes.data) if sumsq_part is not None else None, C.byref(parts))
+            C.c_void_p(sumsq_part.ctypes.data) if sumsq_part is not None else None, C.byref(parts), *extra)
     if st != 0:
         raise EngineError(st, "nmfamd_op_hals_sweep")
     k = parts.value
