@@ -56,7 +56,9 @@ typedef struct nmfamd_params {
 	double alphaH;   /* AHCLS "alphaH" */
 	double theta;    /* nsNMF "theta" */
 	/* extensions without a reference counterpart (nmfgpu::compute: Parameter names "divergence", "sparseCompute") */
-	double divergence;      /* 0 = Frobenius objective; 1 = generalised KL divergence (Multiplicative only; implies sparse_compute) */
+	double divergence;      /* 0 = Frobenius objective; 1 = generalised KL divergence (Multiplicative only; over the stored entries of a sparse image of V -- implies
+	                           sparse_compute -- unless nmfamd_params_v2.dense_compute = 1); 2 = Itakura-Saito divergence (Multiplicative only, always the dense path of
+	                           docs/DIVERGENCE.md: every entry of V finite and > 0, dense input only) */
 	double sparse_compute;  /* 1 = keep V as CSR + CSC in HBM and use SpMM / SDDMM kernels instead of densifying (Multiplicative, and HALS with
 	                           divergence 0; rank <= 256) */
 	double precision;       /* Parameter "precision", float engines only.  0 = fp32 accuracy: products on the bf16 matrix pipe with every
@@ -67,6 +69,20 @@ typedef struct nmfamd_params {
 	                           engine has no three-phase / sharded form: nmfamd_engine_h_step / _w_products / _w_finish and nmfamd_sharded_create return
 	                           NMFAMD_INVALID_ARGUMENT; nmfamd_engine_frobenius / _rmsd report the error over the observed entries */
 } nmfamd_params;
+
+/* nmfamd_params with the fields added since nmfamd_engine_create's struct was frozen.  nmfamd_engine_create reads a nmfamd_params of the size it was compiled
+ * with, so a field added there would be read past the struct of a caller built against an older header; the fields that follow therefore live in this
+ * struct, which nmfamd_engine_create_v2 takes together with its size (it reads min(params_size, sizeof(nmfamd_params_v2)) bytes and takes the rest as 0, as
+ * nmfamd_engine_geometry_sized does for its struct).  Fields are only ever added at the END. */
+typedef struct nmfamd_params_v2 {
+	nmfamd_params base;
+	double dense_compute;   /* Parameter "denseCompute".  1 with base.divergence = 1: the KL update on a dense resident V (docs/DIVERGENCE.md: fused matrix-pipe half-steps,
+	                           kernels_beta.hip) instead of over the stored entries; every entry finite and >= 0, sparse input is densified.  The same iteration as the
+	                           sparse path.  Refused with divergence = 0; not needed with divergence = 2.  The dense divergence engines (this, and divergence = 2)
+	                           are single-GPU: rank <= 256, no sparse_compute / missing_values / bf16 precision, no three-phase / sharded form
+	                           (nmfamd_engine_h_step / _w_products / _w_finish and nmfamd_sharded_create return NMFAMD_INVALID_ARGUMENT); constant_w is available.
+	                           An upload that breaks the value rule returns NMFAMD_INVALID_ARGUMENT with nmfamd_engine_last_error set */
+} nmfamd_params_v2;
 
 typedef struct nmfamd_engine nmfamd_engine;  /* opaque; owns every device buffer of one factorisation */
 
@@ -82,6 +98,10 @@ NMFAMD_API const char* nmfamd_engine_last_error(const nmfamd_engine* e);
  * every kernel and copy of this engine is issued on it. */
 NMFAMD_API int nmfamd_engine_create(int m, int n, int r, int algorithm, const nmfamd_params* params,
                                     int elem_bytes, void* stream, nmfamd_engine** out);
+/* The same with the sized, extended parameter struct (nmfamd_params_v2; params_size = sizeof of the caller's struct, at least sizeof(nmfamd_params) unless
+ * params is NULL) and the row blocks of nmfamd_engine_create_blocks (1: none). */
+NMFAMD_API int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* params, unsigned long params_size,
+                                       int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out);
 NMFAMD_API void nmfamd_engine_destroy(nmfamd_engine* e);
 
 /* Upload V from host memory; builds V, its transpose and the sorted tr(V^T V) vector.
@@ -119,6 +139,9 @@ NMFAMD_API double nmfamd_engine_frobenius(nmfamd_engine* e);
 NMFAMD_API double nmfamd_engine_rmsd(nmfamd_engine* e);
 /* Generalised KL divergence D(V || W H) of the most recent error iteration (divergence = 1 only). */
 NMFAMD_API double nmfamd_engine_kl_divergence(nmfamd_engine* e);
+/* The objective of whichever divergence the engine has, of the most recent error iteration: the generalised KL divergence (divergence = 1, sparse or dense: equal to
+ * nmfamd_engine_kl_divergence) or the Itakura-Saito divergence sum (v / p - log(v / p) - 1), p = (W H) + eps (divergence = 2). */
+NMFAMD_API double nmfamd_engine_divergence(nmfamd_engine* e);
 
 /* Dominant-kernel timing.  enable = k > 0: every launch of the factor-product kernel (the two
  * products against V, reference: gemm TN / NT at AlgorithmMultiplicativeFrobenius.h:187-188,240-241)
@@ -141,7 +164,8 @@ typedef struct nmfamd_geometry {
 	int slabs_h, slabs_w;  /* split-K slices of the two factor products */
 	long exchange_count;   /* elements of the multi-GPU exchange buffer */
 	int product_kernel;    /* 0 fp32 MFMA, 1 bf16-rounded operands, 2 fp32 by exact 3 x bf16 operand splitting, 3 fp64 MFMA,
-	                          4 VALU kernel (NMFAMD_FORCE_VALU), 5 sparse SpMM */
+	                          4 VALU kernel (NMFAMD_FORCE_VALU), 5 sparse SpMM, 6 the fused dense beta-divergence half-step (kernels_beta.hip: slabs_h / slabs_w
+	                          are then the reduction slabs of its two launches, which fix the summation order; resident_images = 2, kl_blocks_* = 0) */
 	int resident_images;   /* dense images of V kept in HBM: 2 (V and V^T, each streamed along its output index), 1 (only V: W^T V
 	                          reads it along the reduction index; chosen when two would not fit, or by NMFAMD_ONE_IMAGE), 0 sparse */
 	int one_pass;          /* rank-64 multiplicative update: 1 = V is streamed ONCE per iteration (W^T V, the H update and V H^T in one
@@ -351,6 +375,20 @@ NMFAMD_API int nmfamd_op_hals_sweep_pen_f64(double* P, const double* slabs, int 
  * d(c) = sqrt(sum of the parts); where d(c) > 0, Wt(:, c) / d(c) and H(:, c) * d(c). */
 NMFAMD_API int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad, const float* sumsq_part, int parts);
 NMFAMD_API int nmfamd_op_hals_normalize_f64(double* Wt, int RP, int mpad, double* H, int npad, const double* sumsq_part, int parts);
+/* One half-step of the dense beta-divergence update (kernels_beta.hip, docs/DIVERGENCE.md) on host arrays, for tests: the fused launch and the update launch.
+ * A [out_pad][RP] is the panel that is updated (in place), B [red_pad][RP] the other one, X [out_pad][ldx] the image of V with X(o, k) the entry at output index o and
+ * reduction index k (zero on the padding; ldx >= red_pad, a multiple of 4); coordinates c >= r, rows o >= out_valid and reduction indices k >= red_valid are padding.
+ * beta: 1 generalised KL (dsum: the RP denominators, the column sums of B) or 0 Itakura-Saito (dsum unused).  form: 0 update, 1 update + error terms, 2 error
+ * terms only (A stays as it is).  force_slabs: 0 = the planned slab count, else that many (at most 16, at most the number of reduction tiles); *slabs: the count that ran.
+ * t_frob / t_div (out_pad values each, forms 1 and 2): per output row the sums of (x - p)^2 and of the divergence, p = A(o, :) . B(k, :) + eps.  sumsq_part / sum_part
+ * (optional, (out_pad / 128) * RP values): the per-workgroup sums of squares / sums of the new values.  NMFAMD_INVALID_ARGUMENT wherever the launchers refuse
+ * (RP not 64 / 128 / 256, sizes that are not multiples of 128, ...). */
+NMFAMD_API int nmfamd_op_beta_half_step_f32(float* A, const float* B, const float* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid,
+                                            int beta, int form, int force_slabs, const float* dsum, float* t_frob, float* t_div, float* sumsq_part, float* sum_part,
+                                            int* slabs);
+NMFAMD_API int nmfamd_op_beta_half_step_f64(double* A, const double* B, const double* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid,
+                                            int beta, int form, int force_slabs, const double* dsum, double* t_frob, double* t_div, double* sumsq_part, double* sum_part,
+                                            int* slabs);
 /* Test access to an engine's device intermediates in panel layout: which = 0 Wt, 1 H, 2 W^T W,
  * 3 H H^T, 4 slabs, 5 inverse, 6 V, 7 Vt; rank-256 fp32 engines also 8 W^T W as last reduced, 9 staged column sums of squares,
  * 10 / 11 the bf16 fragments of W / H as 4-byte words. */

@@ -213,6 +213,9 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		if (idx >= 0) prm.sparse_compute = d.parameters[idx].value;
 		idx = parameter_index(d.parameters, d.numParameters, "precision");
 		if (idx >= 0 && std::is_same<T, float>::value) prm.precision = d.parameters[idx].value;
+		// "divergence" = 2 (Itakura-Saito) and "denseCompute" = 1 with "divergence" = 1 (dense KL): the dense beta-divergence update (docs/DIVERGENCE.md)
+		idx = parameter_index(d.parameters, d.numParameters, "denseCompute");
+		if (idx >= 0) prm.dense_compute = d.parameters[idx].value;
 		// (HALS takes sparse compute with the Frobenius objective: its two products against V are the SpMM launches of the sparse multiplicative update)
 		const bool sparse_hals = d.algorithm == NmfAlgorithm::HALS && prm.divergence == 0;
 		if ((prm.divergence != 0 || prm.sparse_compute != 0) && d.algorithm != NmfAlgorithm::Multiplicative && !sparse_hals) {
@@ -223,10 +226,15 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 			log_error("[ERROR] 'sparseCompute' with the HALS algorithm supports at most 256 features!");
 			return ResultType::ErrorInvalidArgument;
 		}
-		if (prm.divergence != 0 && d.useConstantBasisVectors) {
+		if (prm.divergence != 0 && d.useConstantBasisVectors && !prm.is_beta_dense()) {
 			log_error("[ERROR] The KL-divergence update does not support constant basis vectors!");
 			return ResultType::ErrorInvalidArgument;
 		}
+	}
+	// (the engine's own rule for the dense divergence update, asked here so that a refusal comes before any device work; "missingValues" is read further down)
+	if (const char* why = nmfamd::beta_dense_fault(prm, d.algorithm == NmfAlgorithm::Multiplicative, (int)d.features)) {
+		log_error((std::string("[ERROR] ") + why).c_str());
+		return ResultType::ErrorInvalidArgument;
 	}
 	{
 		// "l1W", "l1H", "l2W", "l2H" (docs/HALS.md): the penalties of scikit-learn's coordinate descent on the HALS sweeps; absent = 0
@@ -260,8 +268,8 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 				log_error("[ERROR] 'missingValues' is only available for the Multiplicative algorithm!");
 				return ResultType::ErrorInvalidArgument;
 			}
-			if (prm.divergence != 0) {
-				log_error("[ERROR] 'missingValues' does not combine with 'divergence' (no masked KL update)!");
+			if (prm.divergence != 0 || prm.dense_compute != 0) {
+				log_error("[ERROR] 'missingValues' does not combine with 'divergence' or 'denseCompute' (no masked divergence update)!");
 				return ResultType::ErrorInvalidArgument;
 			}
 			if ((d.initMethod != NmfInitializationMethod::CopyExisting && d.initMethod != NmfInitializationMethod::AllRandomValues) ||
@@ -310,6 +318,10 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		if (idx >= 0) shard_mode = d.parameters[idx].value != 0 ? nmfamd::SHARD_REPLICATED : nmfamd::SHARD_ROW_BLOCKS;
 		if (num_gpus > 1 && prm.missing_values != 0) {
 			log_error("[ERROR] 'numGpus' > 1 is not available with 'missingValues'!");
+			return ResultType::ErrorInvalidArgument;
+		}
+		if (num_gpus > 1 && prm.is_beta_dense()) {
+			log_error("[ERROR] 'numGpus' > 1 is not available with the dense divergence update ('divergence' = 2, 'denseCompute')!");
 			return ResultType::ErrorInvalidArgument;
 		}
 		if (num_gpus > 1 && d.algorithm == NmfAlgorithm::HALS) {

@@ -163,12 +163,21 @@ int nmfamd_engine_create(int m, int n, int r, int algorithm, const nmfamd_params
 }
 
 int nmfamd_engine_create_blocks(int m, int n, int r, int algorithm, const nmfamd_params* params, int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out) {
+	return nmfamd_engine_create_v2(m, n, r, algorithm, params, params ? sizeof(nmfamd_params) : 0, elem_bytes, stream, row_blocks, out);
+}
+
+int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* params_sized, unsigned long params_size, int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out) {
+	if (params_sized != nullptr && params_size < sizeof(nmfamd_params)) return NMFAMD_INVALID_ARGUMENT;
+	nmfamd_params_v2 v2;
+	std::memset(&v2, 0, sizeof(v2));
+	if (params_sized != nullptr) std::memcpy(&v2, params_sized, params_size < sizeof(v2) ? (size_t)params_size : sizeof(v2));
+	const nmfamd_params* params = params_sized != nullptr ? &v2.base : nullptr;
 	if (!out || (elem_bytes != 4 && elem_bytes != 8) || row_blocks < 1 || row_blocks > 64) return NMFAMD_INVALID_ARGUMENT;
 	*out = nullptr;
 	g_create_error.clear();
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	AlgorithmParams p;
-	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; }
+	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; p.dense_compute = v2.dense_compute; }
 	nmfamd_engine* e = new (std::nothrow) nmfamd_engine();
 	if (!e) return NMFAMD_NO_HOST_MEMORY;
 	e->elem_bytes = elem_bytes;
@@ -322,6 +331,7 @@ int nmfamd_engine_synchronize(nmfamd_engine* e) {
 
 double nmfamd_engine_frobenius(nmfamd_engine* e) { return !e ? 0.0 : (e->elem_bytes == 4 ? e->f->frobenius() : e->d->frobenius()); }
 double nmfamd_engine_kl_divergence(nmfamd_engine* e) { return !e ? 0.0 : (e->elem_bytes == 4 ? e->f->kl_divergence() : e->d->kl_divergence()); }
+double nmfamd_engine_divergence(nmfamd_engine* e) { return !e ? 0.0 : (e->elem_bytes == 4 ? e->f->divergence_value() : e->d->divergence_value()); }
 double nmfamd_engine_rmsd(nmfamd_engine* e) { return !e ? 0.0 : (e->elem_bytes == 4 ? e->f->rmsd() : e->d->rmsd()); }
 
 int nmfamd_engine_kernel_timing(nmfamd_engine* e, int enable) {
@@ -868,9 +878,65 @@ int op_hals_normalize(T* Wt, int RP, int mpad, T* H, int npad, const T* sumsq_pa
 	if (hipMemcpy(Wt, dW.p, w, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(H, dH.p, h, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
 	return NMFAMD_OK;
 }
+
+template <typename T>
+int op_beta_half_step(T* A, const T* B, const T* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid, int beta, int form,
+                      int force_slabs, const T* dsum, T* t_frob, T* t_div, T* sumsq_part, T* sum_part, int* slabs) {
+	const bool update = form == 0 || form == 1, terms = form == 1 || form == 2;
+	if (!A || !B || !X || !beta_half_step_available(RP) || r < 1 || r > RP || (beta != 0 && beta != 1) || form < 0 || form > 2 || out_pad < 128 || out_pad % 128 != 0 ||
+	    red_pad < 128 || red_pad % 128 != 0 || out_valid < 0 || out_valid > out_pad || red_valid < 0 || red_valid > red_pad || ldx < red_pad || ldx % 4 != 0 ||
+	    force_slabs < 0 || (update && beta == 1 && !dsum) || (terms && (!t_frob || !t_div)))
+		return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	int dev = 0;
+	hipDeviceProp_t prop;
+	if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return NMFAMD_HIP_ERROR;
+	const BetaPlan plan = plan_beta_half_step(out_pad, red_pad, RP, sizeof(T), prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256, force_slabs);
+	if (slabs) *slabs = plan.slabs;
+	const size_t panelA = sizeof(T) * (size_t)out_pad * RP, panelB = sizeof(T) * (size_t)red_pad * RP, image = sizeof(T) * (size_t)out_pad * (size_t)ldx;
+	const size_t parts = (size_t)(out_pad / 128) * RP;
+	const long part_stride = (long)out_pad * RP;
+	DevBuf dA, dB, dX, dNum, dDen, dT, dOut, dSum, dD;
+	if (dA.alloc(panelA) != hipSuccess || dB.alloc(panelB) != hipSuccess || dX.alloc(image) != hipSuccess || dNum.alloc(panelA * plan.slabs) != hipSuccess ||
+	    dDen.alloc(panelA * plan.slabs) != hipSuccess || dT.alloc(sizeof(T) * 2 * (size_t)plan.slabs * out_pad) != hipSuccess ||
+	    dOut.alloc(sizeof(T) * 2 * (size_t)out_pad) != hipSuccess || dSum.alloc(sizeof(T) * 2 * parts) != hipSuccess || dD.alloc(sizeof(T) * (size_t)RP) != hipSuccess)
+		return NMFAMD_NO_DEVICE_MEMORY;
+	if (hipMemcpy(dA.p, A, panelA, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dB.p, B, panelB, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(dX.p, X, image, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dSum.p, 0, sizeof(T) * 2 * parts) != hipSuccess ||
+	    hipMemset(dOut.p, 0, sizeof(T) * 2 * (size_t)out_pad) != hipSuccess || hipMemset(dD.p, 0, sizeof(T) * (size_t)RP) != hipSuccess)
+		return NMFAMD_HIP_ERROR;
+	if (dsum && hipMemcpy(dD.p, dsum, sizeof(T) * (size_t)RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	T* tf = terms ? (T*)dT.p : nullptr;
+	T* td = terms ? (T*)dT.p + (size_t)plan.slabs * out_pad : nullptr;
+	T* of = terms ? (T*)dOut.p : nullptr;
+	T* od = terms ? (T*)dOut.p + out_pad : nullptr;
+	const T eps = std::numeric_limits<T>::epsilon();
+	if (launch_beta_fused<T>((const T*)dX.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update, terms, eps, plan, (T*)dNum.p, (T*)dDen.p, part_stride, tf, td, out_pad,
+	                         out_pad, out_valid, red_valid, nullptr) != hipSuccess)
+		return NMFAMD_HIP_ERROR;
+	if (launch_beta_update<T>((T*)dA.p, (const T*)dNum.p, (const T*)dDen.p, part_stride, plan.slabs, (const T*)dD.p, RP, r, out_pad, out_valid, eps, beta, update,
+	                          (T*)dSum.p, (T*)dSum.p + parts, tf, td, out_pad, of, od, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+		return NMFAMD_HIP_ERROR;
+	if (hipMemcpy(A, dA.p, panelA, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (terms && (hipMemcpy(t_frob, of, sizeof(T) * (size_t)out_pad, hipMemcpyDeviceToHost) != hipSuccess ||
+	              hipMemcpy(t_div, od, sizeof(T) * (size_t)out_pad, hipMemcpyDeviceToHost) != hipSuccess)) return NMFAMD_HIP_ERROR;
+	if (sumsq_part && hipMemcpy(sumsq_part, dSum.p, sizeof(T) * parts, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (sum_part && hipMemcpy(sum_part, (T*)dSum.p + parts, sizeof(T) * parts, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
 }
 
 extern "C" {
+
+int nmfamd_op_beta_half_step_f32(float* A, const float* B, const float* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid, int beta,
+                                 int form, int force_slabs, const float* dsum, float* t_frob, float* t_div, float* sumsq_part, float* sum_part, int* slabs) {
+	return op_beta_half_step<float>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, beta, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs);
+}
+
+int nmfamd_op_beta_half_step_f64(double* A, const double* B, const double* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid, int beta,
+                                 int form, int force_slabs, const double* dsum, double* t_frob, double* t_div, double* sumsq_part, double* sum_part, int* slabs) {
+	return op_beta_half_step<double>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, beta, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs);
+}
 
 int nmfamd_op_hals_sweep_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid, float* ps,
                              float* sumsq_part, int* parts) {

@@ -140,7 +140,7 @@ Engine<T>::~Engine() {
 	if (inv_work_) (void)hipFree(inv_work_);
 	if (range_flag_) (void)hipFree(range_flag_);
 	{
-		void* sp[] = {csr_ptr_, csr_idx_, csc_ptr_, csc_idx_, csc_from_csr_, csr_val_, csc_val_, q_, q2_, t_vwh_, t_kl_, rowsum_part_, sW_, sH_, kl_scale_, csr_bptr_, csc_bptr_, kl_part_, kl_tpart_, msq_part_};
+		void* sp[] = {csr_ptr_, csr_idx_, csc_ptr_, csc_idx_, csc_from_csr_, csr_val_, csc_val_, q_, q2_, t_vwh_, t_kl_, rowsum_part_, sW_, sH_, kl_scale_, csr_bptr_, csc_bptr_, kl_part_, kl_tpart_, msq_part_, beta_den_, beta_tpart_};
 		for (void* b : sp) if (b) (void)hipFree(b);
 	}
 	{ void* bb[] = {Vb_, Vtb_, Wtb_, Hb_, Wx3_, Hx3_, qx3_, gram_tri_part_, Gw_raw_, Gh_raw_, colsq_}; for (void* b : bb) if (b) (void)hipFree(b); }
@@ -178,6 +178,8 @@ Status Engine<T>::allocate() {
 	if (m_ <= 0 || n_ <= 0 || r_ <= 0 || alg_ < 0 || alg_ > ALG_HALS) return ST_INVALID;
 	if (alg_ == ALG_HALS && !panel_sweep_hals_available(RP_, sizeof(T))) { last_error_ = "HALS: no sweep kernel for this padded rank (fp32: 64 ... 512, fp64: multiples of 64 up to 512)"; return ST_INVALID; }
 	if (Status s = set_hals_penalties(prm_.l1W, prm_.l1H, prm_.l2W, prm_.l2H)) return s;      // (values that came with the parameters: the setter's checks, and its rounding of prm_ to T)
+	if (const char* why = beta_dense_fault(prm_, alg_ == ALG_MU, r_, row_blocks_)) { last_error_ = why; return ST_INVALID; }
+	beta_dense_ = prm_.is_beta_dense();
 	int dev = 0;
 	HIPX(hipGetDevice(&dev));
 	hipDeviceProp_t prop;
@@ -194,7 +196,7 @@ Status Engine<T>::allocate() {
 	if (!mfma) { planH_.splits = 1; planW_.splits = 1; planH_.th = planW_.th = 128; planH_.xtiles = (int)(pad128(n_) / 128); planW_.xtiles = (int)(pad128(m_) / 128); }
 	tiled_ = mfma;
 	// (the SpMM / KL / masked kernels gather RP / 64 = 1, 2 or 4 values per lane: sparse runs keep the 128-column padding in either precision, see the constructor)
-	sparse_ = prm_.sparse_compute != 0 || prm_.divergence != 0 || prm_.is_masked();
+	sparse_ = !beta_dense_ && (prm_.sparse_compute != 0 || prm_.divergence != 0 || prm_.is_masked());
 	if (prm_.is_masked() && (alg_ != ALG_MU || prm_.divergence != 0 || RP_ > 256)) { last_error_ = "missing values: multiplicative update with the Frobenius objective, rank <= 256"; return ST_INVALID; }
 	if (sparse_) {
 		// sparse compute: multiplicative update (either objective, masked or not) and HALS (Frobenius, not masked), padded rank 64 / 128 / 256
@@ -206,6 +208,16 @@ Status Engine<T>::allocate() {
 		tiled_ = false;
 		planH_.splits = planW_.splits = 1; planH_.th = planW_.th = 128;
 		planH_.xtiles = (int)(pad128(n_) / 128); planW_.xtiles = (int)(pad128(m_) / 128);
+	}
+	if (beta_dense_) {
+		// dense beta-divergence update (kernels_beta.hip): V_ is the plain column-major image, Vt_ its transpose; the slab counts of the two fused half-steps
+		// (a function of the shape and the CU count) are what slabs_h() / slabs_w() report
+		tiled_ = false;
+		planH_.th = planW_.th = 128;
+		planH_.xtiles = (int)(pad128(n_) / 128); planW_.xtiles = (int)(pad128(m_) / 128);
+		betaH_ = plan_beta_half_step(pad128(n_), pad128(m_), RP_, sizeof(T), num_cus_);
+		betaW_ = plan_beta_half_step(pad128(m_), pad128(n_), RP_, sizeof(T), num_cus_);
+		planH_.splits = betaH_.slabs; planW_.splits = betaW_.slabs;
 	}
 	if (prm_.precision > 0) {
 		// bf16 operands for the two big products, dense (resident) V only; every algorithm, padded rank 64 or k * 128
@@ -355,6 +367,16 @@ Status Engine<T>::allocate() {
 		HIPX(dalloc(&kl_scale_, RP_));
 		HIPX(hipHostMalloc((void**)&pin_kl_, sizeof(T) * (2 * (size_t)m_ + 3 * (size_t)RP_)));
 		if (prm_.is_masked()) HIPX(dalloc(&msq_part_, (long)(MASKED_NORM_PARTS + 16) * RP_));      // (+ 16: launch_normalize_panel's compaction scratch)
+	}
+	if (beta_dense_) {
+		HIPX(dalloc(&t_vwh_, mpad_));
+		HIPX(dalloc(&t_kl_, mpad_));
+		HIPX(dalloc(&rowsum_part_, (std::max(mpad_, npad_) / 128) * RP_));
+		HIPX(dalloc(&sW_, RP_));
+		HIPX(dalloc(&sH_, RP_));
+		HIPX(dalloc(&beta_tpart_, 2l * BETA_MAX_SLABS * mpad_));
+		if (prm_.beta() == 0) HIPX(dalloc(&beta_den_, slab_elems));
+		HIPX(hipHostMalloc((void**)&pin_kl_, sizeof(T) * (2 * (size_t)m_ + 3 * (size_t)RP_)));
 	}
 	HIPX(dalloc(&Wt_, panelW));
 	HIPX(dalloc(&H_, panelH));
@@ -553,6 +575,10 @@ Status Engine<T>::finish_upload(T* Vcol) {
 template <typename T>
 Status Engine<T>::upload_dense(const T* V, long ld) {
 	if (!V || ld < m_) return ST_INVALID;
+	if (beta_dense_) {
+		beta_uploaded_ = false;
+		if (Status st = beta_check_values(V, n_, ld, m_)) return st;
+	}
 	if (sparse_ && prm_.is_masked()) {
 		// missing values: every entry that is not NaN is observed -- zeros included -- and becomes a stored entry
 		std::vector<int> rows, cols; std::vector<T> vals;
@@ -586,12 +612,34 @@ Status Engine<T>::upload_dense(const T* V, long ld) {
 	hipError_t e = hipMemcpy2DAsync(Vcol, mpad_ * sizeof(T), V, ld * sizeof(T), m_ * sizeof(T), n_, hipMemcpyHostToDevice, stream_);
 	Status st = e == hipSuccess ? finish_upload(Vcol) : hip_fail(e, "hipMemcpy2DAsync(V)");
 	if (staged) (void)hipFree(Vcol);
+	if (beta_dense_ && st == ST_OK) beta_uploaded_ = true;
 	return st;
+}
+
+// The dense beta-divergence update's demand on V: every entry finite, and > 0 at beta = 0 (Itakura-Saito is undefined at 0) or >= 0 at beta = 1
+template <typename T>
+Status Engine<T>::beta_check_values(const T* values, long count, long ld, long rows) {
+	const bool is = prm_.beta() == 0;
+	for (long j = 0; j < count; ++j)
+		for (long i = 0; i < rows; ++i) {
+			const T v = values[(size_t)j * ld + i];
+			if (!std::isfinite(v) || v < T(0) || (is && v == T(0))) {
+				last_error_ = is ? "Itakura-Saito divergence: every entry of V has to be finite and > 0" : "dense KL divergence: every entry of V has to be finite and >= 0";
+				return ST_INVALID;
+			}
+		}
+	return ST_OK;
 }
 
 template <typename T>
 Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const int* b, long nnz, int base) {
 	if (format < 1 || format > 3 || nnz < 0 || (nnz > 0 && (!values || !a || !b))) return ST_INVALID;
+	if (beta_dense_) {
+		// the stored entries are densified (launch_densify below); an unstored entry is a zero, which the Itakura-Saito divergence does not take
+		beta_uploaded_ = false;
+		if (prm_.beta() == 0) { last_error_ = "Itakura-Saito divergence: sparse input is refused (unstored entries are zeros); upload V dense"; return ST_INVALID; }
+		if (nnz > 0) { if (Status st = beta_check_values(values, 1, nnz, nnz)) return st; }
+	}
 	if (sparse_ && prm_.is_masked()) {
 		// missing values: every stored entry is observed (stored zeros too, which both image builders keep); its value must be finite, and there must be one
 		if (nnz == 0) { last_error_ = "missing values: no stored entry"; return ST_INVALID; }
@@ -642,6 +690,7 @@ Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const
 		else e = launch_densify<T>(format, d_val, d_a, d_b, nullptr, nnz, outer, base, Vcol, mpad_, m_, n_, stream_);
 		if (e != hipSuccess) { st = hip_fail(e, "densify"); break; }
 		st = finish_upload(Vcol);
+		if (beta_dense_ && st == ST_OK) beta_uploaded_ = true;
 	} while (0);
 	if ((tiled_ || bf16_) && Vcol) (void)hipFree(Vcol);
 	if (d_val) (void)hipFree(d_val);
@@ -1114,6 +1163,23 @@ void Engine<T>::finalize_error(bool resolve) {
 		rmsd_ = frob_ / std::sqrt((double)nnz_);
 		masked_unresolved_ = false;
 	}
+	if (beta_pending_) {
+		(void)hipEventSynchronize(err_event_);
+		h_psN_.assign(pin_kl_, pin_kl_ + m_);                       // per-row sums of (v - p)^2
+		h_klrow_.assign(pin_kl_ + m_, pin_kl_ + 2 * (size_t)m_);    // per-row sums of the divergence
+		beta_pending_ = false;
+		beta_unresolved_ = true;
+	}
+	if (resolve && beta_unresolved_) {
+		// direct sums, in double, row order
+		double s = 0, d = 0;
+		for (int i = 0; i < m_; ++i) { s += (double)h_psN_[i]; d += (double)h_klrow_[i]; }
+		frob2_ = s;
+		frob_ = std::sqrt(s);
+		rmsd_ = frob_ / std::sqrt((double)m_ * (double)n_);
+		kl_ = d;
+		beta_unresolved_ = false;
+	}
 	if (kl_pending_) {
 		(void)hipEventSynchronize(err_event_);
 		h_psN_.assign(pin_kl_, pin_kl_ + m_);                       // per-row terms of tr(H^T W^T V)
@@ -1159,6 +1225,7 @@ Status Engine<T>::h_step(bool compute_error) {
 	// first call of an iteration in the sharded form: decides whether this iteration's products are timed
 	timing_now_ = timing_ && (timing_iter_++ % timing_stride_ == 0);
 	if (prm_.is_masked()) return masked_refuses("h_step");
+	if (beta_dense_) return beta_refuses("h_step");
 	if (prm_.divergence != 0) { kl_err_iter_ = compute_error; return kl_h_step(); }
 	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	return h_step_impl(compute_error);
@@ -1279,6 +1346,7 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 template <typename T>
 Status Engine<T>::w_products(T* exchange) {
 	if (prm_.is_masked()) return masked_refuses("w_products");
+	if (beta_dense_) return beta_refuses("w_products");
 	if (prm_.divergence != 0) return kl_w_products(exchange, kl_err_iter_);      // (sparse Frobenius compute shards through the code below: its two products are SpMMs over the shard's images)
 	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	T* ex_hht = exchange + (long)RP_ * mpad_;
@@ -1329,6 +1397,7 @@ Status Engine<T>::w_products(T* exchange) {
 template <typename T>
 Status Engine<T>::w_finish(const T* exchange, bool compute_error) {
 	if (prm_.is_masked()) return masked_refuses("w_finish");
+	if (beta_dense_) return beta_refuses("w_finish");
 	if (prm_.divergence != 0) return kl_w_finish(exchange, compute_error);
 	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	const T eps = std::numeric_limits<T>::epsilon();
@@ -1405,6 +1474,7 @@ Status Engine<T>::w_finish(const T* exchange, bool compute_error) {
 template <typename T>
 Status Engine<T>::w_finish_peers(const T* const* exchanges, int count, bool compute_error) {
 	if (prm_.is_masked()) return masked_refuses("w_finish_peers");
+	if (beta_dense_) return beta_refuses("w_finish_peers");
 	if (!direct_w_finish() || count < 1 || count > PEER_SLABS_MAX || exchanges == nullptr) return ST_INVALID;
 	if constexpr (std::is_same<T, float>::value) {
 		PeerSlabs panels = {}, hhts = {};
@@ -1425,6 +1495,7 @@ Status Engine<T>::w_finish_peers(const T* const* exchanges, int count, bool comp
 template <typename T>
 Status Engine<T>::w_update_rows(const T* num_rows, const T* hht, long row0, long rows, bool compute_error, T* colsq) {
 	if (prm_.is_masked()) return masked_refuses("w_update_rows");
+	if (beta_dense_) return beta_refuses("w_update_rows");
 	if (alg_ != ALG_MU && alg_ != ALG_NSNMF) return ST_INVALID;
 	if (rows <= 0 || rows % 128 != 0 || row0 < 0 || row0 % 128 != 0 || row0 + rows > mpad_) return ST_INVALID;
 	const T eps = std::numeric_limits<T>::epsilon();
@@ -1457,6 +1528,7 @@ Status Engine<T>::w_update_rows(const T* num_rows, const T* hht, long row0, long
 template <typename T>
 Status Engine<T>::w_normalize_rows(long row0, long rows, T* colsq) {
 	if (prm_.is_masked()) return masked_refuses("w_normalize_rows");
+	if (beta_dense_) return beta_refuses("w_normalize_rows");
 	if (rows <= 0 || rows % 128 != 0 || row0 < 0 || row0 + rows > mpad_) return ST_INVALID;
 	// colsq: the r sums of squares over ALL rows (one "partial"): kernel::normalizeColumns' sum > 0 ? x / sqrt(sum) : x
 	if constexpr (std::is_same<T, float>::value) {
@@ -1569,7 +1641,7 @@ template <typename T>
 bool Engine<T>::fused_capable() const {
 	// (evaluated before allocate(): no tiled_ here.  nsNMF (round 6): only on the split-operand products with the Gram matrices taken from the images -- x3_ is false
 	//  until the plan has chosen that path, so the one-pass request and the native-fp32 plan never see it)
-	return std::is_same<T, float>::value && RP_ == 64 &&
+	return std::is_same<T, float>::value && RP_ == 64 && !prm_.is_beta_dense() &&
 	       (alg_ == ALG_MU || (alg_ == ALG_NSNMF && x3_ && !bf16_ && !sparse_ && std::getenv("NMFAMD_GRAM_PARTIALS") == nullptr)) &&
 	       std::getenv("NMFAMD_FORCE_VALU") == nullptr && std::getenv("NMFAMD_NO_FUSED_MU") == nullptr;
 }
@@ -1646,7 +1718,7 @@ Status Engine<T>::iterate_fused32w(bool compute_error) {
 // (example/main.cpp: NmfDescription<double>, nsNMF, r = 158; the R binding).  NMFAMD_NO_FUSED_MU=1 keeps the generic launch sequence (the cross-check path).
 template <typename T>
 bool Engine<T>::fused64_capable() const {
-	return std::is_same<T, double>::value && tiled_ && !sparse_ && !bf16_ && (alg_ == ALG_MU || alg_ == ALG_NSNMF) && RP_ % 64 == 0 && RP_ <= 512 &&
+	return std::is_same<T, double>::value && tiled_ && !sparse_ && !bf16_ && !beta_dense_ && (alg_ == ALG_MU || alg_ == ALG_NSNMF) && RP_ % 64 == 0 && RP_ <= 512 &&
 	       (RP_ == 64 || panel_update_wide_f64_available(RP_)) && std::getenv("NMFAMD_FORCE_VALU") == nullptr && std::getenv("NMFAMD_NO_FUSED_MU") == nullptr;
 }
 
@@ -1973,6 +2045,7 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 	const T eps = std::numeric_limits<T>::epsilon();
 	timing_now_ = timing_ && (timing_iter_++ % timing_stride_ == 0);
 	if (prm_.is_masked()) return iterate_masked(compute_error, constant_w);      // (before the KL test: a masked engine never has divergence != 0, allocate())
+	if (beta_dense_) return iterate_beta(compute_error, constant_w);
 	if (prm_.divergence != 0) return constant_w ? ST_INVALID : iterate_kl(compute_error);
 	if (fused_capable() && !constant_w) return iterate_mu64(compute_error);
 	if (fused64_capable() && !constant_w) return iterate_fused64(compute_error);
@@ -2353,6 +2426,64 @@ Status Engine<T>::iterate_masked(bool compute_error, bool constant_w) {
 	}
 	if (!constant_w) HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, msq_part_, masked_norm_parts(m_), stream_));
 	return ST_OK;
+}
+
+// Dense beta-divergence update (docs/DIVERGENCE.md): generalised KL (beta = 1) or Itakura-Saito (beta = 0) on the dense images, one fused launch and one update
+// launch per half-step (kernels_beta.hip), in the skeleton of the other multiplicative iterations -- H step, W step with the new H, normalisation, error of the
+// pair (W_{k-1}, H_k) from the W launch's own evaluation of P:
+//   beta = 1:  H .*= (W^T (V ./ P)) ./ (colsum(W) + eps);  W .*= ((V ./ P) H^T) ./ (rowsum(H) + eps);  normalise the columns of W (H is not rescaled): iterate_kl's iteration
+//   beta = 0:  H .*= sqrt((W^T (V ./ P^2)) ./ (W^T (1 ./ P) + eps));  W likewise;  W(:, k) /= d_k, H(k, :) *= d_k with d_k = ||W(:, k)|| (W H unchanged)
+// Under constant W the H step runs alone; an error iteration then takes its terms from the terms-only form of the W-side launch.
+template <typename T>
+Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
+	if (!beta_uploaded_) { last_error_ = "dense divergence update: no V has been uploaded"; return ST_INVALID; }
+	const T eps = std::numeric_limits<T>::epsilon();
+	const int beta = prm_.beta();
+	const int partsH = (int)(npad_ / 128), partsW = (int)(mpad_ / 128);
+	// H step: X = the column-major image (row j of X = column j of V)
+	if (beta == 1 && !kl_sw_ready_) { HIPX(launch_panel_rowsum<T>(Wt_, RP_, (int)mpad_, rowsum_part_, sW_, stream_)); kl_sw_ready_ = true; }
+	record_begin();
+	HIPX(launch_beta_fused<T>(V_, mpad_, H_, Wt_, RP_, beta, true, false, eps, betaH_, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0,
+	                          (int)npad_, n_, m_, stream_));
+	record_end();
+	HIPX(launch_beta_update<T>(H_, slabs_, beta_den_, slab_stride_, betaH_.slabs, sW_, RP_, r_, (int)npad_, n_, eps, beta, true, (T*)nullptr,
+	                           beta == 1 ? rowsum_part_ : (T*)nullptr, (const T*)nullptr, (const T*)nullptr, 0, (T*)nullptr, (T*)nullptr, stream_));
+	if (beta == 1) HIPX(launch_kl_sums<T>(rowsum_part_, nullptr, partsH, RP_, sH_, stream_));
+	if (constant_w && !compute_error) return ST_OK;
+	// W step (or, under constant W, its terms-only form): X = the transposed image
+	T* tf = compute_error ? beta_tpart_ : (T*)nullptr;
+	T* td = compute_error ? beta_tpart_ + (long)BETA_MAX_SLABS * mpad_ : (T*)nullptr;
+	record_begin(1);
+	HIPX(launch_beta_fused<T>(Vt_, npad_, Wt_, H_, RP_, beta, !constant_w, compute_error, eps, betaW_, slabs_, beta_den_, slab_stride_, tf, td, mpad_,
+	                          (int)mpad_, m_, n_, stream_));
+	record_end();
+	HIPX(launch_beta_update<T>(Wt_, slabs_, beta_den_, slab_stride_, betaW_.slabs, sH_, RP_, r_, (int)mpad_, m_, eps, beta, !constant_w, sumsq_part_,
+	                           beta == 1 ? rowsum_part_ : (T*)nullptr, tf, td, mpad_, compute_error ? t_vwh_ : (T*)nullptr, compute_error ? t_kl_ : (T*)nullptr, stream_));
+	if (compute_error) {
+		finalize_error(false);      // (the pinned buffer is about to be reused; an older copy is long complete)
+		HIPX(hipMemcpyAsync(pin_kl_, t_vwh_, sizeof(T) * m_, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipMemcpyAsync(pin_kl_ + m_, t_kl_, sizeof(T) * m_, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipEventRecord(err_event_, stream_));
+		beta_pending_ = true;
+	}
+	if (constant_w) return ST_OK;
+	if (beta == 1) {
+		// as iterate_kl: the column sums of the NORMALISED W from the update's partials, then the normalisation itself
+		HIPX(launch_kl_sums<T>(rowsum_part_, sumsq_part_, partsW, RP_, sW_, stream_));
+		kl_sw_ready_ = true;
+		HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, partsW, stream_));
+	} else {
+		HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, partsW, stream_));
+	}
+	return ST_OK;
+}
+
+template <typename T>
+Status Engine<T>::beta_refuses(const char* what) {
+	static thread_local char text[160];
+	std::snprintf(text, sizeof(text), "dense divergence update: %s -- no three-phase / sharded form (single GPU)", what);
+	last_error_ = text;
+	return ST_INVALID;
 }
 
 template <typename T>

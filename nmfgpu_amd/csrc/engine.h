@@ -21,14 +21,18 @@ enum Algorithm { ALG_MU = 0, ALG_GDCLS = 1, ALG_ALS = 2, ALG_ACLS = 3, ALG_AHCLS
 struct AlgorithmParams {
 	double lambda = 0, lambdaW = 0, lambdaH = 0, alphaW = 0, alphaH = 0, theta = 0;
 	// extensions without a reference counterpart (selected by new Parameter names, see abi.cpp):
-	double divergence = 0;      // 0: Frobenius objective, 1: generalised KL divergence (multiplicative update only)
+	double divergence = 0;      // 0: Frobenius objective, 1: generalised KL divergence, 2: Itakura-Saito divergence (multiplicative update only; 2 is always the dense path)
 	double sparse_compute = 0;  // 1: keep V as CSR + CSC in HBM and multiply by SpMM instead of densifying
 	double precision = 0;       // 1: bf16 MFMA operands (V, W, H rounded to bf16 inside the two big products), fp32 everywhere else
 	double missing_values = 0;  // 1: fit the stored entries only (multiplicative update; implies sparse compute, kernels_masked.hip, docs/MISSING.md)
 	// HALS only (docs/HALS.md): L1 / L2 penalties on W and on H, scikit-learn's coordinate descent; all 0: the unpenalised iteration.  Engine::set_hals_penalties
 	// changes them between iterations.
 	double l1W = 0, l1H = 0, l2W = 0, l2H = 0;
+	double dense_compute = 0;   // 1 with divergence = 1: the KL update on a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) instead of over the stored entries
 	bool is_masked() const { return missing_values != 0; }
+	// the dense beta-divergence update: Itakura-Saito (beta = 0) always, generalised KL (beta = 1) with dense_compute
+	bool is_beta_dense() const { return divergence == 2 || (divergence == 1 && dense_compute != 0); }
+	int beta() const { return divergence == 2 ? 0 : 1; }
 	bool hals_penalised() const { return l1W != 0 || l1H != 0 || l2W != 0 || l2H != 0; }
 };
 
@@ -43,6 +47,19 @@ inline const char* hals_penalties_fault(double l1W, double l1H, double l2W, doub
 		any = any || x != 0;
 	}
 	if (any && !is_hals) return "HALS penalties: only the HALS algorithm takes l1W / l1H / l2W / l2H";
+	return nullptr;
+}
+
+// What the parameters of the dense beta-divergence update (docs/DIVERGENCE.md) must satisfy, stated once for Engine::allocate and nmfgpu::compute: nullptr, or why not.
+inline const char* beta_dense_fault(const AlgorithmParams& p, bool is_mu, int r, int row_blocks = 1) {
+	if (!(p.dense_compute == 0 || p.dense_compute == 1)) return "dense divergence update: 'denseCompute' has to be 0 or 1";
+	if (p.dense_compute != 0 && p.divergence == 0) return "dense divergence update: 'denseCompute' selects the dense form of a divergence ('divergence' = 1 or 2), not the Frobenius objective";
+	if (!p.is_beta_dense()) return nullptr;
+	if (!is_mu) return "dense divergence update: the Multiplicative algorithm only";
+	if (p.sparse_compute != 0 || p.missing_values != 0) return "dense divergence update: does not combine with 'sparseCompute' or 'missingValues' (V is kept dense; Itakura-Saito is undefined at 0)";
+	if (p.precision > 0) return "dense divergence update: no bf16 operands";
+	if (r > 256) return "dense divergence update: rank <= 256";
+	if (row_blocks > 1) return "dense divergence update: single GPU only (no row blocks)";
 	return nullptr;
 }
 
@@ -111,9 +128,10 @@ public:
 	// KL update (sparse V): the exchange also carries the row sums of the local H and, on error iterations, the per-row error terms:
 	//   [ numerator panel RP x mpad | H_g H_g^T RP x RP | rowsum(H_g) RP | tr terms mpad | KL terms mpad ]
 	// (masked engines have no three-phase form: no exchange)
-	long exchange_count() const { return prm_.is_masked() ? 0 : (long)RP_ * mpad_ + (long)RP_ * RP_ + (prm_.divergence != 0 ? (long)RP_ + 2 * mpad_ : 0); }
+	long exchange_count() const { return prm_.is_masked() || beta_dense_ ? 0 : (long)RP_ * mpad_ + (long)RP_ * RP_ + (prm_.divergence != 0 ? (long)RP_ + 2 * mpad_ : 0); }
 	bool is_kl() const { return prm_.divergence != 0; }
 	bool is_masked() const { return prm_.is_masked(); }
+	bool is_beta_dense() const { return beta_dense_; }
 	// sharded runs: the error terms refer to the whole matrix (sorted tr(V^T V) terms of ALL columns, sum of ALL entries, total column count)
 	void set_error_globals(const std::vector<T>& vtv_sorted_all, double sum_v_all, long total_columns) { h_vtv_ = vtv_sorted_all; sum_v_ = sum_v_all; err_total_columns_ = total_columns; }
 	double sum_v() const { return sum_v_; }
@@ -126,7 +144,7 @@ public:
 	Status w_normalize_rows(long row0, long rows, T* colsq);
 	void w_rows_replaced() { kl_sw_ready_ = false; kl_scale_pending_ = false; fused_ready_ = false; w_pending_ = false; f32w_pending_ = false; f64_pending_ = false; f64_product_ahead_ = false; h_product_ahead_ = false; gram_w_ready_ = false; wx3_valid_ = false; tri_gw_ready_ = false; qx3_holds_g_ = false; tri_scale_pending_ = false; tri_scale_from_gram_ = false; if (!tri_rows_cover_) wtb_valid_ = false; }
 	T* w_panel() { return Wt_; }
-	int kl_blocks(bool w_step) const { return prm_.divergence != 0 ? (w_step ? kl_blocks_w_ : kl_blocks_h_) : 0; }
+	int kl_blocks(bool w_step) const { return prm_.divergence != 0 && !beta_dense_ ? (w_step ? kl_blocks_w_ : kl_blocks_h_) : 0; }
 	int gram_k_slices() const { return gram_spread_ ? GRAM_REDUCE_BLOCKS : gram_ksplit_; }      // (16: the spread form)
 	bool w_col_split() const { return w_col_split_; }
 	int fused_launches() const {
@@ -163,6 +181,7 @@ public:
 	// asynchronously; the first reader waits for them and does the sorted summation, so a caller
 	// that does not look at the error every time (the benchmark loop) never stalls the stream.
 	double kl_divergence() { finalize_error(true); return kl_; }
+	double divergence_value() { finalize_error(true); return kl_; }      // the objective of whichever divergence the engine has (KL or Itakura-Saito)
 	bool sparse_mode() const { return sparse_; }
 	bool sparse_setup_on_device() const { return sparse_setup_on_device_; }
 	long nnz() const { return nnz_; }
@@ -190,9 +209,9 @@ public:
 	int slabs_h() const { return planH_.splits; }
 	int slabs_w() const { return planW_.splits; }
 	// which kernel runs the two big products: 0 fp32 MFMA, 1 bf16-rounded operands, 2 fp32 by exact 3 x bf16 splitting,
-	// 3 fp64 MFMA, 4 VALU fallback kernel (NMFAMD_FORCE_VALU), 5 sparse (SpMM)
+	// 3 fp64 MFMA, 4 VALU fallback kernel (NMFAMD_FORCE_VALU), 5 sparse (SpMM), 6 the fused dense beta-divergence half-step (kernels_beta.hip)
 	int resident_images() const { return sparse_ ? 0 : (one_image_ ? 1 : 2); }
-	int product_kernel() const { return sparse_ ? 5 : bf16_ ? 1 : x3_ ? 2 : !tiled_ ? 4 : (sizeof(T) == 8 ? 3 : 0); }
+	int product_kernel() const { return beta_dense_ ? 6 : sparse_ ? 5 : bf16_ ? 1 : x3_ ? 2 : !tiled_ ? 4 : (sizeof(T) == 8 ? 3 : 0); }
 	const char* last_error() const { return last_error_; }
 
 	// test access to device intermediates (panel layout, host copies)
@@ -229,6 +248,9 @@ private:
 	Status iterate_kl(bool compute_error);            // KL-divergence multiplicative update (sparse mode)
 	Status iterate_masked(bool compute_error, bool constant_w);   // multiplicative update over the stored entries only (kernels_masked.hip)
 	Status masked_refuses(const char* what);          // ST_INVALID with last_error_ set: no three-phase / sharded form of the masked update
+	Status iterate_beta(bool compute_error, bool constant_w);     // dense beta-divergence multiplicative update (kernels_beta.hip, docs/DIVERGENCE.md)
+	Status beta_refuses(const char* what);            // ... nor of the dense beta-divergence update
+	Status beta_check_values(const T* values, long count, long ld, long rows);   // upload: beta = 0 needs finite values > 0, beta = 1 finite values >= 0
 	Status fetch_error_terms(int count_n);            // enqueue the copies, do not wait
 	void finalize_error(bool resolve);
 	void record_begin(int kind = 0);
@@ -297,6 +319,12 @@ private:
 	// masked update: per-workgroup sums of squares of the new W rows ([MASKED_NORM_PARTS + 16][RP]); the per-row residual terms travel through pin_kl_ (first m)
 	T* msq_part_ = nullptr;
 	bool masked_pending_ = false, masked_unresolved_ = false;
+	// dense beta-divergence update: V_ is the column-major image (the H step's), Vt_ its transpose (the W step's); slabs_ holds the slabs' partial numerators,
+	// beta_den_ their partial denominators (beta = 0), beta_tpart_ the slabs' parts of the two per-row error terms ([2][BETA_MAX_SLABS][mpad])
+	bool beta_dense_ = false, beta_uploaded_ = false;
+	BetaPlan betaH_, betaW_;
+	T *beta_den_ = nullptr, *beta_tpart_ = nullptr;
+	bool beta_pending_ = false, beta_unresolved_ = false;
 	// rank-64 MU fast path: W is kept unnormalised with a pending column scale (kernels_mu64.hip)
 	float *gramW_part_ = nullptr, *gramH_part_ = nullptr, *scale_ = nullptr, *Graw64_ = nullptr;
 	bool w_col_split_ = false;       // V H^T from 128 x 32 workgroups and one slab (narrow column shards, Engine::init)

@@ -24,6 +24,11 @@ class _Params(C.Structure):
                                           "missing_values")]
 
 
+class _ParamsV2(C.Structure):
+    """nmfamd_params_v2: the frozen struct followed by the fields added since (nmfamd_engine_create_v2 takes it with its size)."""
+    _fields_ = [("base", _Params), ("dense_compute", C.c_double)]
+
+
 class _Geometry(C.Structure):
     _fields_ = [("m", C.c_int), ("n", C.c_int), ("r", C.c_int), ("padded_rank", C.c_int),
                 ("padded_m", C.c_long), ("padded_n", C.c_long), ("slabs_h", C.c_int), ("slabs_w", C.c_int),
@@ -54,8 +59,12 @@ class Engine:
     def __init__(self, m: int, n: int, r: int, algorithm: str = "mu", dtype=np.float32, stream: int = 0,
                  lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence: str = "frobenius",
                  sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False,
-                 l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0):
-        """missing_values=True: fit the observed entries only (docs/MISSING.md) -- the stored entries of upload_sparse, the non-NaN entries of
+                 l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False):
+        """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V) or
+        "is" (Itakura-Saito, always dense: every entry of V > 0) -- docs/DIVERGENCE.md.  The dense divergence engines are "mu" only, rank <= 256, single GPU;
+        divergence_value reports their objective.
+
+        missing_values=True: fit the observed entries only (docs/MISSING.md) -- the stored entries of upload_sparse, the non-NaN entries of
         upload (zeros included).  Multiplicative update ("mu") with the Frobenius objective only; implies sparse_compute.
 
         l1_w, l1_h, l2_w, l2_h: "hals" only (docs/HALS.md) -- the L1 / L2 penalties of scikit-learn's coordinate descent on W and H; see
@@ -66,9 +75,9 @@ class Engine:
             raise TypeError("float32 or float64")
         self.m, self.n, self.r = m, n, r
         self._ctor = dict(algorithm=algorithm, stream=stream, row_blocks=row_blocks,
-                          params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0}[divergence],
+                          params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0, "is": 2.0}[divergence],
                                   float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
-                                  float(missing_values)],
+                                  float(missing_values), float(dense_compute)],
                           penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)])
         self._h = None
         self._lib.nmfamd_engine_frobenius.restype = C.c_double
@@ -80,10 +89,15 @@ class Engine:
 
     def _create(self):
         c = self._ctor
-        p = _Params(*c["params"])
+        p = _ParamsV2(_Params(*c["params"][:10]), *c["params"][10:])
         h = C.c_void_p()
         # row_blocks > 1: the padded row count is a multiple of 128 * row_blocks (row-block form of the sharded W step)
-        st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p), self.dtype.itemsize,
+        if not hasattr(self._lib, "nmfamd_engine_create_v2"):
+            # (NMFAMD_LIBRARY names a build from before the sized entry -- tools/time_beta.py times such a build: it reads the frozen struct only)
+            st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p.base), self.dtype.itemsize,
+                                                       C.c_void_p(c["stream"]), int(c["row_blocks"]), C.byref(h))
+        else:
+            st = self._lib.nmfamd_engine_create_v2(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p), C.c_ulong(C.sizeof(p)), self.dtype.itemsize,
                                                    C.c_void_p(c["stream"]), int(c["row_blocks"]), C.byref(h))
         if st != 0:
             raise EngineError(st, "nmfamd_engine_create", (self._lib.nmfamd_engine_last_error(None) or b"").decode())
@@ -184,6 +198,13 @@ class Engine:
     @property
     def kl_divergence(self) -> float:
         return float(self._lib.nmfamd_engine_kl_divergence(self._h))
+
+    @property
+    def divergence_value(self) -> float:
+        """The objective of whichever divergence the engine has (generalised KL or Itakura-Saito), of the most recent error iteration."""
+        fn = self._lib.nmfamd_engine_divergence
+        fn.restype = C.c_double
+        return float(fn(self._h))
 
     @property
     def rmsd(self) -> float:
@@ -597,6 +618,38 @@ def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_v
         raise EngineError(st, "nmfamd_op_hals_sweep")
     k = parts.value
     return {"P": P, "ps": ps, "sumsq_part": None if sumsq_part is None else sumsq_part[:k * RP].reshape(k, RP), "parts": k}
+
+
+def op_beta_half_step(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: int, out_valid: int, red_valid: int, beta: int, form: int = 0, *,
+                      dsum: Optional[np.ndarray] = None, force_slabs: int = 0):
+    """One half-step of the dense beta-divergence update (nmfamd_op_beta_half_step_*) on padded arrays: A (out_pad, RP) the panel that is updated, B (red_pad, RP)
+    the other panel, X (out_pad, ldx) the image of V (X[o, k]; zero on the padding).  beta: 1 (KL; dsum = the RP column sums of B) or 0 (Itakura-Saito).
+    form: 0 update, 1 update + error terms, 2 error terms only.  Returns a dict: `A` (the new panel), `t_frob`, `t_div` (out_pad values each; None for form 0),
+    `sumsq_part`, `sum_part` ((out_pad // 128, RP)) and `slabs`."""
+    dt = np.dtype(A.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("float32 or float64")
+    A = np.array(A, dtype=dt, order="C"); B = np.ascontiguousarray(B, dtype=dt); X = np.ascontiguousarray(X, dtype=dt)
+    out_pad, RP = A.shape
+    red_pad = B.shape[0]
+    if B.shape[1] != RP or X.shape[0] != out_pad or X.shape[1] < red_pad:
+        raise ValueError("shapes: A (out_pad, RP); B (red_pad, RP); X (out_pad, >= red_pad)")
+    d = None if dsum is None else np.ascontiguousarray(dsum, dtype=dt)
+    if d is not None and d.shape != (RP,):
+        raise ValueError("dsum must hold RP values")
+    terms = form in (1, 2)
+    tf = np.zeros(out_pad, dt) if terms else None
+    td = np.zeros(out_pad, dt) if terms else None
+    parts = out_pad // 128
+    sq, sm = np.zeros((max(parts, 1), RP), dt), np.zeros((max(parts, 1), RP), dt)
+    slabs = C.c_int(0)
+    fn = library().nmfamd_op_beta_half_step_f32 if dt == np.float32 else library().nmfamd_op_beta_half_step_f64
+    ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+    st = fn(ptr(A), ptr(B), ptr(X), C.c_long(X.shape[1]), RP, int(r), out_pad, int(out_valid), red_pad, int(red_valid), int(beta), int(form), int(force_slabs),
+            ptr(d), ptr(tf), ptr(td), ptr(sq), ptr(sm), C.byref(slabs))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_beta_half_step")
+    return {"A": A, "t_frob": tf, "t_div": td, "sumsq_part": sq, "sum_part": sm, "slabs": slabs.value}
 
 
 def op_hals_normalize(Wt: np.ndarray, H: np.ndarray, sumsq_part: np.ndarray):

@@ -1,0 +1,88 @@
+"""Iteration times of the dense beta-divergence update (docs/DIVERGENCE.md) on one strictly positive dense V: the dense KL iteration (--mode dense-kl), the
+Itakura-Saito iteration (--mode is), and the KL iteration that takes the sparse route for dense input (--mode kl: what a build without the dense path runs).
+
+One process per run: without --child this script starts --runs fresh child processes one after the other and prints their figures with the median and the
+spread.  A child warms up, then times plain iterations and error iterations (wall time per iteration, stream synchronised around each block) and reads the
+event-timed H-side / W-side launches (nmfamd_engine_kernel_timing_read3).  NMFAMD_LIBRARY selects the library, so the same script times another build.
+
+    python tools/time_beta.py --mode dense-kl [--rows 10000] [--cols 5000] [--rank 64] [--iters 50] [--warmup 10] [--runs 5]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def problem(m, n, r, seed=7):
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    V = (rng.random((m, 5), dtype=np.float32) @ rng.random((5, n), dtype=np.float32)) * rng.gamma(8.0, 1.0 / 8.0, (m, n)).astype(np.float32) + np.float32(1e-3)
+    W = (1.0 - rng.random((m, r))).astype(np.float32)
+    H = (1.0 - rng.random((r, n))).astype(np.float32)
+    return np.asfortranarray(V), np.asfortranarray(W), np.asfortranarray(H)
+
+
+def time_block(eng, iters, error_every):
+    eng.synchronize()
+    t0 = time.perf_counter()
+    eng.iterate(iters, first_iteration=1, error_every=error_every, last_iteration=0)
+    eng.synchronize()
+    if error_every:
+        eng.frobenius      # (waits for the last error terms and sums them)
+    return (time.perf_counter() - t0) / iters * 1e3
+
+
+def child(a):
+    import nmfgpu_amd as na
+    V, W, H = problem(a.rows, a.cols, a.rank)
+    kw = {"dense-kl": dict(divergence="kl", dense_compute=True), "is": dict(divergence="is"), "kl": dict(divergence="kl")}[a.mode]
+    eng = na.Engine(a.rows, a.cols, a.rank, "mu", **kw)
+    eng.upload(V)
+    eng.set_factors(W, H)
+    eng.iterate(a.warmup, first_iteration=1, error_every=0, last_iteration=0)
+    plain = time_block(eng, a.iters, 0)
+    err = time_block(eng, a.iters, 1)
+    eng.kernel_timing(1)
+    eng.iterate(a.iters, first_iteration=1, error_every=0, last_iteration=0)
+    _, _, idle, (ms_h, ms_w), (c_h, c_w) = eng.kernel_timing_read3()
+    eng.kernel_timing(0)
+    g = eng.geometry()
+    out = {"mode": a.mode, "rows": a.rows, "cols": a.cols, "rank": a.rank, "ms_iteration": plain, "ms_error_iteration": err, "ms_h_launch": ms_h / max(c_h, 1),
+           "ms_w_launch": ms_w / max(c_w, 1), "ms_idle_event_pair": idle, "product_kernel": g["product_kernel"], "slabs_h": g["slabs_h"], "slabs_w": g["slabs_w"],
+           "frobenius": eng.frobenius}
+    eng.close()
+    print(json.dumps(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["dense-kl", "is", "kl"], default="dense-kl")
+    ap.add_argument("--rows", type=int, default=10000)
+    ap.add_argument("--cols", type=int, default=5000)
+    ap.add_argument("--rank", type=int, default=64)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--child", action="store_true")
+    a = ap.parse_args()
+    if a.child:
+        return child(a)
+    results = []
+    for _ in range(a.runs):
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--mode", a.mode, "--rows", str(a.rows), "--cols", str(a.cols), "--rank", str(a.rank),
+               "--iters", str(a.iters), "--warmup", str(a.warmup)]
+        line = subprocess.run(cmd, check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout.strip().splitlines()[-1]
+        print(line, flush=True)
+        results.append(json.loads(line))
+    for key in ("ms_iteration", "ms_error_iteration", "ms_h_launch", "ms_w_launch"):
+        vals = [r[key] for r in results]
+        print(f"{a.mode} {a.rows} x {a.cols} r {a.rank} {key}: median {statistics.median(vals):.4f} min {min(vals):.4f} max {max(vals):.4f} ({len(vals)} runs)")
+
+
+if __name__ == "__main__":
+    main()
