@@ -40,7 +40,8 @@ enum {
 };
 
 /* algorithm ids = nmfgpu::NmfAlgorithm (include/nmfgpu.h:107-114; NMFAMD_HALS is an extension: coordinate descent, docs/HALS.md -- dense or
-   sparse compute, L1 / L2 penalties through nmfamd_engine_set_hals_penalties, no three-phase / sharded form) */
+   sparse compute, L1 / L2 penalties through nmfamd_engine_set_hals_penalties, no three-phase / sharded form).  The dense divergence engines (NMFAMD_MU with
+   divergence 2, 3, or 1 with dense_compute) take the same penalties on their multiplicative update (docs/DIVERGENCE.md) */
 enum { NMFAMD_MU = 0, NMFAMD_GDCLS = 1, NMFAMD_ALS = 2, NMFAMD_ACLS = 3, NMFAMD_AHCLS = 4, NMFAMD_NSNMF = 5, NMFAMD_HALS = 6 };
 
 /* sparse formats = nmfgpu::StorageFormat (include/nmfgpu.h:177-186) */
@@ -58,7 +59,8 @@ typedef struct nmfamd_params {
 	/* extensions without a reference counterpart (nmfgpu::compute: Parameter names "divergence", "sparseCompute") */
 	double divergence;      /* 0 = Frobenius objective; 1 = generalised KL divergence (Multiplicative only; over the stored entries of a sparse image of V -- implies
 	                           sparse_compute -- unless nmfamd_params_v2.dense_compute = 1); 2 = Itakura-Saito divergence (Multiplicative only, always the dense path of
-	                           docs/DIVERGENCE.md: every entry of V finite and > 0, dense input only) */
+	                           docs/DIVERGENCE.md: every entry of V finite and > 0, dense input only); 3 = the beta-divergence at nmfamd_params_v3.beta (Multiplicative only,
+	                           always the dense path; nmfamd_engine_create_v2) */
 	double sparse_compute;  /* 1 = keep V as CSR + CSC in HBM and use SpMM / SDDMM kernels instead of densifying (Multiplicative, and HALS with
 	                           divergence 0; rank <= 256) */
 	double precision;       /* Parameter "precision", float engines only.  0 = fp32 accuracy: products on the bf16 matrix pipe with every
@@ -84,6 +86,18 @@ typedef struct nmfamd_params_v2 {
 	                           An upload that breaks the value rule returns NMFAMD_INVALID_ARGUMENT with nmfamd_engine_last_error set */
 } nmfamd_params_v2;
 
+/* nmfamd_params_v2 followed by what has been added since (nmfamd_params_v2 keeps its size: callers pass sizeof of the struct they were built with).
+ * nmfamd_engine_create_v2 reads min(params_size, sizeof(nmfamd_params_v3)) bytes and takes the rest as 0. */
+typedef struct nmfamd_params_v3 {
+	nmfamd_params_v2 v2;
+	double beta;            /* Parameter "beta", with v2.base.divergence = 3: the beta of the beta-divergence, any finite value (0.5 and 1.5 are the usual choices for
+	                           magnitude spectrograms; 2 is the Frobenius objective run as a multiplicative divergence update).  The multiplicative update of
+	                           scikit-learn's solver="mu" on a dense resident V (docs/DIVERGENCE.md); beta is taken in the engine's precision.  beta = 0 and beta = 1 run the
+	                           engines of divergence = 2 and of divergence = 1 with dense_compute, bit for bit.  beta <= 0: every entry of V finite and > 0, dense
+	                           input only; beta > 0: finite and >= 0, sparse input is densified.  A non-zero beta with another divergence, and a non-finite beta, are
+	                           refused.  The limits of the dense divergence engines (nmfamd_params_v2.dense_compute) apply */
+} nmfamd_params_v3;
+
 typedef struct nmfamd_engine nmfamd_engine;  /* opaque; owns every device buffer of one factorisation */
 
 /* Number of visible HIP devices (0 when there is none), and the library's build description. */
@@ -98,8 +112,8 @@ NMFAMD_API const char* nmfamd_engine_last_error(const nmfamd_engine* e);
  * every kernel and copy of this engine is issued on it. */
 NMFAMD_API int nmfamd_engine_create(int m, int n, int r, int algorithm, const nmfamd_params* params,
                                     int elem_bytes, void* stream, nmfamd_engine** out);
-/* The same with the sized, extended parameter struct (nmfamd_params_v2; params_size = sizeof of the caller's struct, at least sizeof(nmfamd_params) unless
- * params is NULL) and the row blocks of nmfamd_engine_create_blocks (1: none). */
+/* The same with the sized, extended parameter struct (nmfamd_params_v2 or nmfamd_params_v3; params_size = sizeof of the caller's struct, at least
+ * sizeof(nmfamd_params) unless params is NULL) and the row blocks of nmfamd_engine_create_blocks (1: none). */
 NMFAMD_API int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* params, unsigned long params_size,
                                        int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out);
 NMFAMD_API void nmfamd_engine_destroy(nmfamd_engine* e);
@@ -129,10 +143,12 @@ NMFAMD_API int nmfamd_engine_iterate(nmfamd_engine* e, int count, int first_iter
 NMFAMD_API int nmfamd_engine_synchronize(nmfamd_engine* e);
 /* HALS engines: the penalties of scikit-learn's coordinate descent, which then minimises
  *   1/2 ||V - W H||^2 + l1W ||W||_1 + l1H ||H||_1 + 1/2 l2W ||W||^2 + 1/2 l2H ||H||^2     (docs/HALS.md has the mapping from alpha_W, alpha_H, l1_ratio).
+ * Dense divergence engines (divergence 2, 3, or 1 with dense_compute): the same four terms added to the divergence, by scikit-learn's solver="mu" -- each
+ * half-step's denominator carries + l1 + l2 A before the power (docs/DIVERGENCE.md); nmfamd_engine_divergence keeps reporting the divergence alone.
  * Valid any time between iterations (a regularisation path on one resident V); takes effect at the next nmfamd_engine_iterate.  While any of the four is
  * non-zero the column normalisation of W is skipped; all zeros restores the unpenalised iteration.  nmfamd_engine_frobenius / _rmsd keep reporting
  * ||V - W H||, not the penalised objective.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error) for a negative or non-finite value, and for a
- * non-zero value on an engine of another algorithm. */
+ * non-zero value on any other engine. */
 NMFAMD_API int nmfamd_engine_set_hals_penalties(nmfamd_engine* e, double l1W, double l1H, double l2W, double l2H);
 /* Frobenius norm / RMSD of the most recent error iteration (IAlgorithm::frobeniusNorm / rmsd). */
 NMFAMD_API double nmfamd_engine_frobenius(nmfamd_engine* e);
@@ -140,7 +156,8 @@ NMFAMD_API double nmfamd_engine_rmsd(nmfamd_engine* e);
 /* Generalised KL divergence D(V || W H) of the most recent error iteration (divergence = 1 only). */
 NMFAMD_API double nmfamd_engine_kl_divergence(nmfamd_engine* e);
 /* The objective of whichever divergence the engine has, of the most recent error iteration: the generalised KL divergence (divergence = 1, sparse or dense: equal to
- * nmfamd_engine_kl_divergence) or the Itakura-Saito divergence sum (v / p - log(v / p) - 1), p = (W H) + eps (divergence = 2). */
+ * nmfamd_engine_kl_divergence), the Itakura-Saito divergence sum (v / p - log(v / p) - 1), p = (W H) + eps (divergence = 2), or the beta-divergence
+ * sum (v^beta + (beta - 1) p^beta - beta v p^(beta - 1)) / (beta (beta - 1)) with v^beta = 0 at v = 0 (divergence = 3).  The divergence alone: no penalty terms. */
 NMFAMD_API double nmfamd_engine_divergence(nmfamd_engine* e);
 
 /* Dominant-kernel timing.  enable = k > 0: every launch of the factor-product kernel (the two
@@ -389,6 +406,14 @@ NMFAMD_API int nmfamd_op_beta_half_step_f32(float* A, const float* B, const floa
 NMFAMD_API int nmfamd_op_beta_half_step_f64(double* A, const double* B, const double* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid,
                                             int beta, int form, int force_slabs, const double* dsum, double* t_frob, double* t_div, double* sumsq_part, double* sum_part,
                                             int* slabs);
+/* The same with any finite beta (0 and 1 run the launches above; every other value the general form, where t_div is the beta-divergence of
+ * nmfamd_engine_divergence) and penalties l1, l2 >= 0 on the updated panel: A <- A (num / (den + eps + l1 + l2 A))^gamma.  dsum: beta = 1 only. */
+NMFAMD_API int nmfamd_op_beta_half_step_general_f32(float* A, const float* B, const float* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad,
+                                                    int red_valid, double beta, double l1, double l2, int form, int force_slabs, const float* dsum, float* t_frob,
+                                                    float* t_div, float* sumsq_part, float* sum_part, int* slabs);
+NMFAMD_API int nmfamd_op_beta_half_step_general_f64(double* A, const double* B, const double* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad,
+                                                    int red_valid, double beta, double l1, double l2, int form, int force_slabs, const double* dsum, double* t_frob,
+                                                    double* t_div, double* sumsq_part, double* sum_part, int* slabs);
 /* Test access to an engine's device intermediates in panel layout: which = 0 Wt, 1 H, 2 W^T W,
  * 3 H H^T, 4 slabs, 5 inverse, 6 V, 7 Vt; rank-256 fp32 engines also 8 W^T W as last reduced, 9 staged column sums of squares,
  * 10 / 11 the bf16 fragments of W / H as 4-byte words. */

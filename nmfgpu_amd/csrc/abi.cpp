@@ -216,6 +216,15 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		// "divergence" = 2 (Itakura-Saito) and "denseCompute" = 1 with "divergence" = 1 (dense KL): the dense beta-divergence update (docs/DIVERGENCE.md)
 		idx = parameter_index(d.parameters, d.numParameters, "denseCompute");
 		if (idx >= 0) prm.dense_compute = d.parameters[idx].value;
+		// "divergence" = 3 with "beta": the general beta-divergence, always the dense update; a "beta" without it is refused whatever its value
+		idx = parameter_index(d.parameters, d.numParameters, "beta");
+		if (idx >= 0) {
+			prm.beta_value = d.parameters[idx].value;
+			if (prm.divergence != 3) {
+				log_error("[ERROR] Parameter 'beta' needs 'divergence' = 3 (the general beta-divergence)!");
+				return ResultType::ErrorInvalidArgument;
+			}
+		}
 		// (HALS takes sparse compute with the Frobenius objective: its two products against V are the SpMM launches of the sparse multiplicative update)
 		const bool sparse_hals = d.algorithm == NmfAlgorithm::HALS && prm.divergence == 0;
 		if ((prm.divergence != 0 || prm.sparse_compute != 0) && d.algorithm != NmfAlgorithm::Multiplicative && !sparse_hals) {
@@ -237,7 +246,8 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		return ResultType::ErrorInvalidArgument;
 	}
 	{
-		// "l1W", "l1H", "l2W", "l2H" (docs/HALS.md): the penalties of scikit-learn's coordinate descent on the HALS sweeps; absent = 0
+		// "l1W", "l1H", "l2W", "l2H": the penalties of scikit-learn's coordinate descent on the HALS sweeps (docs/HALS.md) and of its multiplicative update on the
+		// dense divergence updates (docs/DIVERGENCE.md: "divergence" 2, 3, and 1 with "denseCompute"); absent = 0
 		struct { const char* name; double* slot; } pen[] = {{"l1W", &prm.l1W}, {"l1H", &prm.l1H}, {"l2W", &prm.l2W}, {"l2H", &prm.l2H}};
 		for (auto& p : pen) {
 			const int idx = parameter_index(d.parameters, d.numParameters, p.name);
@@ -245,7 +255,7 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 			*p.slot = d.parameters[idx].value;
 		}
 		// (the engine's own rule, asked here so that a refusal comes before any device work)
-		if (const char* why = nmfamd::hals_penalties_fault(prm.l1W, prm.l1H, prm.l2W, prm.l2H, sizeof(T) == 4, d.algorithm == NmfAlgorithm::HALS)) {
+		if (const char* why = nmfamd::hals_penalties_fault(prm.l1W, prm.l1H, prm.l2W, prm.l2H, sizeof(T) == 4, prm.takes_penalties(d.algorithm == NmfAlgorithm::HALS))) {
 			log_error((std::string("[ERROR] ") + why).c_str());
 			return ResultType::ErrorInvalidArgument;
 		}
@@ -321,7 +331,7 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 			return ResultType::ErrorInvalidArgument;
 		}
 		if (num_gpus > 1 && prm.is_beta_dense()) {
-			log_error("[ERROR] 'numGpus' > 1 is not available with the dense divergence update ('divergence' = 2, 'denseCompute')!");
+			log_error("[ERROR] 'numGpus' > 1 is not available with the dense divergence update ('divergence' = 2 or 3, 'denseCompute')!");
 			return ResultType::ErrorInvalidArgument;
 		}
 		if (num_gpus > 1 && d.algorithm == NmfAlgorithm::HALS) {

@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <memory>
@@ -168,16 +169,17 @@ int nmfamd_engine_create_blocks(int m, int n, int r, int algorithm, const nmfamd
 
 int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* params_sized, unsigned long params_size, int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out) {
 	if (params_sized != nullptr && params_size < sizeof(nmfamd_params)) return NMFAMD_INVALID_ARGUMENT;
-	nmfamd_params_v2 v2;
-	std::memset(&v2, 0, sizeof(v2));
-	if (params_sized != nullptr) std::memcpy(&v2, params_sized, params_size < sizeof(v2) ? (size_t)params_size : sizeof(v2));
+	nmfamd_params_v3 v3;
+	std::memset(&v3, 0, sizeof(v3));
+	if (params_sized != nullptr) std::memcpy(&v3, params_sized, params_size < sizeof(v3) ? (size_t)params_size : sizeof(v3));
+	const nmfamd_params_v2& v2 = v3.v2;
 	const nmfamd_params* params = params_sized != nullptr ? &v2.base : nullptr;
 	if (!out || (elem_bytes != 4 && elem_bytes != 8) || row_blocks < 1 || row_blocks > 64) return NMFAMD_INVALID_ARGUMENT;
 	*out = nullptr;
 	g_create_error.clear();
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	AlgorithmParams p;
-	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; p.dense_compute = v2.dense_compute; }
+	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; p.dense_compute = v2.dense_compute; p.beta_value = v3.beta; }
 	nmfamd_engine* e = new (std::nothrow) nmfamd_engine();
 	if (!e) return NMFAMD_NO_HOST_MEMORY;
 	e->elem_bytes = elem_bytes;
@@ -880,10 +882,13 @@ int op_hals_normalize(T* Wt, int RP, int mpad, T* H, int npad, const T* sumsq_pa
 }
 
 template <typename T>
-int op_beta_half_step(T* A, const T* B, const T* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid, int beta, int form,
-                      int force_slabs, const T* dsum, T* t_frob, T* t_div, T* sumsq_part, T* sum_part, int* slabs) {
+int op_beta_half_step(T* A, const T* B, const T* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid, double beta_value, double l1d,
+                      double l2d, int form, int force_slabs, const T* dsum, T* t_frob, T* t_div, T* sumsq_part, T* sum_part, int* slabs) {
 	const bool update = form == 0 || form == 1, terms = form == 1 || form == 2;
-	if (!A || !B || !X || !beta_half_step_available(RP) || r < 1 || r > RP || (beta != 0 && beta != 1) || form < 0 || form > 2 || out_pad < 128 || out_pad % 128 != 0 ||
+	const double beta = (double)(T)beta_value;      // (in the precision of T, as the launchers take it)
+	const T l1 = (T)l1d, l2 = (T)l2d;
+	if (!A || !B || !X || !beta_half_step_available(RP) || r < 1 || r > RP || !std::isfinite(beta) || !(l1d >= 0) || !(l2d >= 0) || !std::isfinite((double)l1) ||
+	    !std::isfinite((double)l2) || form < 0 || form > 2 || out_pad < 128 || out_pad % 128 != 0 ||
 	    red_pad < 128 || red_pad % 128 != 0 || out_valid < 0 || out_valid > out_pad || red_valid < 0 || red_valid > red_pad || ldx < red_pad || ldx % 4 != 0 ||
 	    force_slabs < 0 || (update && beta == 1 && !dsum) || (terms && (!t_frob || !t_div)))
 		return NMFAMD_INVALID_ARGUMENT;
@@ -914,7 +919,7 @@ int op_beta_half_step(T* A, const T* B, const T* X, long ldx, int RP, int r, int
 	if (launch_beta_fused<T>((const T*)dX.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update, terms, eps, plan, (T*)dNum.p, (T*)dDen.p, part_stride, tf, td, out_pad,
 	                         out_pad, out_valid, red_valid, nullptr) != hipSuccess)
 		return NMFAMD_HIP_ERROR;
-	if (launch_beta_update<T>((T*)dA.p, (const T*)dNum.p, (const T*)dDen.p, part_stride, plan.slabs, (const T*)dD.p, RP, r, out_pad, out_valid, eps, beta, update,
+	if (launch_beta_update<T>((T*)dA.p, (const T*)dNum.p, (const T*)dDen.p, part_stride, plan.slabs, (const T*)dD.p, RP, r, out_pad, out_valid, eps, beta, l1, l2, update,
 	                          (T*)dSum.p, (T*)dSum.p + parts, tf, td, out_pad, of, od, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
 		return NMFAMD_HIP_ERROR;
 	if (hipMemcpy(A, dA.p, panelA, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
@@ -930,12 +935,26 @@ extern "C" {
 
 int nmfamd_op_beta_half_step_f32(float* A, const float* B, const float* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid, int beta,
                                  int form, int force_slabs, const float* dsum, float* t_frob, float* t_div, float* sumsq_part, float* sum_part, int* slabs) {
-	return op_beta_half_step<float>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, beta, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs);
+	if (beta != 0 && beta != 1) return NMFAMD_INVALID_ARGUMENT;
+	return op_beta_half_step<float>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, (double)beta, 0.0, 0.0, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs);
 }
 
 int nmfamd_op_beta_half_step_f64(double* A, const double* B, const double* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid, int beta,
                                  int form, int force_slabs, const double* dsum, double* t_frob, double* t_div, double* sumsq_part, double* sum_part, int* slabs) {
-	return op_beta_half_step<double>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, beta, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs);
+	if (beta != 0 && beta != 1) return NMFAMD_INVALID_ARGUMENT;
+	return op_beta_half_step<double>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, (double)beta, 0.0, 0.0, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs);
+}
+
+int nmfamd_op_beta_half_step_general_f32(float* A, const float* B, const float* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid,
+                                         double beta, double l1, double l2, int form, int force_slabs, const float* dsum, float* t_frob, float* t_div,
+                                         float* sumsq_part, float* sum_part, int* slabs) {
+	return op_beta_half_step<float>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, beta, l1, l2, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs);
+}
+
+int nmfamd_op_beta_half_step_general_f64(double* A, const double* B, const double* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid,
+                                         double beta, double l1, double l2, int form, int force_slabs, const double* dsum, double* t_frob, double* t_div,
+                                         double* sumsq_part, double* sum_part, int* slabs) {
+	return op_beta_half_step<double>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, beta, l1, l2, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs);
 }
 
 int nmfamd_op_hals_sweep_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid, float* ps,

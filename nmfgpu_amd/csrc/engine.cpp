@@ -180,6 +180,11 @@ Status Engine<T>::allocate() {
 	if (Status s = set_hals_penalties(prm_.l1W, prm_.l1H, prm_.l2W, prm_.l2H)) return s;      // (values that came with the parameters: the setter's checks, and its rounding of prm_ to T)
 	if (const char* why = beta_dense_fault(prm_, alg_ == ALG_MU, r_, row_blocks_)) { last_error_ = why; return ST_INVALID; }
 	beta_dense_ = prm_.is_beta_dense();
+	if (beta_dense_) {
+		// beta in the engine's precision, as the penalties: a value that rounds to 0 or 1 there IS the Itakura-Saito or the dense KL engine
+		beta_ = (double)(T)prm_.beta();
+		if (!std::isfinite(beta_)) { last_error_ = "dense divergence update: 'beta' out of the range of the engine's precision"; return ST_INVALID; }
+	}
 	int dev = 0;
 	HIPX(hipGetDevice(&dev));
 	hipDeviceProp_t prop;
@@ -375,7 +380,7 @@ Status Engine<T>::allocate() {
 		HIPX(dalloc(&sW_, RP_));
 		HIPX(dalloc(&sH_, RP_));
 		HIPX(dalloc(&beta_tpart_, 2l * BETA_MAX_SLABS * mpad_));
-		if (prm_.beta() == 0) HIPX(dalloc(&beta_den_, slab_elems));
+		if (beta_ != 1) HIPX(dalloc(&beta_den_, slab_elems));
 		HIPX(hipHostMalloc((void**)&pin_kl_, sizeof(T) * (2 * (size_t)m_ + 3 * (size_t)RP_)));
 	}
 	HIPX(dalloc(&Wt_, panelW));
@@ -616,15 +621,18 @@ Status Engine<T>::upload_dense(const T* V, long ld) {
 	return st;
 }
 
-// The dense beta-divergence update's demand on V: every entry finite, and > 0 at beta = 0 (Itakura-Saito is undefined at 0) or >= 0 at beta = 1
+// The dense beta-divergence update's demand on V: every entry finite, and > 0 at beta <= 0 (such a divergence is undefined at 0) or >= 0 at beta > 0
 template <typename T>
 Status Engine<T>::beta_check_values(const T* values, long count, long ld, long rows) {
-	const bool is = prm_.beta() == 0;
+	const bool is = beta_ <= 0;
 	for (long j = 0; j < count; ++j)
 		for (long i = 0; i < rows; ++i) {
 			const T v = values[(size_t)j * ld + i];
 			if (!std::isfinite(v) || v < T(0) || (is && v == T(0))) {
-				last_error_ = is ? "Itakura-Saito divergence: every entry of V has to be finite and > 0" : "dense KL divergence: every entry of V has to be finite and >= 0";
+				last_error_ = beta_ == 0   ? "Itakura-Saito divergence: every entry of V has to be finite and > 0"
+				              : beta_ == 1 ? "dense KL divergence: every entry of V has to be finite and >= 0"
+				              : is         ? "beta-divergence with beta <= 0: every entry of V has to be finite and > 0"
+				                           : "beta-divergence with beta > 0: every entry of V has to be finite and >= 0";
 				return ST_INVALID;
 			}
 		}
@@ -635,9 +643,13 @@ template <typename T>
 Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const int* b, long nnz, int base) {
 	if (format < 1 || format > 3 || nnz < 0 || (nnz > 0 && (!values || !a || !b))) return ST_INVALID;
 	if (beta_dense_) {
-		// the stored entries are densified (launch_densify below); an unstored entry is a zero, which the Itakura-Saito divergence does not take
+		// the stored entries are densified (launch_densify below); an unstored entry is a zero, which a divergence with beta <= 0 (Itakura-Saito) does not take
 		beta_uploaded_ = false;
-		if (prm_.beta() == 0) { last_error_ = "Itakura-Saito divergence: sparse input is refused (unstored entries are zeros); upload V dense"; return ST_INVALID; }
+		if (beta_ <= 0) {
+			last_error_ = beta_ == 0 ? "Itakura-Saito divergence: sparse input is refused (unstored entries are zeros); upload V dense"
+			                         : "beta-divergence with beta <= 0: sparse input is refused (unstored entries are zeros); upload V dense";
+			return ST_INVALID;
+		}
 		if (nnz > 0) { if (Status st = beta_check_values(values, 1, nnz, nnz)) return st; }
 	}
 	if (sparse_ && prm_.is_masked()) {
@@ -2033,7 +2045,8 @@ Status Engine<T>::begin_next_iteration() {
 
 template <typename T>
 Status Engine<T>::set_hals_penalties(double l1W, double l1H, double l2W, double l2H) {
-	if (const char* why = hals_penalties_fault(l1W, l1H, l2W, l2H, sizeof(T) == 4, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
+	// (prm_, not beta_dense_: allocate() calls this before it has looked at the divergence)
+	if (const char* why = hals_penalties_fault(l1W, l1H, l2W, l2H, sizeof(T) == 4, prm_.takes_penalties(alg_ == ALG_HALS))) { last_error_ = why; return ST_INVALID; }
 	// kept rounded to T, as the sweeps take them: a value that rounds to 0 in the engine's precision is 0 for the normalisation switch too, and the
 	// (T) casts where the sweeps are launched change nothing any more
 	prm_.l1W = (double)(T)l1W; prm_.l1H = (double)(T)l1H; prm_.l2W = (double)(T)l2W; prm_.l2H = (double)(T)l2H;
@@ -2428,27 +2441,32 @@ Status Engine<T>::iterate_masked(bool compute_error, bool constant_w) {
 	return ST_OK;
 }
 
-// Dense beta-divergence update (docs/DIVERGENCE.md): generalised KL (beta = 1) or Itakura-Saito (beta = 0) on the dense images, one fused launch and one update
-// launch per half-step (kernels_beta.hip), in the skeleton of the other multiplicative iterations -- H step, W step with the new H, normalisation, error of the
-// pair (W_{k-1}, H_k) from the W launch's own evaluation of P:
+// Dense beta-divergence update (docs/DIVERGENCE.md): generalised KL (beta = 1), Itakura-Saito (beta = 0) or any other beta on the dense images, one fused launch and
+// one update launch per half-step (kernels_beta.hip), in the skeleton of the other multiplicative iterations -- H step, W step with the new H, normalisation, error of
+// the pair (W_{k-1}, H_k) from the W launch's own evaluation of P:
 //   beta = 1:  H .*= (W^T (V ./ P)) ./ (colsum(W) + eps);  W .*= ((V ./ P) H^T) ./ (rowsum(H) + eps);  normalise the columns of W (H is not rescaled): iterate_kl's iteration
 //   beta = 0:  H .*= sqrt((W^T (V ./ P^2)) ./ (W^T (1 ./ P) + eps));  W likewise;  W(:, k) /= d_k, H(k, :) *= d_k with d_k = ||W(:, k)|| (W H unchanged)
+//   general:   H .*= ((W^T (V .* P^(beta - 2))) ./ (W^T P^(beta - 1) + eps))^gamma;  W likewise;  the compensated normalisation of beta = 0
+// With a penalty (set_hals_penalties) the denominators carry + l1 + l2 A (l1H, l2H in the H step, l1W, l2W in the W step) and there is no normalisation, HALS's rule:
+// W D^-1 . D H keeps W H but not the penalty terms.  The KL denominators sW_ / sH_ are then the column sums of the panels as they are.
 // Under constant W the H step runs alone; an error iteration then takes its terms from the terms-only form of the W-side launch.
 template <typename T>
 Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
 	if (!beta_uploaded_) { last_error_ = "dense divergence update: no V has been uploaded"; return ST_INVALID; }
 	const T eps = std::numeric_limits<T>::epsilon();
-	const int beta = prm_.beta();
+	const double beta = beta_;
+	const bool kl = beta == 1, penalised = prm_.hals_penalised();
+	const T l1W = (T)prm_.l1W, l1H = (T)prm_.l1H, l2W = (T)prm_.l2W, l2H = (T)prm_.l2H;
 	const int partsH = (int)(npad_ / 128), partsW = (int)(mpad_ / 128);
 	// H step: X = the column-major image (row j of X = column j of V)
-	if (beta == 1 && !kl_sw_ready_) { HIPX(launch_panel_rowsum<T>(Wt_, RP_, (int)mpad_, rowsum_part_, sW_, stream_)); kl_sw_ready_ = true; }
+	if (kl && !kl_sw_ready_) { HIPX(launch_panel_rowsum<T>(Wt_, RP_, (int)mpad_, rowsum_part_, sW_, stream_)); kl_sw_ready_ = true; }
 	record_begin();
 	HIPX(launch_beta_fused<T>(V_, mpad_, H_, Wt_, RP_, beta, true, false, eps, betaH_, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0,
 	                          (int)npad_, n_, m_, stream_));
 	record_end();
-	HIPX(launch_beta_update<T>(H_, slabs_, beta_den_, slab_stride_, betaH_.slabs, sW_, RP_, r_, (int)npad_, n_, eps, beta, true, (T*)nullptr,
-	                           beta == 1 ? rowsum_part_ : (T*)nullptr, (const T*)nullptr, (const T*)nullptr, 0, (T*)nullptr, (T*)nullptr, stream_));
-	if (beta == 1) HIPX(launch_kl_sums<T>(rowsum_part_, nullptr, partsH, RP_, sH_, stream_));
+	HIPX(launch_beta_update<T>(H_, slabs_, beta_den_, slab_stride_, betaH_.slabs, sW_, RP_, r_, (int)npad_, n_, eps, beta, l1H, l2H, true, (T*)nullptr,
+	                           kl ? rowsum_part_ : (T*)nullptr, (const T*)nullptr, (const T*)nullptr, 0, (T*)nullptr, (T*)nullptr, stream_));
+	if (kl) HIPX(launch_kl_sums<T>(rowsum_part_, nullptr, partsH, RP_, sH_, stream_));
 	if (constant_w && !compute_error) return ST_OK;
 	// W step (or, under constant W, its terms-only form): X = the transposed image
 	T* tf = compute_error ? beta_tpart_ : (T*)nullptr;
@@ -2457,8 +2475,8 @@ Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
 	HIPX(launch_beta_fused<T>(Vt_, npad_, Wt_, H_, RP_, beta, !constant_w, compute_error, eps, betaW_, slabs_, beta_den_, slab_stride_, tf, td, mpad_,
 	                          (int)mpad_, m_, n_, stream_));
 	record_end();
-	HIPX(launch_beta_update<T>(Wt_, slabs_, beta_den_, slab_stride_, betaW_.slabs, sH_, RP_, r_, (int)mpad_, m_, eps, beta, !constant_w, sumsq_part_,
-	                           beta == 1 ? rowsum_part_ : (T*)nullptr, tf, td, mpad_, compute_error ? t_vwh_ : (T*)nullptr, compute_error ? t_kl_ : (T*)nullptr, stream_));
+	HIPX(launch_beta_update<T>(Wt_, slabs_, beta_den_, slab_stride_, betaW_.slabs, sH_, RP_, r_, (int)mpad_, m_, eps, beta, l1W, l2W, !constant_w, sumsq_part_,
+	                           kl ? rowsum_part_ : (T*)nullptr, tf, td, mpad_, compute_error ? t_vwh_ : (T*)nullptr, compute_error ? t_kl_ : (T*)nullptr, stream_));
 	if (compute_error) {
 		finalize_error(false);      // (the pinned buffer is about to be reused; an older copy is long complete)
 		HIPX(hipMemcpyAsync(pin_kl_, t_vwh_, sizeof(T) * m_, hipMemcpyDeviceToHost, stream_));
@@ -2467,12 +2485,12 @@ Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
 		beta_pending_ = true;
 	}
 	if (constant_w) return ST_OK;
-	if (beta == 1) {
-		// as iterate_kl: the column sums of the NORMALISED W from the update's partials, then the normalisation itself
-		HIPX(launch_kl_sums<T>(rowsum_part_, sumsq_part_, partsW, RP_, sW_, stream_));
+	if (kl) {
+		// as iterate_kl: the column sums of the NORMALISED W from the update's partials, then the normalisation itself; penalised: the sums of W as it is
+		HIPX(launch_kl_sums<T>(rowsum_part_, penalised ? (const T*)nullptr : sumsq_part_, partsW, RP_, sW_, stream_));
 		kl_sw_ready_ = true;
-		HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, partsW, stream_));
-	} else {
+		if (!penalised) HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, partsW, stream_));
+	} else if (!penalised) {
 		HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, partsW, stream_));
 	}
 	return ST_OK;

@@ -21,24 +21,28 @@ enum Algorithm { ALG_MU = 0, ALG_GDCLS = 1, ALG_ALS = 2, ALG_ACLS = 3, ALG_AHCLS
 struct AlgorithmParams {
 	double lambda = 0, lambdaW = 0, lambdaH = 0, alphaW = 0, alphaH = 0, theta = 0;
 	// extensions without a reference counterpart (selected by new Parameter names, see abi.cpp):
-	double divergence = 0;      // 0: Frobenius objective, 1: generalised KL divergence, 2: Itakura-Saito divergence (multiplicative update only; 2 is always the dense path)
+	double divergence = 0;      // 0: Frobenius objective, 1: generalised KL divergence, 2: Itakura-Saito divergence, 3: the beta-divergence at beta_value (multiplicative
+	                            // update only; 2 and 3 are always the dense path)
 	double sparse_compute = 0;  // 1: keep V as CSR + CSC in HBM and multiply by SpMM instead of densifying
 	double precision = 0;       // 1: bf16 MFMA operands (V, W, H rounded to bf16 inside the two big products), fp32 everywhere else
 	double missing_values = 0;  // 1: fit the stored entries only (multiplicative update; implies sparse compute, kernels_masked.hip, docs/MISSING.md)
-	// HALS only (docs/HALS.md): L1 / L2 penalties on W and on H, scikit-learn's coordinate descent; all 0: the unpenalised iteration.  Engine::set_hals_penalties
-	// changes them between iterations.
+	// L1 / L2 penalties on W and on H; all 0: the unpenalised iteration.  HALS (docs/HALS.md: scikit-learn's coordinate descent) and the dense divergence updates
+	// (docs/DIVERGENCE.md: scikit-learn's solver="mu") take them, no other engine.  Engine::set_hals_penalties changes them between iterations.
 	double l1W = 0, l1H = 0, l2W = 0, l2H = 0;
 	double dense_compute = 0;   // 1 with divergence = 1: the KL update on a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) instead of over the stored entries
+	double beta_value = 0;      // divergence = 3: the beta of the divergence, any finite value (0 and 1 run the Itakura-Saito and dense KL engines as they are)
 	bool is_masked() const { return missing_values != 0; }
-	// the dense beta-divergence update: Itakura-Saito (beta = 0) always, generalised KL (beta = 1) with dense_compute
-	bool is_beta_dense() const { return divergence == 2 || (divergence == 1 && dense_compute != 0); }
-	int beta() const { return divergence == 2 ? 0 : 1; }
+	// the dense beta-divergence update: Itakura-Saito (beta = 0) and the general form always, generalised KL (beta = 1) with dense_compute
+	bool is_beta_dense() const { return divergence == 2 || divergence == 3 || (divergence == 1 && dense_compute != 0); }
+	double beta() const { return divergence == 2 ? 0.0 : divergence == 3 ? beta_value : 1.0; }
+	bool takes_penalties(bool is_hals) const { return is_hals || is_beta_dense(); }
 	bool hals_penalised() const { return l1W != 0 || l1H != 0 || l2W != 0 || l2H != 0; }
 };
 
-// What a set of HALS penalties (l1W, l1H, l2W, l2H) must satisfy, stated once for Engine::set_hals_penalties and nmfgpu::compute: nullptr, or why not.
-// fp32: the sweeps of a float engine take the values as float, where a large double is not finite.
-inline const char* hals_penalties_fault(double l1W, double l1H, double l2W, double l2H, bool fp32, bool is_hals) {
+// What a set of penalties (l1W, l1H, l2W, l2H) must satisfy, stated once for Engine::set_hals_penalties and nmfgpu::compute: nullptr, or why not.
+// fp32: the kernels of a float engine take the values as float, where a large double is not finite.  takes_penalties: a HALS engine or a dense divergence engine
+// (AlgorithmParams::takes_penalties).
+inline const char* hals_penalties_fault(double l1W, double l1H, double l2W, double l2H, bool fp32, bool takes_penalties) {
 	const double v[4] = {l1W, l1H, l2W, l2H};
 	bool any = false;
 	for (double x : v) {
@@ -46,7 +50,7 @@ inline const char* hals_penalties_fault(double l1W, double l1H, double l2W, doub
 		if (fp32 && x > 3.4028234663852886e38) return "HALS penalties: value out of the range of the engine's precision";
 		any = any || x != 0;
 	}
-	if (any && !is_hals) return "HALS penalties: only the HALS algorithm takes l1W / l1H / l2W / l2H";
+	if (any && !takes_penalties) return "HALS penalties: only the HALS algorithm takes l1W / l1H / l2W / l2H";
 	return nullptr;
 }
 
@@ -54,9 +58,11 @@ inline const char* hals_penalties_fault(double l1W, double l1H, double l2W, doub
 inline const char* beta_dense_fault(const AlgorithmParams& p, bool is_mu, int r, int row_blocks = 1) {
 	if (!(p.dense_compute == 0 || p.dense_compute == 1)) return "dense divergence update: 'denseCompute' has to be 0 or 1";
 	if (p.dense_compute != 0 && p.divergence == 0) return "dense divergence update: 'denseCompute' selects the dense form of a divergence ('divergence' = 1 or 2), not the Frobenius objective";
+	if (!(p.beta_value - p.beta_value == 0)) return "dense divergence update: 'beta' has to be finite";
+	if (p.beta_value != 0 && p.divergence != 3) return "dense divergence update: 'beta' needs 'divergence' = 3 (the general beta-divergence)";
 	if (!p.is_beta_dense()) return nullptr;
 	if (!is_mu) return "dense divergence update: the Multiplicative algorithm only";
-	if (p.sparse_compute != 0 || p.missing_values != 0) return "dense divergence update: does not combine with 'sparseCompute' or 'missingValues' (V is kept dense; Itakura-Saito is undefined at 0)";
+	if (p.sparse_compute != 0 || p.missing_values != 0) return "dense divergence update: does not combine with 'sparseCompute' or 'missingValues' (V is kept dense; a divergence with beta <= 0 is undefined at 0)";
 	if (p.precision > 0) return "dense divergence update: no bf16 operands";
 	if (r > 256) return "dense divergence update: rank <= 256";
 	if (row_blocks > 1) return "dense divergence update: single GPU only (no row blocks)";
@@ -144,6 +150,7 @@ public:
 	Status w_normalize_rows(long row0, long rows, T* colsq);
 	void w_rows_replaced() { kl_sw_ready_ = false; kl_scale_pending_ = false; fused_ready_ = false; w_pending_ = false; f32w_pending_ = false; f64_pending_ = false; f64_product_ahead_ = false; h_product_ahead_ = false; gram_w_ready_ = false; wx3_valid_ = false; tri_gw_ready_ = false; qx3_holds_g_ = false; tri_scale_pending_ = false; tri_scale_from_gram_ = false; if (!tri_rows_cover_) wtb_valid_ = false; }
 	T* w_panel() { return Wt_; }
+	double beta() const { return beta_; }      // the beta of a dense divergence engine, in the precision of T
 	int kl_blocks(bool w_step) const { return prm_.divergence != 0 && !beta_dense_ ? (w_step ? kl_blocks_w_ : kl_blocks_h_) : 0; }
 	int gram_k_slices() const { return gram_spread_ ? GRAM_REDUCE_BLOCKS : gram_ksplit_; }      // (16: the spread form)
 	bool w_col_split() const { return w_col_split_; }
@@ -181,7 +188,7 @@ public:
 	// asynchronously; the first reader waits for them and does the sorted summation, so a caller
 	// that does not look at the error every time (the benchmark loop) never stalls the stream.
 	double kl_divergence() { finalize_error(true); return kl_; }
-	double divergence_value() { finalize_error(true); return kl_; }      // the objective of whichever divergence the engine has (KL or Itakura-Saito)
+	double divergence_value() { finalize_error(true); return kl_; }      // the objective of whichever divergence the engine has (KL, Itakura-Saito or general beta; no penalty terms)
 	bool sparse_mode() const { return sparse_; }
 	bool sparse_setup_on_device() const { return sparse_setup_on_device_; }
 	long nnz() const { return nnz_; }
@@ -250,7 +257,7 @@ private:
 	Status masked_refuses(const char* what);          // ST_INVALID with last_error_ set: no three-phase / sharded form of the masked update
 	Status iterate_beta(bool compute_error, bool constant_w);     // dense beta-divergence multiplicative update (kernels_beta.hip, docs/DIVERGENCE.md)
 	Status beta_refuses(const char* what);            // ... nor of the dense beta-divergence update
-	Status beta_check_values(const T* values, long count, long ld, long rows);   // upload: beta = 0 needs finite values > 0, beta = 1 finite values >= 0
+	Status beta_check_values(const T* values, long count, long ld, long rows);   // upload: beta <= 0 needs finite values > 0, beta > 0 finite values >= 0
 	Status fetch_error_terms(int count_n);            // enqueue the copies, do not wait
 	void finalize_error(bool resolve);
 	void record_begin(int kind = 0);
@@ -322,6 +329,7 @@ private:
 	// dense beta-divergence update: V_ is the column-major image (the H step's), Vt_ its transpose (the W step's); slabs_ holds the slabs' partial numerators,
 	// beta_den_ their partial denominators (beta = 0), beta_tpart_ the slabs' parts of the two per-row error terms ([2][BETA_MAX_SLABS][mpad])
 	bool beta_dense_ = false, beta_uploaded_ = false;
+	double beta_ = 1;      // prm_.beta() rounded to T: what the launches take and what selects the engine (0: Itakura-Saito, 1: dense KL, else the general form)
 	BetaPlan betaH_, betaW_;
 	T *beta_den_ = nullptr, *beta_tpart_ = nullptr;
 	bool beta_pending_ = false, beta_unresolved_ = false;

@@ -520,7 +520,8 @@ template <typename T>
 hipError_t launch_masked_half_step(const int* ptr, const int* idx, const T* val, T* A, const T* B, int RP, T eps, bool update,
                                    T* t_res, T* sumsq_part, int rows, hipStream_t stream);
 
-// ---- dense beta-divergence NMF: generalised KL (beta = 1) and Itakura-Saito (beta = 0) on a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) ----------------
+// ---- dense beta-divergence NMF: generalised KL (beta = 1), Itakura-Saito (beta = 0) and the general form (any other finite beta), with optional L1 / L2 penalties, on
+// ---- a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) ---------------------------------------------------------------------------------------------------
 // How one half-step is cut: workgroups of `bo` output columns, reduction tiles of `kt` rows, `slabs` slices of the reduction range (tiles_per_slab tiles each, the last
 // one maybe fewer) that write one partial panel each.  A function of the shape, the element size and the CU count only: it fixes the order of the sums.
 constexpr int BETA_MAX_SLABS = 16;
@@ -528,20 +529,21 @@ struct BetaPlan { int bo = 0, kt = 0, slabs = 0, tiles = 0, tiles_per_slab = 0; 
 bool beta_half_step_available(int RP);      // padded ranks 64, 128, 256
 BetaPlan plan_beta_half_step(long out_pad, long red_pad, int RP, size_t elem_bytes, int num_cus, int force_slabs = 0);
 // The fused launch: A [out_pad][RP] (read only), B [red_pad][RP], X [out_pad][ldx] with X(o, k) the entry of V at output index o and reduction index k (zero on the
-// padding), red_pad = plan.tiles * plan.kt <= ldx.  update: the slabs' partial numerators num_part (and, beta = 0, denominators den_part) at part_stride elements;
+// padding), red_pad = plan.tiles * plan.kt <= ldx.  beta: any finite value, taken in the precision of T; 1 and 0 run their own element-wise maps, every other value the
+// general one (P^(beta - 2) as exp2((beta - 2) log2 P)).  update: the slabs' partial numerators num_part (and, beta != 1, denominators den_part) at part_stride elements;
 // terms: the slabs' parts of the per-output-row error terms sum_k (x - p)^2 (tf_part) and of the divergence (td_part) at t_stride elements.  Entries with o >= out_valid
 // or k >= red_valid add nothing to any sum.
 template <typename T>
-hipError_t launch_beta_fused(const T* X, long ldx, const T* A, const T* B, int RP, int beta, bool update, bool terms, T eps, const BetaPlan& plan,
+hipError_t launch_beta_fused(const T* X, long ldx, const T* A, const T* B, int RP, double beta, bool update, bool terms, T eps, const BetaPlan& plan,
                              T* num_part, T* den_part, long part_stride, T* tf_part, T* td_part, long t_stride,
                              int out_pad, int out_valid, int red_valid, hipStream_t stream);
-// The slabs in order, then A(o, c) <- A(o, c) (num / (den + eps))^gamma for o < out_valid, c < r and 0 elsewhere (beta = 1: den = dsum(c), gamma = 1; beta = 0: den from
-// den_part, gamma = 1/2); sumsq_part / sum_part (optional): [out_pad / 128][RP] sums of squares / sums of the new values; t_frob / t_div (optional, both or none):
+// The slabs in order, then A(o, c) <- A(o, c) (num / (den + eps + l1 + l2 A(o, c)))^gamma for o < out_valid, c < r and 0 elsewhere (beta = 1: den = dsum(c); otherwise
+// den from den_part; gamma = 1 / (2 - beta) below beta = 1, 1 up to beta = 2, 1 / (beta - 1) above; l1, l2 >= 0, both 0: the unpenalised quotient); sumsq_part / sum_part (optional): [out_pad / 128][RP] sums of squares / sums of the new values; t_frob / t_div (optional, both or none):
 // the error terms of out_pad rows, slabs in order.  update = false: the terms only, A untouched.
 template <typename T>
 hipError_t launch_beta_update(T* A, const T* num_part, const T* den_part, long part_stride, int slabs, const T* dsum, int RP, int r, int out_pad, int out_valid, T eps,
-                              int beta, bool update, T* sumsq_part, T* sum_part, const T* tf_part, const T* td_part, long t_stride, T* t_frob, T* t_div,
-                              hipStream_t stream);
+                              double beta, T l1, T l2, bool update, T* sumsq_part, T* sum_part, const T* tf_part, const T* td_part, long t_stride, T* t_frob,
+                              T* t_div, hipStream_t stream);
 
 // ---- the CSR and CSC images of a sparse V built on the device (kernels_sparse_setup.hip) ----------------------------------------
 // flags (one int, zeroed by the caller): bit 0 = an entry outside the matrix or outside every pointer range, bit 1 = pointer array not ascending, bit 2 = the

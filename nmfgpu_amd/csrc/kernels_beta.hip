@@ -1,12 +1,14 @@
-// kernels_beta.hip -- dense beta-divergence NMF: the multiplicative update at beta = 1 (generalised KL) and beta = 0 (Itakura-Saito) on a dense resident V
-// (docs/DIVERGENCE.md).
+// kernels_beta.hip -- dense beta-divergence NMF: the multiplicative update at beta = 1 (generalised KL), beta = 0 (Itakura-Saito) and any other real beta (the
+// general form), with optional L1 / L2 penalties, on a dense resident V (docs/DIVERGENCE.md).
 //
 // One half-step, written once for both sides.  A is the panel that is updated ([out_pad][RP]: H in the H step, Wt in the W step), B the other panel
 // ([red_pad][RP]), X the image of V with the output index as its row ([out_pad][ldx]: the column-major V in the H step, its transpose in the W step):
 //     P(k, o) = sum_c B(k, c) A(o, c) + eps
 //     beta = 1:  Q = X ./ P                      num(o, c) = sum_k Q(k, o) B(k, c)                                   den(c) = sum_k B(k, c)  (a vector: the caller's)
 //     beta = 0:  Q = X ./ P^2,  R = 1 ./ P       num(o, c) = sum_k Q(k, o) B(k, c),  den(o, c) = sum_k R(k, o) B(k, c)
-//     A(o, c) <- A(o, c) (num / (den + eps))^gamma,   gamma = 1 (beta = 1) or 1/2 (beta = 0)
+//     general:   Q = X .* P^(beta - 2),  R = P^(beta - 1)   the same two products as beta = 0
+//     A(o, c) <- A(o, c) (num / (den + eps + l1 + l2 A(o, c)))^gamma,   gamma = 1 / (2 - beta) below beta = 1, 1 up to beta = 2, 1 / (beta - 1) above
+// The template parameter BETA names the element-wise map: 1, 0, or BETA_GENERAL with beta a kernel argument.
 // k_beta_fused_* forms P tile by tile, applies the element-wise map with the V tile in registers and accumulates num (and den): P, Q and R never reach HBM and V is
 // read once.  The reduction index is cut into slabs (blockIdx.y) so that a launch has a few hundred workgroups whatever the shape; every slab writes its own partial
 // panels and k_beta_update adds them in slab order, applies the update, zeroes the padding and leaves the per-workgroup sums the normalisation and the other
@@ -20,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "kernels.h"
 #include "split3.h"
@@ -28,9 +31,18 @@ namespace nmfamd {
 
 typedef float beta_f32x16 __attribute__((ext_vector_type(16)));
 
+constexpr int BETA_GENERAL = 2;      // (the value of the BETA template parameter that takes beta at run time)
+
+// p^y = exp2(y log2 p) for p > 0.  fp32: the hardware's log2 and exp2 (v_log_f32, v_exp_f32; P >= eps and V is not denormal where it matters, so their flush of
+// denormals costs nothing) -- the relative error is about |y log2 p| 2^-24, which on factors of ordinary size is a few ulp (docs/DIVERGENCE.md)
+__device__ inline float beta_log2(float p) { return __builtin_amdgcn_logf(p); }
+__device__ inline double beta_log2(double p) { return log2(p); }
+__device__ inline float beta_exp2(float y) { return __builtin_amdgcn_exp2f(y); }
+__device__ inline double beta_exp2(double y) { return exp2(y); }
+
 // the element-wise map and the error terms of one entry (x = v, p = (W H) + eps); padding entries (valid = false) give zeros and no terms
 template <typename T, int BETA, bool TERMS>
-__device__ inline void beta_entry(T x, T p, bool valid, T& q, T& rr, T& tf, T& td) {
+__device__ inline void beta_entry(T x, T p, bool valid, T be, T& q, T& rr, T& tf, T& td) {
 	q = 0; rr = 0;
 	if (!valid) return;
 	if (BETA == 1) {
@@ -39,6 +51,17 @@ __device__ inline void beta_entry(T x, T p, bool valid, T& q, T& rr, T& tf, T& t
 			const T d = x - p;
 			tf += d * d;
 			td += (x > T(0) ? x * log(q) : T(0)) - x + p;
+		}
+	} else if (BETA == BETA_GENERAL) {
+		// t = p^(beta - 2); the divergence term (x^beta + (beta - 1) p^beta - beta x p^(beta - 1)) is left unscaled: the kernel divides the row sums by beta (beta - 1)
+		const T t = beta_exp2((be - T(2)) * beta_log2(p));
+		q = x * t;
+		rr = t * p;
+		if (TERMS) {
+			const T d = x - p;
+			tf += d * d;
+			const T xb = x > T(0) ? beta_exp2(be * beta_log2(x)) : T(0);
+			td += xb + (be - T(1)) * (rr * p) - be * (x * rr);
 		}
 	} else {
 		const T ip = T(1) / p;
@@ -54,7 +77,7 @@ __device__ inline void beta_entry(T x, T p, bool valid, T& q, T& rr, T& tf, T& t
 
 // WO x WK waves: WO tiles of 32 output columns, WK tiles of 32 reduction rows per step (WO * WK = 4)
 template <int RP, int BETA, bool UPDATE, bool TERMS, int WO, int WK>
-__global__ __launch_bounds__(256) void k_beta_fused_f32(const float* __restrict__ X, long ldx, const float* __restrict__ A, const float* __restrict__ B, float eps,
+__global__ __launch_bounds__(256) void k_beta_fused_f32(const float* __restrict__ X, long ldx, const float* __restrict__ A, const float* __restrict__ B, float eps, float bexp,
                                                         float* __restrict__ num_part, float* __restrict__ den_part, long part_stride,
                                                         float* __restrict__ tf_part, float* __restrict__ td_part, long t_stride,
                                                         int out_valid, int red_valid, int tiles_total, int tiles_per_slab) {
@@ -71,6 +94,7 @@ __global__ __launch_bounds__(256) void k_beta_fused_f32(const float* __restrict_
 	const int tile_begin = slab * tiles_per_slab, tile_end = min(tile_begin + tiles_per_slab, tiles_total);
 	const int o = o0 + 32 * wo + li;
 	const float e_v = in_vgpr(eps);     // (a uniform argument meets vector values below: split3.h)
+	const float b_v = BETA == BETA_GENERAL ? in_vgpr(bexp) : 0.f;
 
 	for (int idx = threadIdx.x * 4; idx < BO * RP; idx += 1024) {
 		const int row = idx / RP, col = idx % RP;
@@ -120,7 +144,7 @@ __global__ __launch_bounds__(256) void k_beta_fused_f32(const float* __restrict_
 #pragma unroll
 		for (int v = 0; v < 16; ++v) {
 			const int kk = kt + 32 * wk + (v & 3) + 8 * (v >> 2) + 4 * h;
-			beta_entry<float, BETA, TERMS>(x[v], P[v] + e_v, kk < red_valid && o < out_valid, q[v], rr[v], tf, td);
+			beta_entry<float, BETA, TERMS>(x[v], P[v] + e_v, kk < red_valid && o < out_valid, b_v, q[v], rr[v], tf, td);
 		}
 		if (UPDATE) {
 			const float* b2 = Bs + (32 * wk + 4 * h) * LD + li;
@@ -130,7 +154,7 @@ __global__ __launch_bounds__(256) void k_beta_fused_f32(const float* __restrict_
 				for (int ct = 0; ct < NC; ++ct) {
 					const float bop = b2[((v & 3) + 8 * (v >> 2)) * LD + 32 * ct];
 					num[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(q[v], bop, num[ct], 0, 0, 0);
-					if (BETA == 0) den[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(rr[v], bop, den[ct], 0, 0, 0);
+					if (BETA != 1) den[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(rr[v], bop, den[ct], 0, 0, 0);
 				}
 			}
 		}
@@ -140,7 +164,7 @@ __global__ __launch_bounds__(256) void k_beta_fused_f32(const float* __restrict_
 		// the WK waves of an output tile in wave order, through the region of the B tile; then the slab's partial panel rows, coalesced
 		float* R = Bs;
 #pragma unroll
-		for (int pass = 0; pass < (BETA == 0 ? 2 : 1); ++pass) {
+		for (int pass = 0; pass < (BETA != 1 ? 2 : 1); ++pass) {
 			for (int w = 0; w < WK; ++w) {
 				if (wk == w) {
 #pragma unroll
@@ -160,6 +184,7 @@ __global__ __launch_bounds__(256) void k_beta_fused_f32(const float* __restrict_
 		}
 	}
 	if (TERMS) {
+		if (BETA == BETA_GENERAL) td *= 1.f / (b_v * (b_v - 1.f));
 		// lane halves (h = 0 then 1), then the WK waves in order
 		const float of = __shfl_xor(tf, 32), od = __shfl_xor(td, 32);
 		const float sf = h == 0 ? tf + of : of + tf, sd = h == 0 ? td + od : od + td;
@@ -178,7 +203,7 @@ __global__ __launch_bounds__(256) void k_beta_fused_f32(const float* __restrict_
 // The same half-step with plain FMAs (fp64: the parity form).  A workgroup owns 8 output columns and walks tiles of 32 reduction rows: thread (k, o) forms
 // P(k, o) and the map, thread (o, c mod 32) then accumulates its RP / 32 numerators (and denominators) over the tile's rows in ascending k.
 template <typename T, int RP, int BETA, bool UPDATE, bool TERMS>
-__global__ __launch_bounds__(256) void k_beta_fused_valu(const T* __restrict__ X, long ldx, const T* __restrict__ A, const T* __restrict__ B, T eps,
+__global__ __launch_bounds__(256) void k_beta_fused_valu(const T* __restrict__ X, long ldx, const T* __restrict__ A, const T* __restrict__ B, T eps, T bexp,
                                                          T* __restrict__ num_part, T* __restrict__ den_part, long part_stride,
                                                          T* __restrict__ tf_part, T* __restrict__ td_part, long t_stride,
                                                          int out_valid, int red_valid, int tiles_total, int tiles_per_slab) {
@@ -192,6 +217,7 @@ __global__ __launch_bounds__(256) void k_beta_fused_valu(const T* __restrict__ X
 	const int tile_begin = slab * tiles_per_slab, tile_end = min(tile_begin + tiles_per_slab, tiles_total);
 	const int k1 = threadIdx.x & 31, o1 = threadIdx.x >> 5;      // both phases: o1 = the thread's output column
 	const T e_v = in_vgpr(eps);
+	const T b_v = BETA == BETA_GENERAL ? in_vgpr(bexp) : T(0);
 	for (int idx = threadIdx.x; idx < BO * RP; idx += 256) As[(idx / RP) * LD + idx % RP] = A[(long)o0 * RP + idx];
 	T num[NACC], den[NACC];
 #pragma unroll
@@ -209,7 +235,7 @@ __global__ __launch_bounds__(256) void k_beta_fused_valu(const T* __restrict__ X
 			const T* as = As + o1 * LD;
 			for (int c = 0; c < RP; ++c) p += bs[c] * as[c];
 			T q, rr;
-			beta_entry<T, BETA, TERMS>(x, p + e_v, kt + k1 < red_valid && o0 + o1 < out_valid, q, rr, tf, td);
+			beta_entry<T, BETA, TERMS>(x, p + e_v, kt + k1 < red_valid && o0 + o1 < out_valid, b_v, q, rr, tf, td);
 			Qs[k1 * BO + o1] = q;
 			Rs[k1 * BO + o1] = rr;
 		}
@@ -221,7 +247,7 @@ __global__ __launch_bounds__(256) void k_beta_fused_valu(const T* __restrict__ X
 				for (int u = 0; u < NACC; ++u) {
 					const T b = Bs[k * LD + k1 + 32 * u];
 					num[u] += q * b;
-					if (BETA == 0) den[u] += rr * b;
+					if (BETA != 1) den[u] += rr * b;
 				}
 			}
 		}
@@ -231,14 +257,14 @@ __global__ __launch_bounds__(256) void k_beta_fused_valu(const T* __restrict__ X
 		for (int u = 0; u < NACC; ++u) {
 			const long at = (long)slab * part_stride + (long)(o0 + o1) * RP + k1 + 32 * u;
 			num_part[at] = num[u];
-			if (BETA == 0) den_part[at] = den[u];
+			if (BETA != 1) den_part[at] = den[u];
 		}
 	}
 	if (TERMS) {
 		// a column's 32 row residues in ascending order
 		__syncthreads();
 		Qs[k1 * BO + o1] = tf;
-		Rs[k1 * BO + o1] = td;
+		Rs[k1 * BO + o1] = BETA == BETA_GENERAL ? td / (b_v * (b_v - T(1))) : td;
 		__syncthreads();
 		if ((int)threadIdx.x < BO) {
 			T a = 0, b = 0;
@@ -249,32 +275,45 @@ __global__ __launch_bounds__(256) void k_beta_fused_valu(const T* __restrict__ X
 	}
 }
 
-// The slabs in order, then A(o, c) <- A(o, c) (num / (den + eps))^gamma on the valid coordinates and 0 on the padding; one workgroup per 128 panel rows, which
-// leaves its sums of squares and sums of the new values (sumsq_part, sum_part: [out_pad / 128][RP]) and, on error iterations, the rows' error terms.
-template <typename T>
+// The slabs in order, then A(o, c) <- A(o, c) (num / (den + eps + l1 + l2 A(o, c)))^gamma on the valid coordinates and 0 on the padding; one workgroup per 128
+// panel rows, which leaves its sums of squares and sums of the new values (sumsq_part, sum_part: [out_pad / 128][RP]) and, on error iterations, the rows' error terms.
+// vec_den: the denominator is the vector dsum (beta = 1), else the slabs' den_part.  power: 0 gamma = 1, 1 gamma = 1/2 (a square root), 2 any other gamma (a zero
+// quotient stays 0).  EXT = false is the launch beta = 0 and beta = 1 always had (no penalty, power 0 or 1: the same instructions, so the same bits and the same
+// time); EXT = true carries the penalties and the general power, whose code would otherwise sit in that launch's row loop.
+template <typename T, bool EXT>
 __global__ __launch_bounds__(256) void k_beta_update(T* __restrict__ A, const T* __restrict__ num_part, const T* __restrict__ den_part, long part_stride, int slabs,
-                                                     const T* __restrict__ dsum, int RP, int r, int out_valid, T eps, int beta, int update,
-                                                     T* __restrict__ sumsq_part, T* __restrict__ sum_part,
+                                                     const T* __restrict__ dsum, int RP, int r, int out_valid, T eps, int vec_den, int power, T gamma,
+                                                     int penalised, T l1, T l2, int update, T* __restrict__ sumsq_part, T* __restrict__ sum_part,
                                                      const T* __restrict__ tf_part, const T* __restrict__ td_part, long t_stride, T* __restrict__ t_frob, T* __restrict__ t_div) {
 	__shared__ T s_sq[256], s_sm[256];
 	const int G = 256 / RP, c = threadIdx.x % RP, g = threadIdx.x / RP;
 	const int row0 = blockIdx.x * 128;
 	const T e_v = in_vgpr(eps);
+	const T g_v = EXT ? in_vgpr(gamma) : T(0), l1_v = EXT ? in_vgpr(l1) : T(0), l2_v = EXT ? in_vgpr(l2) : T(0);
 	if (update) {
 		T sq = 0, sm = 0;
-		const T dvec = beta == 1 ? dsum[c] : T(0);
+		const T dvec = vec_den ? dsum[c] : T(0);
 		for (int row = row0 + g; row < row0 + 128; row += G) {
 			const long idx = (long)row * RP + c;
 			T nu = 0, de = 0;
 			for (int s = 0; s < slabs; ++s) {
 				nu += num_part[(long)s * part_stride + idx];
-				if (beta == 0) de += den_part[(long)s * part_stride + idx];
+				if (!vec_den) de += den_part[(long)s * part_stride + idx];
 			}
-			if (beta == 1) de = dvec;
+			if (vec_den) de = dvec;
 			T v = 0;
 			if (row < out_valid && c < r) {
-				const T quo = nu / (de + e_v);
-				v = A[idx] * (beta == 0 ? sqrt(quo) : quo);
+				if (!EXT) {
+					const T quo = nu / (de + e_v);
+					v = A[idx] * (power == 1 ? sqrt(quo) : quo);
+				} else {
+					const T a = A[idx];
+					const T quo = penalised ? nu / (de + e_v + l1_v + l2_v * a) : nu / (de + e_v);
+					T f = quo;
+					if (power == 1) f = sqrt(quo);
+					else if (power == 2) f = quo > T(0) ? exp2(g_v * log2(quo)) : T(0);
+					v = a * f;
+				}
 			}
 			A[idx] = v;
 			sq += v * v;
@@ -330,13 +369,16 @@ BetaPlan plan_beta_half_step(long out_pad, long red_pad, int RP, size_t elem_byt
 }
 
 template <typename T>
-hipError_t launch_beta_fused(const T* X, long ldx, const T* A, const T* B, int RP, int beta, bool update, bool terms, T eps, const BetaPlan& plan,
+hipError_t launch_beta_fused(const T* X, long ldx, const T* A, const T* B, int RP, double beta_value, bool update, bool terms, T eps, const BetaPlan& plan,
                              T* num_part, T* den_part, long part_stride, T* tf_part, T* td_part, long t_stride,
                              int out_pad, int out_valid, int red_valid, hipStream_t stream) {
-	if (!beta_half_step_available(RP) || (beta != 0 && beta != 1) || (!update && !terms) || out_pad <= 0 || out_pad % 128 != 0 || plan.slabs < 1 ||
+	// (beta is taken in the precision of T; 1 and 0 have their own element-wise maps, every other finite value runs the general one)
+	const T bexp = (T)beta_value;
+	const int beta = bexp == T(1) ? 1 : bexp == T(0) ? 0 : BETA_GENERAL;
+	if (!beta_half_step_available(RP) || !std::isfinite((double)bexp) || (!update && !terms) || out_pad <= 0 || out_pad % 128 != 0 || plan.slabs < 1 ||
 	    out_valid > out_pad || red_valid > (long)plan.tiles * plan.kt || ldx < (long)plan.tiles * plan.kt || ldx % 4 != 0)
 		return hipErrorInvalidValue;
-	if (update && (num_part == nullptr || (beta == 0 && den_part == nullptr))) return hipErrorInvalidValue;
+	if (update && (num_part == nullptr || (beta != 1 && den_part == nullptr))) return hipErrorInvalidValue;
 	if (terms && (tf_part == nullptr || td_part == nullptr)) return hipErrorInvalidValue;
 	const dim3 grid((unsigned)(out_pad / plan.bo), (unsigned)plan.slabs), block(256);
 	hipError_t e = hipSuccess;
@@ -345,7 +387,7 @@ hipError_t launch_beta_fused(const T* X, long ldx, const T* A, const T* B, int R
 		static std::atomic<unsigned long long> done{0};                                                                                                    \
 		e = allow_dynamic_lds(reinterpret_cast<const void*>(&KERNEL), (int)(BYTES), done);                                                                 \
 		if (e != hipSuccess) return e;                                                                                                                     \
-		hipLaunchKernelGGL(KERNEL, grid, block, (size_t)(BYTES), stream, X, ldx, A, B, eps, num_part, den_part, part_stride, tf_part, td_part, t_stride,   \
+		hipLaunchKernelGGL(KERNEL, grid, block, (size_t)(BYTES), stream, X, ldx, A, B, eps, bexp, num_part, den_part, part_stride, tf_part, td_part, t_stride,   \
 		                   out_valid, red_valid, plan.tiles, plan.tiles_per_slab);                                                                         \
 	} while (0)
 	if constexpr (sizeof(T) == 4) {
@@ -356,6 +398,10 @@ hipError_t launch_beta_fused(const T* X, long ldx, const T* A, const T* B, int R
 			if (update && terms) NMFAMD_BETA_GO((k_beta_fused_f32<RPV, 1, true, true, WO, WK>), bytes);                                                    \
 			else if (update) NMFAMD_BETA_GO((k_beta_fused_f32<RPV, 1, true, false, WO, WK>), bytes);                                                       \
 			else NMFAMD_BETA_GO((k_beta_fused_f32<RPV, 1, false, true, WO, WK>), bytes);                                                                   \
+		} else if (beta == BETA_GENERAL) { \
+			if (update && terms) NMFAMD_BETA_GO((k_beta_fused_f32<RPV, BETA_GENERAL, true, true, WO, WK>), bytes); \
+			else if (update) NMFAMD_BETA_GO((k_beta_fused_f32<RPV, BETA_GENERAL, true, false, WO, WK>), bytes); \
+			else NMFAMD_BETA_GO((k_beta_fused_f32<RPV, BETA_GENERAL, false, true, WO, WK>), bytes); \
 		} else {                                                                                                                                           \
 			if (update && terms) NMFAMD_BETA_GO((k_beta_fused_f32<RPV, 0, true, true, WO, WK>), bytes);                                                    \
 			else if (update) NMFAMD_BETA_GO((k_beta_fused_f32<RPV, 0, true, false, WO, WK>), bytes);                                                       \
@@ -377,6 +423,10 @@ hipError_t launch_beta_fused(const T* X, long ldx, const T* A, const T* B, int R
 			if (update && terms) NMFAMD_BETA_GO((k_beta_fused_valu<T, RPV, 1, true, true>), bytes);                                                        \
 			else if (update) NMFAMD_BETA_GO((k_beta_fused_valu<T, RPV, 1, true, false>), bytes);                                                           \
 			else NMFAMD_BETA_GO((k_beta_fused_valu<T, RPV, 1, false, true>), bytes);                                                                       \
+		} else if (beta == BETA_GENERAL) { \
+			if (update && terms) NMFAMD_BETA_GO((k_beta_fused_valu<T, RPV, BETA_GENERAL, true, true>), bytes); \
+			else if (update) NMFAMD_BETA_GO((k_beta_fused_valu<T, RPV, BETA_GENERAL, true, false>), bytes); \
+			else NMFAMD_BETA_GO((k_beta_fused_valu<T, RPV, BETA_GENERAL, false, true>), bytes); \
 		} else {                                                                                                                                           \
 			if (update && terms) NMFAMD_BETA_GO((k_beta_fused_valu<T, RPV, 0, true, true>), bytes);                                                        \
 			else if (update) NMFAMD_BETA_GO((k_beta_fused_valu<T, RPV, 0, true, false>), bytes);                                                           \
@@ -394,25 +444,37 @@ hipError_t launch_beta_fused(const T* X, long ldx, const T* A, const T* B, int R
 #undef NMFAMD_BETA_GO
 	return hipGetLastError();
 }
-template hipError_t launch_beta_fused<float>(const float*, long, const float*, const float*, int, int, bool, bool, float, const BetaPlan&, float*, float*, long, float*, float*,
+template hipError_t launch_beta_fused<float>(const float*, long, const float*, const float*, int, double, bool, bool, float, const BetaPlan&, float*, float*, long, float*, float*,
                                              long, int, int, int, hipStream_t);
-template hipError_t launch_beta_fused<double>(const double*, long, const double*, const double*, int, int, bool, bool, double, const BetaPlan&, double*, double*, long, double*,
+template hipError_t launch_beta_fused<double>(const double*, long, const double*, const double*, int, double, bool, bool, double, const BetaPlan&, double*, double*, long, double*,
                                               double*, long, int, int, int, hipStream_t);
 
 template <typename T>
 hipError_t launch_beta_update(T* A, const T* num_part, const T* den_part, long part_stride, int slabs, const T* dsum, int RP, int r, int out_pad, int out_valid, T eps,
-                              int beta, bool update, T* sumsq_part, T* sum_part, const T* tf_part, const T* td_part, long t_stride, T* t_frob, T* t_div,
-                              hipStream_t stream) {
-	if (!beta_half_step_available(RP) || (beta != 0 && beta != 1) || out_pad <= 0 || out_pad % 128 != 0 || slabs < 1 || r < 1 || r > RP) return hipErrorInvalidValue;
-	if (update && (num_part == nullptr || (beta == 0 ? den_part == nullptr : dsum == nullptr))) return hipErrorInvalidValue;
+                              double beta_value, T l1, T l2, bool update, T* sumsq_part, T* sum_part, const T* tf_part, const T* td_part, long t_stride, T* t_frob,
+                              T* t_div, hipStream_t stream) {
+	// gamma: scikit-learn's rule (the majorise-minimise exponent of Fevotte & Idier 2011)
+	const double b = (double)(T)beta_value;      // (in the precision of T, as launch_beta_fused takes it)
+	const bool vec_den = b == 1.0;
+	const double gamma = b < 1.0 ? 1.0 / (2.0 - b) : b <= 2.0 ? 1.0 : 1.0 / (b - 1.0);
+	const int power = gamma == 1.0 ? 0 : gamma == 0.5 ? 1 : 2;
+	const bool penalised = l1 != T(0) || l2 != T(0);
+	if (!beta_half_step_available(RP) || !std::isfinite(b) || !(l1 >= T(0)) || !(l2 >= T(0)) || !std::isfinite((double)l1) || !std::isfinite((double)l2) ||
+	    out_pad <= 0 || out_pad % 128 != 0 || slabs < 1 || r < 1 || r > RP)
+		return hipErrorInvalidValue;
+	if (update && (num_part == nullptr || (vec_den ? dsum == nullptr : den_part == nullptr))) return hipErrorInvalidValue;
 	if ((t_frob == nullptr) != (t_div == nullptr) || (t_frob != nullptr && (tf_part == nullptr || td_part == nullptr)) || (!update && t_frob == nullptr)) return hipErrorInvalidValue;
-	hipLaunchKernelGGL((k_beta_update<T>), dim3((unsigned)(out_pad / 128)), dim3(256), 0, stream, A, num_part, den_part, part_stride, slabs, dsum, RP, r, out_valid, eps, beta,
-	                   update ? 1 : 0, sumsq_part, sum_part, tf_part, td_part, t_stride, t_frob, t_div);
+	if (penalised || power == 2)
+		hipLaunchKernelGGL((k_beta_update<T, true>), dim3((unsigned)(out_pad / 128)), dim3(256), 0, stream, A, num_part, den_part, part_stride, slabs, dsum, RP, r, out_valid,
+		                   eps, vec_den ? 1 : 0, power, (T)gamma, penalised ? 1 : 0, l1, l2, update ? 1 : 0, sumsq_part, sum_part, tf_part, td_part, t_stride, t_frob, t_div);
+	else
+		hipLaunchKernelGGL((k_beta_update<T, false>), dim3((unsigned)(out_pad / 128)), dim3(256), 0, stream, A, num_part, den_part, part_stride, slabs, dsum, RP, r, out_valid,
+		                   eps, vec_den ? 1 : 0, power, (T)gamma, 0, T(0), T(0), update ? 1 : 0, sumsq_part, sum_part, tf_part, td_part, t_stride, t_frob, t_div);
 	return hipGetLastError();
 }
-template hipError_t launch_beta_update<float>(float*, const float*, const float*, long, int, const float*, int, int, int, int, float, int, bool, float*, float*, const float*,
+template hipError_t launch_beta_update<float>(float*, const float*, const float*, long, int, const float*, int, int, int, int, float, double, float, float, bool, float*, float*, const float*,
                                               const float*, long, float*, float*, hipStream_t);
-template hipError_t launch_beta_update<double>(double*, const double*, const double*, long, int, const double*, int, int, int, int, double, int, bool, double*, double*,
+template hipError_t launch_beta_update<double>(double*, const double*, const double*, long, int, const double*, int, int, int, int, double, double, double, double, bool, double*, double*,
                                                const double*, const double*, long, double*, double*, hipStream_t);
 
 } // namespace nmfamd

@@ -29,6 +29,11 @@ class _ParamsV2(C.Structure):
     _fields_ = [("base", _Params), ("dense_compute", C.c_double)]
 
 
+class _ParamsV3(C.Structure):
+    """nmfamd_params_v3: nmfamd_params_v2 (which keeps its size) followed by the fields added since."""
+    _fields_ = [("v2", _ParamsV2), ("beta", C.c_double)]
+
+
 class _Geometry(C.Structure):
     _fields_ = [("m", C.c_int), ("n", C.c_int), ("r", C.c_int), ("padded_rank", C.c_int),
                 ("padded_m", C.c_long), ("padded_n", C.c_long), ("slabs_h", C.c_int), ("slabs_w", C.c_int),
@@ -59,25 +64,30 @@ class Engine:
     def __init__(self, m: int, n: int, r: int, algorithm: str = "mu", dtype=np.float32, stream: int = 0,
                  lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence: str = "frobenius",
                  sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False,
-                 l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False):
-        """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V) or
-        "is" (Itakura-Saito, always dense: every entry of V > 0) -- docs/DIVERGENCE.md.  The dense divergence engines are "mu" only, rank <= 256, single GPU;
-        divergence_value reports their objective.
+                 l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None):
+        """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V),
+        "is" (Itakura-Saito, always dense: every entry of V > 0) or "beta" (the beta-divergence at `beta`, any finite value, always dense: scikit-learn's
+        solver="mu" with beta_loss=beta; beta=0.0 and beta=1.0 are the "is" and the dense "kl" engines; beta <= 0 needs every entry of V > 0) --
+        docs/DIVERGENCE.md.  The dense divergence engines are "mu" only, rank <= 256, single GPU; divergence_value reports their objective.
 
         missing_values=True: fit the observed entries only (docs/MISSING.md) -- the stored entries of upload_sparse, the non-NaN entries of
         upload (zeros included).  Multiplicative update ("mu") with the Frobenius objective only; implies sparse_compute.
 
-        l1_w, l1_h, l2_w, l2_h: "hals" only (docs/HALS.md) -- the L1 / L2 penalties of scikit-learn's coordinate descent on W and H; see
-        set_penalties.  sparse_compute=True is available for "mu" and "hals" (rank <= 256)."""
+        l1_w, l1_h, l2_w, l2_h: the L1 / L2 penalties on W and H of scikit-learn's coordinate descent ("hals", docs/HALS.md) and of its multiplicative update
+        (the dense divergence engines, docs/DIVERGENCE.md); see set_penalties.  sparse_compute=True is available for "mu" and "hals" (rank <= 256)."""
         self._lib = library()
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise TypeError("float32 or float64")
         self.m, self.n, self.r = m, n, r
+        if beta is not None and divergence != "beta":
+            raise ValueError('beta needs divergence="beta"')
+        if divergence == "beta" and beta is None:
+            raise ValueError('divergence="beta" needs a beta')
         self._ctor = dict(algorithm=algorithm, stream=stream, row_blocks=row_blocks,
-                          params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0, "is": 2.0}[divergence],
+                          params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0, "is": 2.0, "beta": 3.0}[divergence],
                                   float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
-                                  float(missing_values), float(dense_compute)],
+                                  float(missing_values), float(dense_compute), float(beta or 0.0)],
                           penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)])
         self._h = None
         self._lib.nmfamd_engine_frobenius.restype = C.c_double
@@ -89,12 +99,12 @@ class Engine:
 
     def _create(self):
         c = self._ctor
-        p = _ParamsV2(_Params(*c["params"][:10]), *c["params"][10:])
+        p = _ParamsV3(_ParamsV2(_Params(*c["params"][:10]), c["params"][10]), c["params"][11])
         h = C.c_void_p()
         # row_blocks > 1: the padded row count is a multiple of 128 * row_blocks (row-block form of the sharded W step)
         if not hasattr(self._lib, "nmfamd_engine_create_v2"):
             # (NMFAMD_LIBRARY names a build from before the sized entry -- tools/time_beta.py times such a build: it reads the frozen struct only)
-            st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p.base), self.dtype.itemsize,
+            st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p.v2.base), self.dtype.itemsize,
                                                        C.c_void_p(c["stream"]), int(c["row_blocks"]), C.byref(h))
         else:
             st = self._lib.nmfamd_engine_create_v2(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p), C.c_ulong(C.sizeof(p)), self.dtype.itemsize,
@@ -185,8 +195,9 @@ class Engine:
 
     def set_penalties(self, l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0):
         """HALS: the iterations that follow minimise 1/2 ||V - W H||^2 + l1_w ||W||_1 + l1_h ||H||_1 + 1/2 l2_w ||W||^2 + 1/2 l2_h ||H||^2
-        (nmfamd_engine_set_hals_penalties; docs/HALS.md has the mapping from scikit-learn's alpha_W, alpha_H, l1_ratio).  Valid between
-        iterations; all zeros restores the unpenalised iteration.  frobenius / rmsd keep reporting ||V - W H||."""
+        (nmfamd_engine_set_hals_penalties; docs/HALS.md has the mapping from scikit-learn's alpha_W, alpha_H, l1_ratio).  Dense divergence engines: the
+        same four terms added to the divergence (scikit-learn's multiplicative update, docs/DIVERGENCE.md).  Valid between iterations; all zeros restores
+        the unpenalised iteration, normalisation included.  frobenius / rmsd / divergence_value keep reporting the unpenalised figures."""
         vals = [float(l1_w), float(l1_h), float(l2_w), float(l2_h)]
         self._check(self._lib.nmfamd_engine_set_hals_penalties(self._h, *(C.c_double(v) for v in vals)), "set_hals_penalties")
         self._ctor["penalties"] = vals
@@ -201,7 +212,8 @@ class Engine:
 
     @property
     def divergence_value(self) -> float:
-        """The objective of whichever divergence the engine has (generalised KL or Itakura-Saito), of the most recent error iteration."""
+        """The objective of whichever divergence the engine has (generalised KL, Itakura-Saito or the beta-divergence at the engine's beta), of the most
+        recent error iteration: the divergence alone, without penalty terms."""
         fn = self._lib.nmfamd_engine_divergence
         fn.restype = C.c_double
         return float(fn(self._h))
@@ -626,6 +638,10 @@ def op_beta_half_step(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: int, out_v
     the other panel, X (out_pad, ldx) the image of V (X[o, k]; zero on the padding).  beta: 1 (KL; dsum = the RP column sums of B) or 0 (Itakura-Saito).
     form: 0 update, 1 update + error terms, 2 error terms only.  Returns a dict: `A` (the new panel), `t_frob`, `t_div` (out_pad values each; None for form 0),
     `sumsq_part`, `sum_part` ((out_pad // 128, RP)) and `slabs`."""
+    return _beta_half_step(A, B, X, r, out_valid, red_valid, int(beta), form, dsum, force_slabs, None)
+
+
+def _beta_half_step(A, B, X, r, out_valid, red_valid, beta, form, dsum, force_slabs, penalties):
     dt = np.dtype(A.dtype)
     if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
         raise TypeError("float32 or float64")
@@ -643,13 +659,26 @@ def op_beta_half_step(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: int, out_v
     parts = out_pad // 128
     sq, sm = np.zeros((max(parts, 1), RP), dt), np.zeros((max(parts, 1), RP), dt)
     slabs = C.c_int(0)
-    fn = library().nmfamd_op_beta_half_step_f32 if dt == np.float32 else library().nmfamd_op_beta_half_step_f64
+    lib = library()
+    if penalties is None:
+        fn, how = (lib.nmfamd_op_beta_half_step_f32 if dt == np.float32 else lib.nmfamd_op_beta_half_step_f64), (int(beta),)
+    else:
+        fn = lib.nmfamd_op_beta_half_step_general_f32 if dt == np.float32 else lib.nmfamd_op_beta_half_step_general_f64
+        how = (C.c_double(beta), C.c_double(penalties[0]), C.c_double(penalties[1]))
     ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
-    st = fn(ptr(A), ptr(B), ptr(X), C.c_long(X.shape[1]), RP, int(r), out_pad, int(out_valid), red_pad, int(red_valid), int(beta), int(form), int(force_slabs),
+    st = fn(ptr(A), ptr(B), ptr(X), C.c_long(X.shape[1]), RP, int(r), out_pad, int(out_valid), red_pad, int(red_valid), *how, int(form), int(force_slabs),
             ptr(d), ptr(tf), ptr(td), ptr(sq), ptr(sm), C.byref(slabs))
     if st != 0:
         raise EngineError(st, "nmfamd_op_beta_half_step")
     return {"A": A, "t_frob": tf, "t_div": td, "sumsq_part": sq, "sum_part": sm, "slabs": slabs.value}
+
+
+def op_beta_half_step_general(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: int, out_valid: int, red_valid: int, beta: float, form: int = 0, *,
+                              l1: float = 0.0, l2: float = 0.0, dsum: Optional[np.ndarray] = None, force_slabs: int = 0):
+    """op_beta_half_step with any finite beta and penalties l1, l2 >= 0 on the updated panel (nmfamd_op_beta_half_step_general_*): A <- A (num / (den + eps + l1 +
+    l2 A))^gamma.  beta = 0 and beta = 1 run the Itakura-Saito and KL launches (dsum: beta = 1 only), every other value the general form, whose `t_div` is the
+    beta-divergence of Engine.divergence_value.  The same arguments and the same dict otherwise."""
+    return _beta_half_step(A, B, X, r, out_valid, red_valid, float(beta), form, dsum, force_slabs, (float(l1), float(l2)))
 
 
 def op_hals_normalize(Wt: np.ndarray, H: np.ndarray, sumsq_part: np.ndarray):
