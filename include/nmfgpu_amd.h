@@ -98,6 +98,17 @@ typedef struct nmfamd_params_v3 {
 	                           refused.  The limits of the dense divergence engines (nmfamd_params_v2.dense_compute) apply */
 } nmfamd_params_v3;
 
+/* nmfamd_params_v3 followed by what has been added since (v2 and v3 keep their sizes).  nmfamd_engine_create_v2 reads min(params_size, sizeof(nmfamd_params_v4))
+ * bytes and takes the rest as 0. */
+typedef struct nmfamd_params_v4 {
+	nmfamd_params_v3 v3;
+	double weighted;        /* 0 or 1.  1: weighted NMF (docs/DIVERGENCE.md, "Weighted update") -- the objective is sum_ij w_ij d_beta(v_ij | (W H)_ij) with a matrix of
+	                           weights w >= 0 uploaded beside V by nmfamd_engine_upload_dense_weighted (the only upload such an engine takes).  A weight of 0 means the
+	                           entry is not there (missing-value NMF for every beta; V may hold anything at it, NaN included); real weights are weighted NMF (LS-NMF at
+	                           beta = 2).  Only on a dense divergence engine: v3.v2.base.divergence = 2 or 3, or 1 with dense_compute; any other value, and weighted = 1
+	                           on any other engine, is refused at creation.  The limits of the dense divergence engines apply */
+} nmfamd_params_v4;
+
 typedef struct nmfamd_engine nmfamd_engine;  /* opaque; owns every device buffer of one factorisation */
 
 /* Number of visible HIP devices (0 when there is none), and the library's build description. */
@@ -112,7 +123,7 @@ NMFAMD_API const char* nmfamd_engine_last_error(const nmfamd_engine* e);
  * every kernel and copy of this engine is issued on it. */
 NMFAMD_API int nmfamd_engine_create(int m, int n, int r, int algorithm, const nmfamd_params* params,
                                     int elem_bytes, void* stream, nmfamd_engine** out);
-/* The same with the sized, extended parameter struct (nmfamd_params_v2 or nmfamd_params_v3; params_size = sizeof of the caller's struct, at least
+/* The same with the sized, extended parameter struct (nmfamd_params_v2, _v3 or _v4; params_size = sizeof of the caller's struct, at least
  * sizeof(nmfamd_params) unless params is NULL) and the row blocks of nmfamd_engine_create_blocks (1: none). */
 NMFAMD_API int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* params, unsigned long params_size,
                                        int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out);
@@ -122,6 +133,12 @@ NMFAMD_API void nmfamd_engine_destroy(nmfamd_engine* e);
  * Replaces DeviceMatrix::copyFrom(inputMatrix) + the trace kernel + host sort
  * (AlgorithmMultiplicativeFrobenius.h:118-126; sparse -> dense with index base: Matrix.h:145-232). */
 NMFAMD_API int nmfamd_engine_upload_dense(nmfamd_engine* e, const void* V, long ld);
+/* Weighted engines (nmfamd_params_v4.weighted = 1): V and the weights Omega, both m x n column-major host matrices of the engine's precision.  Every weight
+ * finite and >= 0, at least one > 0; where a weight is > 0, V obeys the value rule of the engine's beta (finite; > 0 for beta <= 0, >= 0 for beta > 0); where it
+ * is 0, V is not looked at (and is stored as 0).  Keeps four dense images (V, Omega and their transposes: nmfamd_geometry.resident_images = 4); a second call
+ * replaces both matrices.  rmsd = frobenius / sqrt(sum of the weights).  NMFAMD_INVALID_ARGUMENT with nmfamd_engine_last_error for a value that breaks a rule
+ * and on an engine that is not weighted; a weighted engine refuses nmfamd_engine_upload_dense and nmfamd_engine_upload_sparse the same way. */
+NMFAMD_API int nmfamd_engine_upload_dense_weighted(nmfamd_engine* e, const void* V, long ldv, const void* Omega, long ldo);
 /* format CSR: a = rowPtr (m+1), b = column indices; CSC: a = columnPtr (n+1), b = row indices;
  * COO: a = row indices, b = column indices (nnz each).  base = 0 or 1. */
 NMFAMD_API int nmfamd_engine_upload_sparse(nmfamd_engine* e, int format, const void* values, const int* a, const int* b, long nnz, int base);
@@ -182,9 +199,11 @@ typedef struct nmfamd_geometry {
 	long exchange_count;   /* elements of the multi-GPU exchange buffer */
 	int product_kernel;    /* 0 fp32 MFMA, 1 bf16-rounded operands, 2 fp32 by exact 3 x bf16 operand splitting, 3 fp64 MFMA,
 	                          4 VALU kernel (NMFAMD_FORCE_VALU), 5 sparse SpMM, 6 the fused dense beta-divergence half-step (kernels_beta.hip: slabs_h / slabs_w
-	                          are then the reduction slabs of its two launches, which fix the summation order; resident_images = 2, kl_blocks_* = 0) */
+	                          are then the reduction slabs of its two launches, which fix the summation order; resident_images = 2, or 4 on a weighted engine;
+	                          kl_blocks_* = 0) */
 	int resident_images;   /* dense images of V kept in HBM: 2 (V and V^T, each streamed along its output index), 1 (only V: W^T V
-	                          reads it along the reduction index; chosen when two would not fit, or by NMFAMD_ONE_IMAGE), 0 sparse */
+	                          reads it along the reduction index; chosen when two would not fit, or by NMFAMD_ONE_IMAGE), 0 sparse, 4 a weighted dense divergence
+	                          engine (V, the weights and the transposes of both) */
 	int one_pass;          /* rank-64 multiplicative update: 1 = V is streamed ONCE per iteration (W^T V, the H update and V H^T in one
 	                          persistent launch, kernels_onepass.hip; the MEASUREMENT build only since round 6: NMFAMD_ONE_PASS=1 there); 0 = two passes; 2 = a one-pass launch
 	                          gave up (it could not keep its workgroups resident) and the engine reported the error */
@@ -414,6 +433,15 @@ NMFAMD_API int nmfamd_op_beta_half_step_general_f32(float* A, const float* B, co
 NMFAMD_API int nmfamd_op_beta_half_step_general_f64(double* A, const double* B, const double* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad,
                                                     int red_valid, double beta, double l1, double l2, int form, int force_slabs, const double* dsum, double* t_frob,
                                                     double* t_div, double* sumsq_part, double* sum_part, int* slabs);
+/* The weighted half-step (kernels_beta_weighted.hip; docs/DIVERGENCE.md, "Weighted update"): nmfamd_op_beta_half_step_general_* with Omega, an array of the shape
+ * and leading dimension of X that holds the weights (>= 0; 0 on the padding).  An entry with weight 0 is not there, whatever X holds at it.  The denominator is a
+ * product at every beta: dsum is not used. */
+NMFAMD_API int nmfamd_op_beta_half_step_weighted_f32(float* A, const float* B, const float* X, const float* Omega, long ldx, int RP, int r, int out_pad, int out_valid,
+                                                     int red_pad, int red_valid, double beta, double l1, double l2, int form, int force_slabs, const float* dsum,
+                                                     float* t_frob, float* t_div, float* sumsq_part, float* sum_part, int* slabs);
+NMFAMD_API int nmfamd_op_beta_half_step_weighted_f64(double* A, const double* B, const double* X, const double* Omega, long ldx, int RP, int r, int out_pad, int out_valid,
+                                                     int red_pad, int red_valid, double beta, double l1, double l2, int form, int force_slabs, const double* dsum,
+                                                     double* t_frob, double* t_div, double* sumsq_part, double* sum_part, int* slabs);
 /* Test access to an engine's device intermediates in panel layout: which = 0 Wt, 1 H, 2 W^T W,
  * 3 H H^T, 4 slabs, 5 inverse, 6 V, 7 Vt; rank-256 fp32 engines also 8 W^T W as last reduced, 9 staged column sums of squares,
  * 10 / 11 the bf16 fragments of W / H as 4-byte words. */

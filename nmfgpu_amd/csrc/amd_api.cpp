@@ -169,9 +169,10 @@ int nmfamd_engine_create_blocks(int m, int n, int r, int algorithm, const nmfamd
 
 int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* params_sized, unsigned long params_size, int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out) {
 	if (params_sized != nullptr && params_size < sizeof(nmfamd_params)) return NMFAMD_INVALID_ARGUMENT;
-	nmfamd_params_v3 v3;
-	std::memset(&v3, 0, sizeof(v3));
-	if (params_sized != nullptr) std::memcpy(&v3, params_sized, params_size < sizeof(v3) ? (size_t)params_size : sizeof(v3));
+	nmfamd_params_v4 v4;
+	std::memset(&v4, 0, sizeof(v4));
+	if (params_sized != nullptr) std::memcpy(&v4, params_sized, params_size < sizeof(v4) ? (size_t)params_size : sizeof(v4));
+	const nmfamd_params_v3& v3 = v4.v3;
 	const nmfamd_params_v2& v2 = v3.v2;
 	const nmfamd_params* params = params_sized != nullptr ? &v2.base : nullptr;
 	if (!out || (elem_bytes != 4 && elem_bytes != 8) || row_blocks < 1 || row_blocks > 64) return NMFAMD_INVALID_ARGUMENT;
@@ -179,7 +180,7 @@ int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* para
 	g_create_error.clear();
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	AlgorithmParams p;
-	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; p.dense_compute = v2.dense_compute; p.beta_value = v3.beta; }
+	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; p.dense_compute = v2.dense_compute; p.beta_value = v3.beta; p.weighted = v4.weighted; }
 	nmfamd_engine* e = new (std::nothrow) nmfamd_engine();
 	if (!e) return NMFAMD_NO_HOST_MEMORY;
 	e->elem_bytes = elem_bytes;
@@ -285,6 +286,11 @@ const char* nmfamd_sharded_last_error(const nmfamd_sharded* s) { return !s ? "" 
 int nmfamd_engine_upload_dense(nmfamd_engine* e, const void* V, long ld) {
 	return dispatch(e, [&](Engine<float>& g) { return g.upload_dense((const float*)V, ld); },
 	                   [&](Engine<double>& g) { return g.upload_dense((const double*)V, ld); });
+}
+
+int nmfamd_engine_upload_dense_weighted(nmfamd_engine* e, const void* V, long ldv, const void* Omega, long ldo) {
+	return dispatch(e, [&](Engine<float>& g) { return g.upload_dense_weighted((const float*)V, ldv, (const float*)Omega, ldo); },
+	                   [&](Engine<double>& g) { return g.upload_dense_weighted((const double*)V, ldv, (const double*)Omega, ldo); });
 }
 
 int nmfamd_engine_upload_sparse(nmfamd_engine* e, int format, const void* values, const int* a, const int* b, long nnz, int base) {
@@ -883,14 +889,17 @@ int op_hals_normalize(T* Wt, int RP, int mpad, T* H, int npad, const T* sumsq_pa
 
 template <typename T>
 int op_beta_half_step(T* A, const T* B, const T* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid, double beta_value, double l1d,
-                      double l2d, int form, int force_slabs, const T* dsum, T* t_frob, T* t_div, T* sumsq_part, T* sum_part, int* slabs) {
+                      double l2d, int form, int force_slabs, const T* dsum, T* t_frob, T* t_div, T* sumsq_part, T* sum_part, int* slabs, const T* Omega = nullptr,
+                      bool weighted = false) {
+	// weighted: the half-step of kernels_beta_weighted.hip with Omega, an array like X (dsum is not used)
 	const bool update = form == 0 || form == 1, terms = form == 1 || form == 2;
+	if (weighted && !Omega) return NMFAMD_INVALID_ARGUMENT;
 	const double beta = (double)(T)beta_value;      // (in the precision of T, as the launchers take it)
 	const T l1 = (T)l1d, l2 = (T)l2d;
 	if (!A || !B || !X || !beta_half_step_available(RP) || r < 1 || r > RP || !std::isfinite(beta) || !(l1d >= 0) || !(l2d >= 0) || !std::isfinite((double)l1) ||
 	    !std::isfinite((double)l2) || form < 0 || form > 2 || out_pad < 128 || out_pad % 128 != 0 ||
 	    red_pad < 128 || red_pad % 128 != 0 || out_valid < 0 || out_valid > out_pad || red_valid < 0 || red_valid > red_pad || ldx < red_pad || ldx % 4 != 0 ||
-	    force_slabs < 0 || (update && beta == 1 && !dsum) || (terms && (!t_frob || !t_div)))
+	    force_slabs < 0 || (update && beta == 1 && !dsum && !weighted) || (terms && (!t_frob || !t_div)))
 		return NMFAMD_INVALID_ARGUMENT;
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	int dev = 0;
@@ -901,7 +910,9 @@ int op_beta_half_step(T* A, const T* B, const T* X, long ldx, int RP, int r, int
 	const size_t panelA = sizeof(T) * (size_t)out_pad * RP, panelB = sizeof(T) * (size_t)red_pad * RP, image = sizeof(T) * (size_t)out_pad * (size_t)ldx;
 	const size_t parts = (size_t)(out_pad / 128) * RP;
 	const long part_stride = (long)out_pad * RP;
-	DevBuf dA, dB, dX, dNum, dDen, dT, dOut, dSum, dD;
+	DevBuf dA, dB, dX, dNum, dDen, dT, dOut, dSum, dD, dO;
+	if (weighted && (dO.alloc(image) != hipSuccess)) return NMFAMD_NO_DEVICE_MEMORY;
+	if (weighted && hipMemcpy(dO.p, Omega, image, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (dA.alloc(panelA) != hipSuccess || dB.alloc(panelB) != hipSuccess || dX.alloc(image) != hipSuccess || dNum.alloc(panelA * plan.slabs) != hipSuccess ||
 	    dDen.alloc(panelA * plan.slabs) != hipSuccess || dT.alloc(sizeof(T) * 2 * (size_t)plan.slabs * out_pad) != hipSuccess ||
 	    dOut.alloc(sizeof(T) * 2 * (size_t)out_pad) != hipSuccess || dSum.alloc(sizeof(T) * 2 * parts) != hipSuccess || dD.alloc(sizeof(T) * (size_t)RP) != hipSuccess)
@@ -916,11 +927,13 @@ int op_beta_half_step(T* A, const T* B, const T* X, long ldx, int RP, int r, int
 	T* of = terms ? (T*)dOut.p : nullptr;
 	T* od = terms ? (T*)dOut.p + out_pad : nullptr;
 	const T eps = std::numeric_limits<T>::epsilon();
-	if (launch_beta_fused<T>((const T*)dX.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update, terms, eps, plan, (T*)dNum.p, (T*)dDen.p, part_stride, tf, td, out_pad,
-	                         out_pad, out_valid, red_valid, nullptr) != hipSuccess)
+	if ((weighted ? launch_beta_fused_weighted<T>((const T*)dX.p, (const T*)dO.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update, terms, eps, plan, (T*)dNum.p,
+	                                              (T*)dDen.p, part_stride, tf, td, out_pad, out_pad, out_valid, red_valid, nullptr)
+	              : launch_beta_fused<T>((const T*)dX.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update, terms, eps, plan, (T*)dNum.p, (T*)dDen.p, part_stride, tf, td,
+	                                     out_pad, out_pad, out_valid, red_valid, nullptr)) != hipSuccess)
 		return NMFAMD_HIP_ERROR;
 	if (launch_beta_update<T>((T*)dA.p, (const T*)dNum.p, (const T*)dDen.p, part_stride, plan.slabs, (const T*)dD.p, RP, r, out_pad, out_valid, eps, beta, l1, l2, update,
-	                          (T*)dSum.p, (T*)dSum.p + parts, tf, td, out_pad, of, od, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+	                          (T*)dSum.p, (T*)dSum.p + parts, tf, td, out_pad, of, od, nullptr, weighted) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
 		return NMFAMD_HIP_ERROR;
 	if (hipMemcpy(A, dA.p, panelA, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (terms && (hipMemcpy(t_frob, of, sizeof(T) * (size_t)out_pad, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -955,6 +968,20 @@ int nmfamd_op_beta_half_step_general_f64(double* A, const double* B, const doubl
                                          double beta, double l1, double l2, int form, int force_slabs, const double* dsum, double* t_frob, double* t_div,
                                          double* sumsq_part, double* sum_part, int* slabs) {
 	return op_beta_half_step<double>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, beta, l1, l2, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs);
+}
+
+int nmfamd_op_beta_half_step_weighted_f32(float* A, const float* B, const float* X, const float* Omega, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad,
+                                          int red_valid, double beta, double l1, double l2, int form, int force_slabs, const float* dsum, float* t_frob, float* t_div,
+                                          float* sumsq_part, float* sum_part, int* slabs) {
+	return op_beta_half_step<float>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, beta, l1, l2, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs,
+	                                Omega, true);
+}
+
+int nmfamd_op_beta_half_step_weighted_f64(double* A, const double* B, const double* X, const double* Omega, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad,
+                                          int red_valid, double beta, double l1, double l2, int form, int force_slabs, const double* dsum, double* t_frob, double* t_div,
+                                          double* sumsq_part, double* sum_part, int* slabs) {
+	return op_beta_half_step<double>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, beta, l1, l2, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs,
+	                                 Omega, true);
 }
 
 int nmfamd_op_hals_sweep_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid, float* ps,

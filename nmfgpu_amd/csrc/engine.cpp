@@ -135,7 +135,7 @@ Engine<T>::~Engine() {
 #ifdef NMFAMD_DIAG_BUILD
 	if (bf16_) bf_stamps_dump();
 #endif
-	T* bufs[] = {V_, Vt_, Wt_, H_, Ws_, Hs_, slabs_, numW_, Wold_, G_, G2_, HHt_, Qinv_, gram_part_, sumsq_part_, psN_, stage_};   // (psR_ lives behind psN_)
+	T* bufs[] = {V_, Vt_, Om_, Omt_, Wt_, H_, Ws_, Hs_, slabs_, numW_, Wold_, G_, G2_, HHt_, Qinv_, gram_part_, sumsq_part_, psN_, stage_};   // (psR_ lives behind psN_)
 	for (T* b : bufs) if (b) (void)hipFree(b);
 	if (inv_work_) (void)hipFree(inv_work_);
 	if (range_flag_) (void)hipFree(range_flag_);
@@ -179,7 +179,9 @@ Status Engine<T>::allocate() {
 	if (alg_ == ALG_HALS && !panel_sweep_hals_available(RP_, sizeof(T))) { last_error_ = "HALS: no sweep kernel for this padded rank (fp32: 64 ... 512, fp64: multiples of 64 up to 512)"; return ST_INVALID; }
 	if (Status s = set_hals_penalties(prm_.l1W, prm_.l1H, prm_.l2W, prm_.l2H)) return s;      // (values that came with the parameters: the setter's checks, and its rounding of prm_ to T)
 	if (const char* why = beta_dense_fault(prm_, alg_ == ALG_MU, r_, row_blocks_)) { last_error_ = why; return ST_INVALID; }
+	if (const char* why = weighted_fault(prm_)) { last_error_ = why; return ST_INVALID; }
 	beta_dense_ = prm_.is_beta_dense();
+	weighted_ = prm_.weighted != 0;
 	if (beta_dense_) {
 		// beta in the engine's precision, as the penalties: a value that rounds to 0 or 1 there IS the Itakura-Saito or the dense KL engine
 		beta_ = (double)(T)prm_.beta();
@@ -380,7 +382,8 @@ Status Engine<T>::allocate() {
 		HIPX(dalloc(&sW_, RP_));
 		HIPX(dalloc(&sH_, RP_));
 		HIPX(dalloc(&beta_tpart_, 2l * BETA_MAX_SLABS * mpad_));
-		if (beta_ != 1) HIPX(dalloc(&beta_den_, slab_elems));
+		if (beta_ != 1 || weighted_) HIPX(dalloc(&beta_den_, slab_elems));
+		if (weighted_) { HIPX(dalloc(&Om_, elemsV_)); HIPX(dalloc(&Omt_, elemsVt_)); }
 		HIPX(hipHostMalloc((void**)&pin_kl_, sizeof(T) * (2 * (size_t)m_ + 3 * (size_t)RP_)));
 	}
 	HIPX(dalloc(&Wt_, panelW));
@@ -580,6 +583,7 @@ Status Engine<T>::finish_upload(T* Vcol) {
 template <typename T>
 Status Engine<T>::upload_dense(const T* V, long ld) {
 	if (!V || ld < m_) return ST_INVALID;
+	if (weighted_) { last_error_ = "weighted NMF: V is uploaded together with its weights (upload_dense_weighted)"; return ST_INVALID; }
 	if (beta_dense_) {
 		beta_uploaded_ = false;
 		if (Status st = beta_check_values(V, n_, ld, m_)) return st;
@@ -621,6 +625,47 @@ Status Engine<T>::upload_dense(const T* V, long ld) {
 	return st;
 }
 
+// Weighted engines: V and its weights.  The values are checked jointly on the host (the weights alone, then V where its weight is > 0), the sum of the weights is
+// taken in double, and V goes to the device with 0 wherever its weight is 0, so that nothing that is not finite ever sits in a resident image (the kernels
+// mask by the weight all the same).  Four images: V_ / Om_ column-major, Vt_ / Omt_ their transposes.
+template <typename T>
+Status Engine<T>::upload_dense_weighted(const T* V, long ldv, const T* Omega, long ldo) {
+	if (!weighted_) { last_error_ = "weighted upload: the engine was not created with 'weighted' = 1"; return ST_INVALID; }
+	if (!V || !Omega || ldv < m_ || ldo < m_) return ST_INVALID;
+	beta_uploaded_ = false;
+	const bool is = beta_ <= 0;
+	double sum_w = 0;
+	bool any = false;
+	std::vector<T> clean((size_t)m_ * (size_t)n_);
+	for (long j = 0; j < n_; ++j)
+		for (long i = 0; i < m_; ++i) {
+			const T w = Omega[(size_t)j * ldo + i];
+			if (!std::isfinite(w) || w < T(0)) { last_error_ = "weighted NMF: every weight has to be finite and >= 0"; return ST_INVALID; }
+			T v = T(0);
+			if (w > T(0)) {
+				v = V[(size_t)j * ldv + i];
+				if (!std::isfinite(v) || v < T(0) || (is && v == T(0))) {
+					last_error_ = is ? "weighted NMF with beta <= 0: every entry of V with a weight > 0 has to be finite and > 0"
+					                 : "weighted NMF with beta > 0: every entry of V with a weight > 0 has to be finite and >= 0";
+					return ST_INVALID;
+				}
+				any = true;
+				sum_w += (double)w;
+			}
+			clean[(size_t)j * m_ + i] = v;
+		}
+	if (!any) { last_error_ = "weighted NMF: at least one weight has to be > 0"; return ST_INVALID; }
+	hipError_t e = hipMemcpy2DAsync(V_, mpad_ * sizeof(T), clean.data(), m_ * sizeof(T), m_ * sizeof(T), n_, hipMemcpyHostToDevice, stream_);
+	if (e != hipSuccess) return hip_fail(e, "hipMemcpy2DAsync(V)");
+	if (Status st = finish_upload(V_)) return st;      // (V_ is the column-major image; Vt_ its transpose; synchronises)
+	HIPX(hipMemcpy2DAsync(Om_, mpad_ * sizeof(T), Omega, ldo * sizeof(T), m_ * sizeof(T), n_, hipMemcpyHostToDevice, stream_));
+	HIPX(launch_transpose<T>(Om_, mpad_, m_, n_, Omt_, npad_, stream_));
+	HIPX(hipStreamSynchronize(stream_));
+	sum_w_ = sum_w;
+	beta_uploaded_ = true;
+	return ST_OK;
+}
+
 // The dense beta-divergence update's demand on V: every entry finite, and > 0 at beta <= 0 (such a divergence is undefined at 0) or >= 0 at beta > 0
 template <typename T>
 Status Engine<T>::beta_check_values(const T* values, long count, long ld, long rows) {
@@ -642,6 +687,7 @@ Status Engine<T>::beta_check_values(const T* values, long count, long ld, long r
 template <typename T>
 Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const int* b, long nnz, int base) {
 	if (format < 1 || format > 3 || nnz < 0 || (nnz > 0 && (!values || !a || !b))) return ST_INVALID;
+	if (weighted_) { last_error_ = "weighted NMF: sparse input is refused; upload V dense together with its weights (upload_dense_weighted)"; return ST_INVALID; }
 	if (beta_dense_) {
 		// the stored entries are densified (launch_densify below); an unstored entry is a zero, which a divergence with beta <= 0 (Itakura-Saito) does not take
 		beta_uploaded_ = false;
@@ -1188,7 +1234,7 @@ void Engine<T>::finalize_error(bool resolve) {
 		for (int i = 0; i < m_; ++i) { s += (double)h_psN_[i]; d += (double)h_klrow_[i]; }
 		frob2_ = s;
 		frob_ = std::sqrt(s);
-		rmsd_ = frob_ / std::sqrt((double)m_ * (double)n_);
+		rmsd_ = frob_ / std::sqrt(weighted_ ? sum_w_ : (double)m_ * (double)n_);      // (weighted: sum of the weights -- the observed count at 0 / 1 weights)
 		kl_ = d;
 		beta_unresolved_ = false;
 	}
@@ -2450,33 +2496,44 @@ Status Engine<T>::iterate_masked(bool compute_error, bool constant_w) {
 // With a penalty (set_hals_penalties) the denominators carry + l1 + l2 A (l1H, l2H in the H step, l1W, l2W in the W step) and there is no normalisation, HALS's rule:
 // W D^-1 . D H keeps W H but not the penalty terms.  The KL denominators sW_ / sH_ are then the column sums of the panels as they are.
 // Under constant W the H step runs alone; an error iteration then takes its terms from the terms-only form of the W-side launch.
+// Weighted (kernels_beta_weighted.hip): the same skeleton with the images of the weights beside those of V; every denominator is a product (at beta = 1 it is
+// sum_k w(k, o) B(k, :), not colsum(B): no sW_ / sH_, no launch_kl_sums), the normalisation is that of the unweighted engine of the same beta.
 template <typename T>
 Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
-	if (!beta_uploaded_) { last_error_ = "dense divergence update: no V has been uploaded"; return ST_INVALID; }
+	if (!beta_uploaded_) { last_error_ = weighted_ ? "weighted NMF: no V and weights have been uploaded" : "dense divergence update: no V has been uploaded"; return ST_INVALID; }
 	const T eps = std::numeric_limits<T>::epsilon();
 	const double beta = beta_;
-	const bool kl = beta == 1, penalised = prm_.hals_penalised();
+	const bool kl = beta == 1 && !weighted_, penalised = prm_.hals_penalised();      // (kl: the vector denominators of the unweighted beta = 1)
 	const T l1W = (T)prm_.l1W, l1H = (T)prm_.l1H, l2W = (T)prm_.l2W, l2H = (T)prm_.l2H;
 	const int partsH = (int)(npad_ / 128), partsW = (int)(mpad_ / 128);
 	// H step: X = the column-major image (row j of X = column j of V)
 	if (kl && !kl_sw_ready_) { HIPX(launch_panel_rowsum<T>(Wt_, RP_, (int)mpad_, rowsum_part_, sW_, stream_)); kl_sw_ready_ = true; }
 	record_begin();
-	HIPX(launch_beta_fused<T>(V_, mpad_, H_, Wt_, RP_, beta, true, false, eps, betaH_, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0,
-	                          (int)npad_, n_, m_, stream_));
+	if (weighted_)
+		HIPX(launch_beta_fused_weighted<T>(V_, Om_, mpad_, H_, Wt_, RP_, beta, true, false, eps, betaH_, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0,
+		                                   (int)npad_, n_, m_, stream_));
+	else
+		HIPX(launch_beta_fused<T>(V_, mpad_, H_, Wt_, RP_, beta, true, false, eps, betaH_, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0,
+		                          (int)npad_, n_, m_, stream_));
 	record_end();
 	HIPX(launch_beta_update<T>(H_, slabs_, beta_den_, slab_stride_, betaH_.slabs, sW_, RP_, r_, (int)npad_, n_, eps, beta, l1H, l2H, true, (T*)nullptr,
-	                           kl ? rowsum_part_ : (T*)nullptr, (const T*)nullptr, (const T*)nullptr, 0, (T*)nullptr, (T*)nullptr, stream_));
+	                           kl ? rowsum_part_ : (T*)nullptr, (const T*)nullptr, (const T*)nullptr, 0, (T*)nullptr, (T*)nullptr, stream_, weighted_));
 	if (kl) HIPX(launch_kl_sums<T>(rowsum_part_, nullptr, partsH, RP_, sH_, stream_));
 	if (constant_w && !compute_error) return ST_OK;
 	// W step (or, under constant W, its terms-only form): X = the transposed image
 	T* tf = compute_error ? beta_tpart_ : (T*)nullptr;
 	T* td = compute_error ? beta_tpart_ + (long)BETA_MAX_SLABS * mpad_ : (T*)nullptr;
 	record_begin(1);
-	HIPX(launch_beta_fused<T>(Vt_, npad_, Wt_, H_, RP_, beta, !constant_w, compute_error, eps, betaW_, slabs_, beta_den_, slab_stride_, tf, td, mpad_,
-	                          (int)mpad_, m_, n_, stream_));
+	if (weighted_)
+		HIPX(launch_beta_fused_weighted<T>(Vt_, Omt_, npad_, Wt_, H_, RP_, beta, !constant_w, compute_error, eps, betaW_, slabs_, beta_den_, slab_stride_, tf, td, mpad_,
+		                                   (int)mpad_, m_, n_, stream_));
+	else
+		HIPX(launch_beta_fused<T>(Vt_, npad_, Wt_, H_, RP_, beta, !constant_w, compute_error, eps, betaW_, slabs_, beta_den_, slab_stride_, tf, td, mpad_,
+		                          (int)mpad_, m_, n_, stream_));
 	record_end();
 	HIPX(launch_beta_update<T>(Wt_, slabs_, beta_den_, slab_stride_, betaW_.slabs, sH_, RP_, r_, (int)mpad_, m_, eps, beta, l1W, l2W, !constant_w, sumsq_part_,
-	                           kl ? rowsum_part_ : (T*)nullptr, tf, td, mpad_, compute_error ? t_vwh_ : (T*)nullptr, compute_error ? t_kl_ : (T*)nullptr, stream_));
+	                           kl ? rowsum_part_ : (T*)nullptr, tf, td, mpad_, compute_error ? t_vwh_ : (T*)nullptr, compute_error ? t_kl_ : (T*)nullptr, stream_,
+	                           weighted_));
 	if (compute_error) {
 		finalize_error(false);      // (the pinned buffer is about to be reused; an older copy is long complete)
 		HIPX(hipMemcpyAsync(pin_kl_, t_vwh_, sizeof(T) * m_, hipMemcpyDeviceToHost, stream_));
@@ -2491,7 +2548,9 @@ Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
 		kl_sw_ready_ = true;
 		if (!penalised) HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, partsW, stream_));
 	} else if (!penalised) {
-		HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, partsW, stream_));
+		// (the weighted beta = 1: the columns of W normalised, H not rescaled, as above -- without the column sums nobody reads)
+		if (beta == 1) HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, partsW, stream_));
+		else HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, partsW, stream_));
 	}
 	return ST_OK;
 }

@@ -31,6 +31,7 @@ struct AlgorithmParams {
 	double l1W = 0, l1H = 0, l2W = 0, l2H = 0;
 	double dense_compute = 0;   // 1 with divergence = 1: the KL update on a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) instead of over the stored entries
 	double beta_value = 0;      // divergence = 3: the beta of the divergence, any finite value (0 and 1 run the Itakura-Saito and dense KL engines as they are)
+	double weighted = 0;        // 1 on a dense divergence engine: per-entry weights uploaded beside V (upload_dense_weighted; kernels_beta_weighted.hip, docs/DIVERGENCE.md)
 	bool is_masked() const { return missing_values != 0; }
 	// the dense beta-divergence update: Itakura-Saito (beta = 0) and the general form always, generalised KL (beta = 1) with dense_compute
 	bool is_beta_dense() const { return divergence == 2 || divergence == 3 || (divergence == 1 && dense_compute != 0); }
@@ -69,6 +70,13 @@ inline const char* beta_dense_fault(const AlgorithmParams& p, bool is_mu, int r,
 	return nullptr;
 }
 
+// What 'weighted' (nmfamd_params_v4) must satisfy, after beta_dense_fault: nullptr, or why not.
+inline const char* weighted_fault(const AlgorithmParams& p) {
+	if (!(p.weighted == 0 || p.weighted == 1)) return "weighted NMF: 'weighted' has to be 0 or 1";
+	if (p.weighted != 0 && !p.is_beta_dense()) return "weighted NMF: only on a dense divergence engine ('divergence' = 2 or 3, or 1 with 'denseCompute')";
+	return nullptr;
+}
+
 // Status codes shared with nmfgpu_amd.h (NMFAMD_*).
 // ST_VALUE_RANGE: V holds values the split-operand product is not exact for (infinities, NaN, |v| > 2^126, 0 < |v| < 2^-100):
 // the caller recreates the engine with precision = -1 (native fp32 MFMA instructions) -- nmfgpu::compute does that by itself
@@ -103,6 +111,10 @@ public:
 	// V: host, column-major / sparse.  Builds V, Vt and the sorted tr(V^T V) vector.
 	Status upload_dense(const T* V, long ld);
 	Status upload_sparse(int format, const T* values, const int* a, const int* b, long nnz, int base);
+	// weighted engines: V and the weights Omega (m x n, column-major, host); the only upload they take.  Omega finite and >= 0 with one entry > 0; V obeys the rule
+	// of the engine's beta where Omega > 0 and is not looked at (stored as 0) where Omega = 0.  A second call replaces both.
+	Status upload_dense_weighted(const T* V, long ldv, const T* Omega, long ldo);
+	bool is_weighted() const { return weighted_; }
 
 	// W: host m x r (ld), H: host r x n (ld).  Either pointer may be null (leave as is).
 	Status set_factors(const T* W, long ldw, const T* H, long ldh);
@@ -217,7 +229,7 @@ public:
 	int slabs_w() const { return planW_.splits; }
 	// which kernel runs the two big products: 0 fp32 MFMA, 1 bf16-rounded operands, 2 fp32 by exact 3 x bf16 splitting,
 	// 3 fp64 MFMA, 4 VALU fallback kernel (NMFAMD_FORCE_VALU), 5 sparse (SpMM), 6 the fused dense beta-divergence half-step (kernels_beta.hip)
-	int resident_images() const { return sparse_ ? 0 : (one_image_ ? 1 : 2); }
+	int resident_images() const { return sparse_ ? 0 : weighted_ ? 4 : (one_image_ ? 1 : 2); }      // (weighted: V, the weights and both transposes)
 	int product_kernel() const { return beta_dense_ ? 6 : sparse_ ? 5 : bf16_ ? 1 : x3_ ? 2 : !tiled_ ? 4 : (sizeof(T) == 8 ? 3 : 0); }
 	const char* last_error() const { return last_error_; }
 
@@ -333,6 +345,11 @@ private:
 	BetaPlan betaH_, betaW_;
 	T *beta_den_ = nullptr, *beta_tpart_ = nullptr;
 	bool beta_pending_ = false, beta_unresolved_ = false;
+	// ... weighted (prm_.weighted): Om_ / Omt_ are the images of the weights in the layouts of V_ / Vt_, sum_w_ their sum (in double, on the host, at upload: rmsd's
+	// divisor); beta_den_ is allocated at beta = 1 too (the weighted KL denominator is a product)
+	bool weighted_ = false;
+	T *Om_ = nullptr, *Omt_ = nullptr;
+	double sum_w_ = 0;
 	// rank-64 MU fast path: W is kept unnormalised with a pending column scale (kernels_mu64.hip)
 	float *gramW_part_ = nullptr, *gramH_part_ = nullptr, *scale_ = nullptr, *Graw64_ = nullptr;
 	bool w_col_split_ = false;       // V H^T from 128 x 32 workgroups and one slab (narrow column shards, Engine::init)

@@ -539,11 +539,19 @@ hipError_t launch_beta_fused(const T* X, long ldx, const T* A, const T* B, int R
                              int out_pad, int out_valid, int red_valid, hipStream_t stream);
 // The slabs in order, then A(o, c) <- A(o, c) (num / (den + eps + l1 + l2 A(o, c)))^gamma for o < out_valid, c < r and 0 elsewhere (beta = 1: den = dsum(c); otherwise
 // den from den_part; gamma = 1 / (2 - beta) below beta = 1, 1 up to beta = 2, 1 / (beta - 1) above; l1, l2 >= 0, both 0: the unpenalised quotient); sumsq_part / sum_part (optional): [out_pad / 128][RP] sums of squares / sums of the new values; t_frob / t_div (optional, both or none):
-// the error terms of out_pad rows, slabs in order.  update = false: the terms only, A untouched.
+// the error terms of out_pad rows, slabs in order.  update = false: the terms only, A untouched.  weighted: the half-step of launch_beta_fused_weighted -- den
+// from den_part at every beta (dsum is not read).
 template <typename T>
 hipError_t launch_beta_update(T* A, const T* num_part, const T* den_part, long part_stride, int slabs, const T* dsum, int RP, int r, int out_pad, int out_valid, T eps,
                               double beta, T l1, T l2, bool update, T* sumsq_part, T* sum_part, const T* tf_part, const T* td_part, long t_stride, T* t_frob,
-                              T* t_div, hipStream_t stream);
+                              T* t_div, hipStream_t stream, bool weighted = false);
+// The weighted fused launch (kernels_beta_weighted.hip): launch_beta_fused with a second image OX of the layout, leading dimension and padding of X that holds the
+// per-entry weights (>= 0; zero on the padding).  An entry with weight 0 is not there, whatever X holds at it (NaN included); every other entry's contribution to
+// num, den and the two error terms is scaled by its weight.  den_part is written at every beta (beta = 1: den(o, c) = sum_k w(k, o) B(k, c)).
+template <typename T>
+hipError_t launch_beta_fused_weighted(const T* X, const T* OX, long ldx, const T* A, const T* B, int RP, double beta, bool update, bool terms, T eps, const BetaPlan& plan,
+                                      T* num_part, T* den_part, long part_stride, T* tf_part, T* td_part, long t_stride,
+                                      int out_pad, int out_valid, int red_valid, hipStream_t stream);
 
 // ---- the CSR and CSC images of a sparse V built on the device (kernels_sparse_setup.hip) ----------------------------------------
 // flags (one int, zeroed by the caller): bit 0 = an entry outside the matrix or outside every pointer range, bit 1 = pointer array not ascending, bit 2 = the

@@ -452,10 +452,10 @@ template hipError_t launch_beta_fused<double>(const double*, long, const double*
 template <typename T>
 hipError_t launch_beta_update(T* A, const T* num_part, const T* den_part, long part_stride, int slabs, const T* dsum, int RP, int r, int out_pad, int out_valid, T eps,
                               double beta_value, T l1, T l2, bool update, T* sumsq_part, T* sum_part, const T* tf_part, const T* td_part, long t_stride, T* t_frob,
-                              T* t_div, hipStream_t stream) {
+                              T* t_div, hipStream_t stream, bool weighted) {
 	// gamma: scikit-learn's rule (the majorise-minimise exponent of Fevotte & Idier 2011)
 	const double b = (double)(T)beta_value;      // (in the precision of T, as launch_beta_fused takes it)
-	const bool vec_den = b == 1.0;
+	const bool vec_den = b == 1.0 && !weighted;      // (weighted: the beta = 1 denominator is a panel like any other, and the launch is the EXT one at every beta)
 	const double gamma = b < 1.0 ? 1.0 / (2.0 - b) : b <= 2.0 ? 1.0 : 1.0 / (b - 1.0);
 	const int power = gamma == 1.0 ? 0 : gamma == 0.5 ? 1 : 2;
 	const bool penalised = l1 != T(0) || l2 != T(0);
@@ -464,7 +464,7 @@ hipError_t launch_beta_update(T* A, const T* num_part, const T* den_part, long p
 		return hipErrorInvalidValue;
 	if (update && (num_part == nullptr || (vec_den ? dsum == nullptr : den_part == nullptr))) return hipErrorInvalidValue;
 	if ((t_frob == nullptr) != (t_div == nullptr) || (t_frob != nullptr && (tf_part == nullptr || td_part == nullptr)) || (!update && t_frob == nullptr)) return hipErrorInvalidValue;
-	if (penalised || power == 2)
+	if (penalised || power == 2 || weighted)
 		hipLaunchKernelGGL((k_beta_update<T, true>), dim3((unsigned)(out_pad / 128)), dim3(256), 0, stream, A, num_part, den_part, part_stride, slabs, dsum, RP, r, out_valid,
 		                   eps, vec_den ? 1 : 0, power, (T)gamma, penalised ? 1 : 0, l1, l2, update ? 1 : 0, sumsq_part, sum_part, tf_part, td_part, t_stride, t_frob, t_div);
 	else
@@ -473,8 +473,8 @@ hipError_t launch_beta_update(T* A, const T* num_part, const T* den_part, long p
 	return hipGetLastError();
 }
 template hipError_t launch_beta_update<float>(float*, const float*, const float*, long, int, const float*, int, int, int, int, float, double, float, float, bool, float*, float*, const float*,
-                                              const float*, long, float*, float*, hipStream_t);
+                                              const float*, long, float*, float*, hipStream_t, bool);
 template hipError_t launch_beta_update<double>(double*, const double*, const double*, long, int, const double*, int, int, int, int, double, double, double, double, bool, double*, double*,
-                                               const double*, const double*, long, double*, double*, hipStream_t);
+                                               const double*, const double*, long, double*, double*, hipStream_t, bool);
 
 } // namespace nmfamd

@@ -34,6 +34,11 @@ class _ParamsV3(C.Structure):
     _fields_ = [("v2", _ParamsV2), ("beta", C.c_double)]
 
 
+class _ParamsV4(C.Structure):
+    """nmfamd_params_v4: nmfamd_params_v3 (which keeps its size) followed by the fields added since."""
+    _fields_ = [("v3", _ParamsV3), ("weighted", C.c_double)]
+
+
 class _Geometry(C.Structure):
     _fields_ = [("m", C.c_int), ("n", C.c_int), ("r", C.c_int), ("padded_rank", C.c_int),
                 ("padded_m", C.c_long), ("padded_n", C.c_long), ("slabs_h", C.c_int), ("slabs_w", C.c_int),
@@ -64,7 +69,7 @@ class Engine:
     def __init__(self, m: int, n: int, r: int, algorithm: str = "mu", dtype=np.float32, stream: int = 0,
                  lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence: str = "frobenius",
                  sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False,
-                 l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None):
+                 l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None, weighted: bool = False):
         """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V),
         "is" (Itakura-Saito, always dense: every entry of V > 0) or "beta" (the beta-divergence at `beta`, any finite value, always dense: scikit-learn's
         solver="mu" with beta_loss=beta; beta=0.0 and beta=1.0 are the "is" and the dense "kl" engines; beta <= 0 needs every entry of V > 0) --
@@ -74,7 +79,11 @@ class Engine:
         upload (zeros included).  Multiplicative update ("mu") with the Frobenius objective only; implies sparse_compute.
 
         l1_w, l1_h, l2_w, l2_h: the L1 / L2 penalties on W and H of scikit-learn's coordinate descent ("hals", docs/HALS.md) and of its multiplicative update
-        (the dense divergence engines, docs/DIVERGENCE.md); see set_penalties.  sparse_compute=True is available for "mu" and "hals" (rank <= 256)."""
+        (the dense divergence engines, docs/DIVERGENCE.md); see set_penalties.  sparse_compute=True is available for "mu" and "hals" (rank <= 256).
+
+        weighted=True: weighted NMF on a dense divergence engine ("is", "beta", or "kl" with dense_compute) -- the objective is sum w_ij d_beta(v_ij | (W H)_ij) with a
+        matrix of weights >= 0 given to upload(V, weights=...).  A weight of 0 means the entry is missing (V may hold anything there, NaN included); rmsd divides by
+        the sum of the weights (docs/DIVERGENCE.md, "Weighted update")."""
         self._lib = library()
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -87,7 +96,7 @@ class Engine:
         self._ctor = dict(algorithm=algorithm, stream=stream, row_blocks=row_blocks,
                           params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0, "is": 2.0, "beta": 3.0}[divergence],
                                   float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
-                                  float(missing_values), float(dense_compute), float(beta or 0.0)],
+                                  float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted)],
                           penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)])
         self._h = None
         self._lib.nmfamd_engine_frobenius.restype = C.c_double
@@ -99,12 +108,12 @@ class Engine:
 
     def _create(self):
         c = self._ctor
-        p = _ParamsV3(_ParamsV2(_Params(*c["params"][:10]), c["params"][10]), c["params"][11])
+        p = _ParamsV4(_ParamsV3(_ParamsV2(_Params(*c["params"][:10]), c["params"][10]), c["params"][11]), c["params"][12])
         h = C.c_void_p()
         # row_blocks > 1: the padded row count is a multiple of 128 * row_blocks (row-block form of the sharded W step)
         if not hasattr(self._lib, "nmfamd_engine_create_v2"):
             # (NMFAMD_LIBRARY names a build from before the sized entry -- tools/time_beta.py times such a build: it reads the frozen struct only)
-            st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p.v2.base), self.dtype.itemsize,
+            st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p.v3.v2.base), self.dtype.itemsize,
                                                        C.c_void_p(c["stream"]), int(c["row_blocks"]), C.byref(h))
         else:
             st = self._lib.nmfamd_engine_create_v2(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p), C.c_ulong(C.sizeof(p)), self.dtype.itemsize,
@@ -134,12 +143,23 @@ class Engine:
         except Exception:
             pass
 
-    def upload(self, V: np.ndarray):
+    def upload(self, V: np.ndarray, weights: Optional[np.ndarray] = None):
+        """weights (engines created with weighted=True, which take no upload without them): Fortran-ordered, of V's dtype and shape, finite and >= 0 with at
+        least one entry > 0; where a weight is 0, V is not looked at.  A second upload replaces both matrices."""
         V = _f(V)
         if V.dtype != self.dtype:
             raise TypeError(f"V must be {self.dtype}, got {V.dtype}")
         if V.shape != (self.m, self.n):
             raise ValueError(f"V must have shape {(self.m, self.n)}, got {V.shape}")
+        if weights is not None:
+            weights = _f(weights)
+            if weights.dtype != self.dtype:
+                raise TypeError(f"weights must be {self.dtype}, got {weights.dtype}")
+            if weights.shape != (self.m, self.n):
+                raise ValueError(f"weights must have shape {(self.m, self.n)}, got {weights.shape}")
+            self._check(self._lib.nmfamd_engine_upload_dense_weighted(self._h, C.c_void_p(V.ctypes.data), C.c_long(_ld(V)), C.c_void_p(weights.ctypes.data),
+                                                                      C.c_long(_ld(weights))), "upload_dense_weighted")
+            return
         self._upload(lambda: self._lib.nmfamd_engine_upload_dense(self._h, C.c_void_p(V.ctypes.data), C.c_long(_ld(V))), "upload_dense")
 
     def _upload(self, call, what: str):
@@ -641,7 +661,7 @@ def op_beta_half_step(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: int, out_v
     return _beta_half_step(A, B, X, r, out_valid, red_valid, int(beta), form, dsum, force_slabs, None)
 
 
-def _beta_half_step(A, B, X, r, out_valid, red_valid, beta, form, dsum, force_slabs, penalties):
+def _beta_half_step(A, B, X, r, out_valid, red_valid, beta, form, dsum, force_slabs, penalties, Omega=None):
     dt = np.dtype(A.dtype)
     if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
         raise TypeError("float32 or float64")
@@ -660,13 +680,21 @@ def _beta_half_step(A, B, X, r, out_valid, red_valid, beta, form, dsum, force_sl
     sq, sm = np.zeros((max(parts, 1), RP), dt), np.zeros((max(parts, 1), RP), dt)
     slabs = C.c_int(0)
     lib = library()
-    if penalties is None:
+    lead = ()
+    if Omega is not None:
+        Omega = np.ascontiguousarray(Omega, dtype=dt)
+        if Omega.shape != X.shape:
+            raise ValueError("Omega must have the shape of X")
+        lead = (C.c_void_p(Omega.ctypes.data),)
+        fn = lib.nmfamd_op_beta_half_step_weighted_f32 if dt == np.float32 else lib.nmfamd_op_beta_half_step_weighted_f64
+        how = (C.c_double(beta), C.c_double(penalties[0]), C.c_double(penalties[1]))
+    elif penalties is None:
         fn, how = (lib.nmfamd_op_beta_half_step_f32 if dt == np.float32 else lib.nmfamd_op_beta_half_step_f64), (int(beta),)
     else:
         fn = lib.nmfamd_op_beta_half_step_general_f32 if dt == np.float32 else lib.nmfamd_op_beta_half_step_general_f64
         how = (C.c_double(beta), C.c_double(penalties[0]), C.c_double(penalties[1]))
     ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
-    st = fn(ptr(A), ptr(B), ptr(X), C.c_long(X.shape[1]), RP, int(r), out_pad, int(out_valid), red_pad, int(red_valid), *how, int(form), int(force_slabs),
+    st = fn(ptr(A), ptr(B), ptr(X), *lead, C.c_long(X.shape[1]), RP, int(r), out_pad, int(out_valid), red_pad, int(red_valid), *how, int(form), int(force_slabs),
             ptr(d), ptr(tf), ptr(td), ptr(sq), ptr(sm), C.byref(slabs))
     if st != 0:
         raise EngineError(st, "nmfamd_op_beta_half_step")
@@ -679,6 +707,14 @@ def op_beta_half_step_general(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: in
     l2 A))^gamma.  beta = 0 and beta = 1 run the Itakura-Saito and KL launches (dsum: beta = 1 only), every other value the general form, whose `t_div` is the
     beta-divergence of Engine.divergence_value.  The same arguments and the same dict otherwise."""
     return _beta_half_step(A, B, X, r, out_valid, red_valid, float(beta), form, dsum, force_slabs, (float(l1), float(l2)))
+
+
+def op_beta_half_step_weighted(A: np.ndarray, B: np.ndarray, X: np.ndarray, Omega: np.ndarray, r: int, out_valid: int, red_valid: int, beta: float, form: int = 0, *,
+                               l1: float = 0.0, l2: float = 0.0, force_slabs: int = 0):
+    """op_beta_half_step_general with per-entry weights (nmfamd_op_beta_half_step_weighted_*): Omega has the shape of X, weights >= 0 and 0 on the padding.  An entry
+    with weight 0 is not there, whatever X holds at it; num, den and the error terms of every other entry are scaled by its weight.  The denominator is a product
+    at every beta (no dsum).  The same dict."""
+    return _beta_half_step(A, B, X, r, out_valid, red_valid, float(beta), form, None, force_slabs, (float(l1), float(l2)), Omega)
 
 
 def op_hals_normalize(Wt: np.ndarray, H: np.ndarray, sumsq_part: np.ndarray):

@@ -1,12 +1,14 @@
 """Iteration times of the dense beta-divergence update (docs/DIVERGENCE.md) on one strictly positive dense V: the dense KL iteration (--mode dense-kl), the
 Itakura-Saito iteration (--mode is), the general beta-divergence iteration (--mode beta --beta 0.5), and the KL iteration that takes the sparse route for dense
-input (--mode kl: what a build without the dense path runs).  --penalties l1W l1H l2W l2H times the penalised iteration of a dense mode.
+input (--mode kl: what a build without the dense path runs).  --penalties l1W l1H l2W l2H times the penalised iteration of a dense mode.  --weighted F times
+the weighted iteration of a dense mode (docs/DIVERGENCE.md, "Weighted update") with 0 / 1 weights, a share F of them 0 (drawn independently per entry).
+--mode masked --weighted F times the gather-path missing-value engine (docs/MISSING.md: Frobenius, missing_values=True) on the same V and the same 0 / 1 weights.
 
 One process per run: without --child this script starts --runs fresh child processes one after the other and prints their figures with the median and the
 spread.  A child warms up, then times plain iterations and error iterations (wall time per iteration, stream synchronised around each block) and reads the
 event-timed H-side / W-side launches (nmfamd_engine_kernel_timing_read3).  NMFAMD_LIBRARY selects the library, so the same script times another build.
 
-    python tools/time_beta.py --mode dense-kl [--beta 0.5] [--penalties 0 0 0 0] [--rows 10000] [--cols 5000] [--rank 64] [--iters 50] [--warmup 10] [--runs 5]
+    python tools/time_beta.py --mode dense-kl [--beta 0.5] [--penalties 0 0 0 0] [--weighted 0.5] [--rows 10000] [--cols 5000] [--rank 64] [--iters 50] [--warmup 10] [--runs 5]
 """
 import argparse
 import json
@@ -42,11 +44,23 @@ def child(a):
     import nmfgpu_amd as na
     V, W, H = problem(a.rows, a.cols, a.rank)
     kw = {"dense-kl": dict(divergence="kl", dense_compute=True), "is": dict(divergence="is"), "kl": dict(divergence="kl"),
-          "beta": dict(divergence="beta", beta=a.beta)}[a.mode]
+          "beta": dict(divergence="beta", beta=a.beta), "masked": {}}[a.mode]
     if any(a.penalties):
         kw.update(l1_w=a.penalties[0], l1_h=a.penalties[1], l2_w=a.penalties[2], l2_h=a.penalties[3])
-    eng = na.Engine(a.rows, a.cols, a.rank, "mu", **kw)
-    eng.upload(V)
+    if a.mode == "masked":
+        import numpy as np
+        Om = np.random.default_rng(11).random((a.rows, a.cols), dtype=np.float32) >= np.float32(a.weighted if a.weighted is not None else 0.0)
+        V[~Om] = np.nan
+        eng = na.Engine(a.rows, a.cols, a.rank, "mu", missing_values=True)
+        eng.upload(V)
+    elif a.weighted is not None:
+        import numpy as np
+        Om = np.asfortranarray((np.random.default_rng(11).random((a.rows, a.cols), dtype=np.float32) >= np.float32(a.weighted)).astype(np.float32))
+        eng = na.Engine(a.rows, a.cols, a.rank, "mu", weighted=True, **kw)
+        eng.upload(V, weights=Om)
+    else:
+        eng = na.Engine(a.rows, a.cols, a.rank, "mu", **kw)
+        eng.upload(V)
     eng.set_factors(W, H)
     eng.iterate(a.warmup, first_iteration=1, error_every=0, last_iteration=0)
     plain = time_block(eng, a.iters, 0)
@@ -56,7 +70,7 @@ def child(a):
     _, _, idle, (ms_h, ms_w), (c_h, c_w) = eng.kernel_timing_read3()
     eng.kernel_timing(0)
     g = eng.geometry()
-    out = {"mode": a.mode, "beta": a.beta if a.mode == "beta" else None, "penalties": a.penalties, "rows": a.rows, "cols": a.cols, "rank": a.rank, "ms_iteration": plain, "ms_error_iteration": err, "ms_h_launch": ms_h / max(c_h, 1),
+    out = {"mode": a.mode, "beta": a.beta if a.mode == "beta" else None, "penalties": a.penalties, "weighted": a.weighted, "rows": a.rows, "cols": a.cols, "rank": a.rank, "ms_iteration": plain, "ms_error_iteration": err, "ms_h_launch": ms_h / max(c_h, 1),
            "ms_w_launch": ms_w / max(c_w, 1), "ms_idle_event_pair": idle, "product_kernel": g["product_kernel"], "slabs_h": g["slabs_h"], "slabs_w": g["slabs_w"],
            "frobenius": eng.frobenius}
     eng.close()
@@ -65,9 +79,10 @@ def child(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["dense-kl", "is", "kl", "beta"], default="dense-kl")
+    ap.add_argument("--mode", choices=["dense-kl", "is", "kl", "beta", "masked"], default="dense-kl")
     ap.add_argument("--beta", type=float, default=0.5)
     ap.add_argument("--penalties", type=float, nargs=4, default=[0.0, 0.0, 0.0, 0.0])
+    ap.add_argument("--weighted", type=float, default=None, help="share of zero weights of the weighted iteration (0 / 1 weights)")
     ap.add_argument("--rows", type=int, default=10000)
     ap.add_argument("--cols", type=int, default=5000)
     ap.add_argument("--rank", type=int, default=64)
@@ -82,12 +97,14 @@ def main():
     for _ in range(a.runs):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", "--mode", a.mode, "--rows", str(a.rows), "--cols", str(a.cols), "--rank", str(a.rank),
                "--iters", str(a.iters), "--warmup", str(a.warmup), "--beta", str(a.beta), "--penalties", *map(str, a.penalties)]
+        if a.weighted is not None:
+            cmd += ["--weighted", str(a.weighted)]
         line = subprocess.run(cmd, check=True, stdout=subprocess.PIPE, text=True, timeout=600).stdout.strip().splitlines()[-1]
         print(line, flush=True)
         results.append(json.loads(line))
     for key in ("ms_iteration", "ms_error_iteration", "ms_h_launch", "ms_w_launch"):
         vals = [r[key] for r in results]
-        print(f"{a.mode}{' ' + str(a.beta) if a.mode == 'beta' else ''} {a.rows} x {a.cols} r {a.rank} {key}: median {statistics.median(vals):.4f} min {min(vals):.4f} max {max(vals):.4f} ({len(vals)} runs)")
+        print(f"{a.mode}{' ' + str(a.beta) if a.mode == 'beta' else ''}{' weighted ' + str(a.weighted) if a.weighted is not None else ''} {a.rows} x {a.cols} r {a.rank} {key}: median {statistics.median(vals):.4f} min {min(vals):.4f} max {max(vals):.4f} ({len(vals)} runs)")
 
 
 if __name__ == "__main__":
