@@ -81,7 +81,8 @@ typedef struct nmfamd_params_v2 {
 	double dense_compute;   /* Parameter "denseCompute".  1 with base.divergence = 1: the KL update on a dense resident V (docs/DIVERGENCE.md: fused matrix-pipe half-steps,
 	                           kernels_beta.hip) instead of over the stored entries; every entry finite and >= 0, sparse input is densified.  The same iteration as the
 	                           sparse path.  Refused with divergence = 0; not needed with divergence = 2.  The dense divergence engines (this, and divergence = 2)
-	                           are single-GPU: rank <= 256, no sparse_compute / missing_values / bf16 precision, no three-phase / sharded form
+	                           are single-GPU: rank <= 256, no sparse_compute / missing_values / bf16 precision (bf16 product operands under fp32 data are
+	                           nmfamd_params_v5.mixed_precision), no three-phase / sharded form
 	                           (nmfamd_engine_h_step / _w_products / _w_finish and nmfamd_sharded_create return NMFAMD_INVALID_ARGUMENT); constant_w is available.
 	                           An upload that breaks the value rule returns NMFAMD_INVALID_ARGUMENT with nmfamd_engine_last_error set */
 } nmfamd_params_v2;
@@ -98,8 +99,8 @@ typedef struct nmfamd_params_v3 {
 	                           refused.  The limits of the dense divergence engines (nmfamd_params_v2.dense_compute) apply */
 } nmfamd_params_v3;
 
-/* nmfamd_params_v3 followed by what has been added since (v2 and v3 keep their sizes).  nmfamd_engine_create_v2 reads min(params_size, sizeof(nmfamd_params_v4))
- * bytes and takes the rest as 0. */
+/* nmfamd_params_v3 followed by what has been added since (v2 and v3 keep their sizes).  nmfamd_engine_create_v2 takes it with its size (see
+ * nmfamd_params_v5). */
 typedef struct nmfamd_params_v4 {
 	nmfamd_params_v3 v3;
 	double weighted;        /* 0 or 1.  1: weighted NMF (docs/DIVERGENCE.md, "Weighted update") -- the objective is sum_ij w_ij d_beta(v_ij | (W H)_ij) with a matrix of
@@ -108,6 +109,19 @@ typedef struct nmfamd_params_v4 {
 	                           beta = 2).  Only on a dense divergence engine: v3.v2.base.divergence = 2 or 3, or 1 with dense_compute; any other value, and weighted = 1
 	                           on any other engine, is refused at creation.  The limits of the dense divergence engines apply */
 } nmfamd_params_v4;
+
+/* nmfamd_params_v4 followed by what has been added since (v2 to v4 keep their sizes).  nmfamd_engine_create_v2 reads min(params_size, sizeof(nmfamd_params_v5))
+ * bytes and takes the rest as 0. */
+typedef struct nmfamd_params_v5 {
+	nmfamd_params_v4 v4;
+	double mixed_precision; /* 0 or 1.  1: the mixed-precision form of the dense divergence update (docs/DIVERGENCE.md, "Mixed precision"; kernels_beta_bf16.hip) -- the
+	                           operands of the fused half-step's two products (the panels W and H as they are staged, and Q = V .* P^(beta - 2), R = P^(beta - 1) after
+	                           the element-wise map) are rounded to bf16, round to nearest even, and multiplied on the bf16 matrix instructions; V, P + eps, the map,
+	                           the error terms, every accumulation and the master panels stay fp32.  Only on a single-precision dense divergence engine
+	                           (divergence = 2 or 3, or 1 with dense_compute) without weights: any other value, a double-precision engine, weighted = 1 with it, and
+	                           mixed_precision = 1 on any other engine are refused at creation.  base.precision = 1 stays refused on these engines (it would mean V
+	                           itself stored in bf16).  The limits of the dense divergence engines apply */
+} nmfamd_params_v5;
 
 typedef struct nmfamd_engine nmfamd_engine;  /* opaque; owns every device buffer of one factorisation */
 
@@ -200,7 +214,7 @@ typedef struct nmfamd_geometry {
 	int product_kernel;    /* 0 fp32 MFMA, 1 bf16-rounded operands, 2 fp32 by exact 3 x bf16 operand splitting, 3 fp64 MFMA,
 	                          4 VALU kernel (NMFAMD_FORCE_VALU), 5 sparse SpMM, 6 the fused dense beta-divergence half-step (kernels_beta.hip: slabs_h / slabs_w
 	                          are then the reduction slabs of its two launches, which fix the summation order; resident_images = 2, or 4 on a weighted engine;
-	                          kl_blocks_* = 0) */
+	                          kl_blocks_* = 0), 7 the same half-step with bf16 operands (nmfamd_params_v5.mixed_precision, kernels_beta_bf16.hip; resident_images = 2) */
 	int resident_images;   /* dense images of V kept in HBM: 2 (V and V^T, each streamed along its output index), 1 (only V: W^T V
 	                          reads it along the reduction index; chosen when two would not fit, or by NMFAMD_ONE_IMAGE), 0 sparse, 4 a weighted dense divergence
 	                          engine (V, the weights and the transposes of both) */
@@ -433,6 +447,11 @@ NMFAMD_API int nmfamd_op_beta_half_step_general_f32(float* A, const float* B, co
 NMFAMD_API int nmfamd_op_beta_half_step_general_f64(double* A, const double* B, const double* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad,
                                                     int red_valid, double beta, double l1, double l2, int form, int force_slabs, const double* dsum, double* t_frob,
                                                     double* t_div, double* sumsq_part, double* sum_part, int* slabs);
+/* The mixed-precision half-step (kernels_beta_bf16.hip; docs/DIVERGENCE.md, "Mixed precision"): nmfamd_op_beta_half_step_general_f32 with the fused launch whose
+ * product operands are rounded to bf16; the update launch is the same.  Single precision only. */
+NMFAMD_API int nmfamd_op_beta_half_step_mixed_f32(float* A, const float* B, const float* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad,
+                                                  int red_valid, double beta, double l1, double l2, int form, int force_slabs, const float* dsum, float* t_frob,
+                                                  float* t_div, float* sumsq_part, float* sum_part, int* slabs);
 /* The weighted half-step (kernels_beta_weighted.hip; docs/DIVERGENCE.md, "Weighted update"): nmfamd_op_beta_half_step_general_* with Omega, an array of the shape
  * and leading dimension of X that holds the weights (>= 0; 0 on the padding).  An entry with weight 0 is not there, whatever X holds at it.  The denominator is a
  * product at every beta: dsum is not used. */

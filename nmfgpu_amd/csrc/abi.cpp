@@ -246,6 +246,16 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		return ResultType::ErrorInvalidArgument;
 	}
 	{
+		// "mixedPrecision" = 1 (docs/DIVERGENCE.md, "Mixed precision"): the dense divergence update with the operands of its products rounded to bf16; single
+		// precision only ("precision" = 1 stays refused there)
+		const int idx = parameter_index(d.parameters, d.numParameters, "mixedPrecision");
+		if (idx >= 0) prm.mixed_precision = d.parameters[idx].value;
+		if (const char* why = nmfamd::mixed_precision_fault(prm, sizeof(T) == 4)) {
+			log_error((std::string("[ERROR] ") + why).c_str());
+			return ResultType::ErrorInvalidArgument;
+		}
+	}
+	{
 		// "l1W", "l1H", "l2W", "l2H": the penalties of scikit-learn's coordinate descent on the HALS sweeps (docs/HALS.md) and of its multiplicative update on the
 		// dense divergence updates (docs/DIVERGENCE.md: "divergence" 2, 3, and 1 with "denseCompute"); absent = 0
 		struct { const char* name; double* slot; } pen[] = {{"l1W", &prm.l1W}, {"l1H", &prm.l1H}, {"l2W", &prm.l2W}, {"l2H", &prm.l2H}};

@@ -169,9 +169,10 @@ int nmfamd_engine_create_blocks(int m, int n, int r, int algorithm, const nmfamd
 
 int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* params_sized, unsigned long params_size, int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out) {
 	if (params_sized != nullptr && params_size < sizeof(nmfamd_params)) return NMFAMD_INVALID_ARGUMENT;
-	nmfamd_params_v4 v4;
-	std::memset(&v4, 0, sizeof(v4));
-	if (params_sized != nullptr) std::memcpy(&v4, params_sized, params_size < sizeof(v4) ? (size_t)params_size : sizeof(v4));
+	nmfamd_params_v5 v5;
+	std::memset(&v5, 0, sizeof(v5));
+	if (params_sized != nullptr) std::memcpy(&v5, params_sized, params_size < sizeof(v5) ? (size_t)params_size : sizeof(v5));
+	const nmfamd_params_v4& v4 = v5.v4;
 	const nmfamd_params_v3& v3 = v4.v3;
 	const nmfamd_params_v2& v2 = v3.v2;
 	const nmfamd_params* params = params_sized != nullptr ? &v2.base : nullptr;
@@ -180,7 +181,7 @@ int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* para
 	g_create_error.clear();
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	AlgorithmParams p;
-	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; p.dense_compute = v2.dense_compute; p.beta_value = v3.beta; p.weighted = v4.weighted; }
+	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; p.dense_compute = v2.dense_compute; p.beta_value = v3.beta; p.weighted = v4.weighted; p.mixed_precision = v5.mixed_precision; }
 	nmfamd_engine* e = new (std::nothrow) nmfamd_engine();
 	if (!e) return NMFAMD_NO_HOST_MEMORY;
 	e->elem_bytes = elem_bytes;
@@ -890,8 +891,8 @@ int op_hals_normalize(T* Wt, int RP, int mpad, T* H, int npad, const T* sumsq_pa
 template <typename T>
 int op_beta_half_step(T* A, const T* B, const T* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid, double beta_value, double l1d,
                       double l2d, int form, int force_slabs, const T* dsum, T* t_frob, T* t_div, T* sumsq_part, T* sum_part, int* slabs, const T* Omega = nullptr,
-                      bool weighted = false) {
-	// weighted: the half-step of kernels_beta_weighted.hip with Omega, an array like X (dsum is not used)
+                      bool weighted = false, bool mixed = false) {
+	// weighted: the half-step of kernels_beta_weighted.hip with Omega, an array like X (dsum is not used); mixed (float only): the fused launch of kernels_beta_bf16.hip
 	const bool update = form == 0 || form == 1, terms = form == 1 || form == 2;
 	if (weighted && !Omega) return NMFAMD_INVALID_ARGUMENT;
 	const double beta = (double)(T)beta_value;      // (in the precision of T, as the launchers take it)
@@ -927,7 +928,13 @@ int op_beta_half_step(T* A, const T* B, const T* X, long ldx, int RP, int r, int
 	T* of = terms ? (T*)dOut.p : nullptr;
 	T* od = terms ? (T*)dOut.p + out_pad : nullptr;
 	const T eps = std::numeric_limits<T>::epsilon();
-	if ((weighted ? launch_beta_fused_weighted<T>((const T*)dX.p, (const T*)dO.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update, terms, eps, plan, (T*)dNum.p,
+	if (mixed) {
+		if constexpr (sizeof(T) == 4) {
+			if (launch_beta_fused_bf16((const T*)dX.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update, terms, eps, plan, (T*)dNum.p, (T*)dDen.p, part_stride, tf, td,
+			                           out_pad, out_pad, out_valid, red_valid, nullptr) != hipSuccess)
+				return NMFAMD_HIP_ERROR;
+		} else return NMFAMD_INVALID_ARGUMENT;
+	} else if ((weighted ? launch_beta_fused_weighted<T>((const T*)dX.p, (const T*)dO.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update, terms, eps, plan, (T*)dNum.p,
 	                                              (T*)dDen.p, part_stride, tf, td, out_pad, out_pad, out_valid, red_valid, nullptr)
 	              : launch_beta_fused<T>((const T*)dX.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update, terms, eps, plan, (T*)dNum.p, (T*)dDen.p, part_stride, tf, td,
 	                                     out_pad, out_pad, out_valid, red_valid, nullptr)) != hipSuccess)
@@ -968,6 +975,13 @@ int nmfamd_op_beta_half_step_general_f64(double* A, const double* B, const doubl
                                          double beta, double l1, double l2, int form, int force_slabs, const double* dsum, double* t_frob, double* t_div,
                                          double* sumsq_part, double* sum_part, int* slabs) {
 	return op_beta_half_step<double>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, beta, l1, l2, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs);
+}
+
+int nmfamd_op_beta_half_step_mixed_f32(float* A, const float* B, const float* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid,
+                                       double beta, double l1, double l2, int form, int force_slabs, const float* dsum, float* t_frob, float* t_div,
+                                       float* sumsq_part, float* sum_part, int* slabs) {
+	return op_beta_half_step<float>(A, B, X, ldx, RP, r, out_pad, out_valid, red_pad, red_valid, beta, l1, l2, form, force_slabs, dsum, t_frob, t_div, sumsq_part, sum_part, slabs,
+	                                nullptr, false, true);
 }
 
 int nmfamd_op_beta_half_step_weighted_f32(float* A, const float* B, const float* X, const float* Omega, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad,

@@ -181,7 +181,9 @@ Status Engine<T>::allocate() {
 	if (const char* why = beta_dense_fault(prm_, alg_ == ALG_MU, r_, row_blocks_)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = weighted_fault(prm_)) { last_error_ = why; return ST_INVALID; }
 	beta_dense_ = prm_.is_beta_dense();
+	if (const char* why = mixed_precision_fault(prm_, sizeof(T) == 4)) { last_error_ = why; return ST_INVALID; }
 	weighted_ = prm_.weighted != 0;
+	mixed_ = prm_.mixed_precision != 0;
 	if (beta_dense_) {
 		// beta in the engine's precision, as the penalties: a value that rounds to 0 or 1 there IS the Itakura-Saito or the dense KL engine
 		beta_ = (double)(T)prm_.beta();
@@ -2498,6 +2500,18 @@ Status Engine<T>::iterate_masked(bool compute_error, bool constant_w) {
 // Under constant W the H step runs alone; an error iteration then takes its terms from the terms-only form of the W-side launch.
 // Weighted (kernels_beta_weighted.hip): the same skeleton with the images of the weights beside those of V; every denominator is a product (at beta = 1 it is
 // sum_k w(k, o) B(k, :), not colsum(B): no sW_ / sH_, no launch_kl_sums), the normalisation is that of the unweighted engine of the same beta.
+// Mixed precision (kernels_beta_bf16.hip): the two fused launches take bf16 operands; the update launches, the sums and the normalisation are the fp32 engine's.
+// (the mixed-precision launch exists in fp32 only; allocate() refuses the switch on a double engine, so the other overload is never reached)
+static hipError_t beta_fused_mixed(const float* X, long ldx, const float* A, const float* B, int RP, double beta, bool update, bool terms, float eps, const BetaPlan& plan,
+                                   float* num_part, float* den_part, long part_stride, float* tf_part, float* td_part, long t_stride, int out_pad, int out_valid,
+                                   int red_valid, hipStream_t stream) {
+	return launch_beta_fused_bf16(X, ldx, A, B, RP, beta, update, terms, eps, plan, num_part, den_part, part_stride, tf_part, td_part, t_stride, out_pad, out_valid, red_valid, stream);
+}
+static hipError_t beta_fused_mixed(const double*, long, const double*, const double*, int, double, bool, bool, double, const BetaPlan&, double*, double*, long, double*, double*,
+                                   long, int, int, int, hipStream_t) {
+	return hipErrorInvalidValue;
+}
+
 template <typename T>
 Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
 	if (!beta_uploaded_) { last_error_ = weighted_ ? "weighted NMF: no V and weights have been uploaded" : "dense divergence update: no V has been uploaded"; return ST_INVALID; }
@@ -2512,6 +2526,8 @@ Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
 	if (weighted_)
 		HIPX(launch_beta_fused_weighted<T>(V_, Om_, mpad_, H_, Wt_, RP_, beta, true, false, eps, betaH_, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0,
 		                                   (int)npad_, n_, m_, stream_));
+	else if (mixed_)
+		HIPX(beta_fused_mixed(V_, mpad_, H_, Wt_, RP_, beta, true, false, eps, betaH_, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0, (int)npad_, n_, m_, stream_));
 	else
 		HIPX(launch_beta_fused<T>(V_, mpad_, H_, Wt_, RP_, beta, true, false, eps, betaH_, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0,
 		                          (int)npad_, n_, m_, stream_));
@@ -2527,6 +2543,8 @@ Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
 	if (weighted_)
 		HIPX(launch_beta_fused_weighted<T>(Vt_, Omt_, npad_, Wt_, H_, RP_, beta, !constant_w, compute_error, eps, betaW_, slabs_, beta_den_, slab_stride_, tf, td, mpad_,
 		                                   (int)mpad_, m_, n_, stream_));
+	else if (mixed_)
+		HIPX(beta_fused_mixed(Vt_, npad_, Wt_, H_, RP_, beta, !constant_w, compute_error, eps, betaW_, slabs_, beta_den_, slab_stride_, tf, td, mpad_, (int)mpad_, m_, n_, stream_));
 	else
 		HIPX(launch_beta_fused<T>(Vt_, npad_, Wt_, H_, RP_, beta, !constant_w, compute_error, eps, betaW_, slabs_, beta_den_, slab_stride_, tf, td, mpad_,
 		                          (int)mpad_, m_, n_, stream_));

@@ -32,6 +32,7 @@ struct AlgorithmParams {
 	double dense_compute = 0;   // 1 with divergence = 1: the KL update on a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) instead of over the stored entries
 	double beta_value = 0;      // divergence = 3: the beta of the divergence, any finite value (0 and 1 run the Itakura-Saito and dense KL engines as they are)
 	double weighted = 0;        // 1 on a dense divergence engine: per-entry weights uploaded beside V (upload_dense_weighted; kernels_beta_weighted.hip, docs/DIVERGENCE.md)
+	double mixed_precision = 0; // 1 on a dense divergence fp32 engine: the operands of the fused half-step's products rounded to bf16 (kernels_beta_bf16.hip, docs/DIVERGENCE.md)
 	bool is_masked() const { return missing_values != 0; }
 	// the dense beta-divergence update: Itakura-Saito (beta = 0) and the general form always, generalised KL (beta = 1) with dense_compute
 	bool is_beta_dense() const { return divergence == 2 || divergence == 3 || (divergence == 1 && dense_compute != 0); }
@@ -74,6 +75,17 @@ inline const char* beta_dense_fault(const AlgorithmParams& p, bool is_mu, int r,
 inline const char* weighted_fault(const AlgorithmParams& p) {
 	if (!(p.weighted == 0 || p.weighted == 1)) return "weighted NMF: 'weighted' has to be 0 or 1";
 	if (p.weighted != 0 && !p.is_beta_dense()) return "weighted NMF: only on a dense divergence engine ('divergence' = 2 or 3, or 1 with 'denseCompute')";
+	return nullptr;
+}
+
+// What 'mixedPrecision' (nmfamd_params_v5) must satisfy, after beta_dense_fault and weighted_fault: nullptr, or why not.  ('precision' = 1 on a dense divergence
+// engine stays refused by beta_dense_fault: there it would mean V itself stored in bf16.)
+inline const char* mixed_precision_fault(const AlgorithmParams& p, bool fp32) {
+	if (!(p.mixed_precision == 0 || p.mixed_precision == 1)) return "mixed precision: 'mixedPrecision' has to be 0 or 1";
+	if (p.mixed_precision == 0) return nullptr;
+	if (!p.is_beta_dense()) return "mixed precision: only on a dense divergence engine ('divergence' = 2 or 3, or 1 with 'denseCompute')";
+	if (!fp32) return "mixed precision: single-precision engines only";
+	if (p.weighted != 0) return "mixed precision: does not combine with 'weighted' (the weighted kernels have no bf16 form)";
 	return nullptr;
 }
 
@@ -230,7 +242,7 @@ public:
 	// which kernel runs the two big products: 0 fp32 MFMA, 1 bf16-rounded operands, 2 fp32 by exact 3 x bf16 splitting,
 	// 3 fp64 MFMA, 4 VALU fallback kernel (NMFAMD_FORCE_VALU), 5 sparse (SpMM), 6 the fused dense beta-divergence half-step (kernels_beta.hip)
 	int resident_images() const { return sparse_ ? 0 : weighted_ ? 4 : (one_image_ ? 1 : 2); }      // (weighted: V, the weights and both transposes)
-	int product_kernel() const { return beta_dense_ ? 6 : sparse_ ? 5 : bf16_ ? 1 : x3_ ? 2 : !tiled_ ? 4 : (sizeof(T) == 8 ? 3 : 0); }
+	int product_kernel() const { return beta_dense_ ? (mixed_ ? 7 : 6) : sparse_ ? 5 : bf16_ ? 1 : x3_ ? 2 : !tiled_ ? 4 : (sizeof(T) == 8 ? 3 : 0); }
 	const char* last_error() const { return last_error_; }
 
 	// test access to device intermediates (panel layout, host copies)
@@ -348,6 +360,8 @@ private:
 	// ... weighted (prm_.weighted): Om_ / Omt_ are the images of the weights in the layouts of V_ / Vt_, sum_w_ their sum (in double, on the host, at upload: rmsd's
 	// divisor); beta_den_ is allocated at beta = 1 too (the weighted KL denominator is a product)
 	bool weighted_ = false;
+	// ... mixed precision (prm_.mixed_precision, fp32 only): iterate_beta launches launch_beta_fused_bf16 in place of launch_beta_fused, nothing else changes
+	bool mixed_ = false;
 	T *Om_ = nullptr, *Omt_ = nullptr;
 	double sum_w_ = 0;
 	// rank-64 MU fast path: W is kept unnormalised with a pending column scale (kernels_mu64.hip)

@@ -552,6 +552,12 @@ template <typename T>
 hipError_t launch_beta_fused_weighted(const T* X, const T* OX, long ldx, const T* A, const T* B, int RP, double beta, bool update, bool terms, T eps, const BetaPlan& plan,
                                       T* num_part, T* den_part, long part_stride, T* tf_part, T* td_part, long t_stride,
                                       int out_pad, int out_valid, int red_valid, hipStream_t stream);
+// The mixed-precision fused launch (kernels_beta_bf16.hip; fp32 engines only): launch_beta_fused<float> -- the same arguments, the same plan, the same partial panels --
+// with the operands of both products (A, B, and Q, R after the element-wise map) rounded to bf16, round to nearest even, on v_mfma_f32_32x32x16_bf16.  X, P + eps, the
+// map, the error terms and every accumulation stay fp32; launch_beta_update<float> follows it unchanged.
+hipError_t launch_beta_fused_bf16(const float* X, long ldx, const float* A, const float* B, int RP, double beta, bool update, bool terms, float eps, const BetaPlan& plan,
+                                  float* num_part, float* den_part, long part_stride, float* tf_part, float* td_part, long t_stride,
+                                  int out_pad, int out_valid, int red_valid, hipStream_t stream);
 
 // ---- the CSR and CSC images of a sparse V built on the device (kernels_sparse_setup.hip) ----------------------------------------
 // flags (one int, zeroed by the caller): bit 0 = an entry outside the matrix or outside every pointer range, bit 1 = pointer array not ascending, bit 2 = the

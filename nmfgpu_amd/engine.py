@@ -39,6 +39,11 @@ class _ParamsV4(C.Structure):
     _fields_ = [("v3", _ParamsV3), ("weighted", C.c_double)]
 
 
+class _ParamsV5(C.Structure):
+    """nmfamd_params_v5: nmfamd_params_v4 (which keeps its size) followed by the fields added since."""
+    _fields_ = [("v4", _ParamsV4), ("mixed_precision", C.c_double)]
+
+
 class _Geometry(C.Structure):
     _fields_ = [("m", C.c_int), ("n", C.c_int), ("r", C.c_int), ("padded_rank", C.c_int),
                 ("padded_m", C.c_long), ("padded_n", C.c_long), ("slabs_h", C.c_int), ("slabs_w", C.c_int),
@@ -69,7 +74,7 @@ class Engine:
     def __init__(self, m: int, n: int, r: int, algorithm: str = "mu", dtype=np.float32, stream: int = 0,
                  lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence: str = "frobenius",
                  sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False,
-                 l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None, weighted: bool = False):
+                 l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None, weighted: bool = False, mixed_precision: bool = False):
         """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V),
         "is" (Itakura-Saito, always dense: every entry of V > 0) or "beta" (the beta-divergence at `beta`, any finite value, always dense: scikit-learn's
         solver="mu" with beta_loss=beta; beta=0.0 and beta=1.0 are the "is" and the dense "kl" engines; beta <= 0 needs every entry of V > 0) --
@@ -83,7 +88,11 @@ class Engine:
 
         weighted=True: weighted NMF on a dense divergence engine ("is", "beta", or "kl" with dense_compute) -- the objective is sum w_ij d_beta(v_ij | (W H)_ij) with a
         matrix of weights >= 0 given to upload(V, weights=...).  A weight of 0 means the entry is missing (V may hold anything there, NaN included); rmsd divides by
-        the sum of the weights (docs/DIVERGENCE.md, "Weighted update")."""
+        the sum of the weights (docs/DIVERGENCE.md, "Weighted update").
+
+        mixed_precision=True: a float32 dense divergence engine multiplies with bf16 operands (W, H and the mapped V .* P^(beta - 2), P^(beta - 1) rounded to
+        nearest even; V, the element-wise map, every sum and the factors themselves stay float32) -- faster, with a relative error of a few 2^-9 per update
+        (docs/DIVERGENCE.md, "Mixed precision").  Not with float64, not with weighted=True; precision="bf16" stays refused on these engines."""
         self._lib = library()
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -96,7 +105,7 @@ class Engine:
         self._ctor = dict(algorithm=algorithm, stream=stream, row_blocks=row_blocks,
                           params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0, "is": 2.0, "beta": 3.0}[divergence],
                                   float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
-                                  float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted)],
+                                  float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted), float(mixed_precision)],
                           penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)])
         self._h = None
         self._lib.nmfamd_engine_frobenius.restype = C.c_double
@@ -108,12 +117,12 @@ class Engine:
 
     def _create(self):
         c = self._ctor
-        p = _ParamsV4(_ParamsV3(_ParamsV2(_Params(*c["params"][:10]), c["params"][10]), c["params"][11]), c["params"][12])
+        p = _ParamsV5(_ParamsV4(_ParamsV3(_ParamsV2(_Params(*c["params"][:10]), c["params"][10]), c["params"][11]), c["params"][12]), c["params"][13])
         h = C.c_void_p()
         # row_blocks > 1: the padded row count is a multiple of 128 * row_blocks (row-block form of the sharded W step)
         if not hasattr(self._lib, "nmfamd_engine_create_v2"):
             # (NMFAMD_LIBRARY names a build from before the sized entry -- tools/time_beta.py times such a build: it reads the frozen struct only)
-            st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p.v3.v2.base), self.dtype.itemsize,
+            st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p.v4.v3.v2.base), self.dtype.itemsize,
                                                        C.c_void_p(c["stream"]), int(c["row_blocks"]), C.byref(h))
         else:
             st = self._lib.nmfamd_engine_create_v2(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p), C.c_ulong(C.sizeof(p)), self.dtype.itemsize,
@@ -661,10 +670,12 @@ def op_beta_half_step(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: int, out_v
     return _beta_half_step(A, B, X, r, out_valid, red_valid, int(beta), form, dsum, force_slabs, None)
 
 
-def _beta_half_step(A, B, X, r, out_valid, red_valid, beta, form, dsum, force_slabs, penalties, Omega=None):
+def _beta_half_step(A, B, X, r, out_valid, red_valid, beta, form, dsum, force_slabs, penalties, Omega=None, mixed=False):
     dt = np.dtype(A.dtype)
     if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
         raise TypeError("float32 or float64")
+    if mixed and dt != np.dtype(np.float32):
+        raise TypeError("the mixed-precision half-step is float32 only")
     A = np.array(A, dtype=dt, order="C"); B = np.ascontiguousarray(B, dtype=dt); X = np.ascontiguousarray(X, dtype=dt)
     out_pad, RP = A.shape
     red_pad = B.shape[0]
@@ -688,6 +699,9 @@ def _beta_half_step(A, B, X, r, out_valid, red_valid, beta, form, dsum, force_sl
         lead = (C.c_void_p(Omega.ctypes.data),)
         fn = lib.nmfamd_op_beta_half_step_weighted_f32 if dt == np.float32 else lib.nmfamd_op_beta_half_step_weighted_f64
         how = (C.c_double(beta), C.c_double(penalties[0]), C.c_double(penalties[1]))
+    elif mixed:
+        fn = lib.nmfamd_op_beta_half_step_mixed_f32
+        how = (C.c_double(beta), C.c_double(penalties[0]), C.c_double(penalties[1]))
     elif penalties is None:
         fn, how = (lib.nmfamd_op_beta_half_step_f32 if dt == np.float32 else lib.nmfamd_op_beta_half_step_f64), (int(beta),)
     else:
@@ -707,6 +721,13 @@ def op_beta_half_step_general(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: in
     l2 A))^gamma.  beta = 0 and beta = 1 run the Itakura-Saito and KL launches (dsum: beta = 1 only), every other value the general form, whose `t_div` is the
     beta-divergence of Engine.divergence_value.  The same arguments and the same dict otherwise."""
     return _beta_half_step(A, B, X, r, out_valid, red_valid, float(beta), form, dsum, force_slabs, (float(l1), float(l2)))
+
+
+def op_beta_half_step_mixed(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: int, out_valid: int, red_valid: int, beta: float, form: int = 0, *,
+                            l1: float = 0.0, l2: float = 0.0, dsum: Optional[np.ndarray] = None, force_slabs: int = 0):
+    """op_beta_half_step_general (float32 only) with the mixed-precision fused launch (nmfamd_op_beta_half_step_mixed_f32): A, B and the mapped Q, R are rounded to
+    bf16 as operands of the two products; X, the map, every sum and the update stay float32 (docs/DIVERGENCE.md, "Mixed precision").  The same arguments and dict."""
+    return _beta_half_step(A, B, X, r, out_valid, red_valid, float(beta), form, dsum, force_slabs, (float(l1), float(l2)), mixed=True)
 
 
 def op_beta_half_step_weighted(A: np.ndarray, B: np.ndarray, X: np.ndarray, Omega: np.ndarray, r: int, out_valid: int, red_valid: int, beta: float, form: int = 0, *,
