@@ -123,6 +123,21 @@ typedef struct nmfamd_params_v5 {
 	                           itself stored in bf16).  The limits of the dense divergence engines apply */
 } nmfamd_params_v5;
 
+/* nmfamd_params_v5 followed by what has been added since (v2 to v5 keep their sizes).  nmfamd_engine_create_v2 reads min(params_size, sizeof(nmfamd_params_v6))
+ * bytes and takes the rest as 0: a v5-sized struct gives the engine it always gave. */
+typedef struct nmfamd_params_v6 {
+	nmfamd_params_v5 v5;
+	double batch_size;      /* 0, or a positive multiple of 128.  > 0: the minibatch (online) form of the dense divergence update (docs/DIVERGENCE.md, "Minibatch
+	                           update"; scikit-learn's MiniBatchNMF).  One iteration is one pass over the column ranges [0, b), [b, 2 b), ... of V in order (the last one
+	                           the remainder): the columns of H in the batch take the ordinary multiplicative step, W the online one from numerator and denominator
+	                           panels accumulated over the batches.  No normalisation; the errors of an error iteration are those of (W, H) AFTER the pass.  Only on a
+	                           dense divergence engine (divergence = 2 or 3, or 1 with dense_compute), single or double precision, with or without penalties and
+	                           mixed_precision; not with weighted = 1; nmfamd_engine_iterate refuses constant_w on it.  Any other value is refused at creation */
+	double forget_factor;   /* in [0, 1], taken literally: rho = forget_factor^(min(batch_size, n) / n) scales the accumulated panels before a step adds its own
+	                           (scikit-learn's default is 0.7; 0: every step keeps only its own numerator and denominator).  A non-zero value without a batch_size is
+	                           refused at creation */
+} nmfamd_params_v6;
+
 typedef struct nmfamd_engine nmfamd_engine;  /* opaque; owns every device buffer of one factorisation */
 
 /* Number of visible HIP devices (0 when there is none), and the library's build description. */
@@ -137,7 +152,7 @@ NMFAMD_API const char* nmfamd_engine_last_error(const nmfamd_engine* e);
  * every kernel and copy of this engine is issued on it. */
 NMFAMD_API int nmfamd_engine_create(int m, int n, int r, int algorithm, const nmfamd_params* params,
                                     int elem_bytes, void* stream, nmfamd_engine** out);
-/* The same with the sized, extended parameter struct (nmfamd_params_v2, _v3 or _v4; params_size = sizeof of the caller's struct, at least
+/* The same with the sized, extended parameter struct (nmfamd_params_v2 ... _v6; params_size = sizeof of the caller's struct, at least
  * sizeof(nmfamd_params) unless params is NULL) and the row blocks of nmfamd_engine_create_blocks (1: none). */
 NMFAMD_API int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* params, unsigned long params_size,
                                        int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out);
@@ -461,6 +476,16 @@ NMFAMD_API int nmfamd_op_beta_half_step_weighted_f32(float* A, const float* B, c
 NMFAMD_API int nmfamd_op_beta_half_step_weighted_f64(double* A, const double* B, const double* X, const double* Omega, long ldx, int RP, int r, int out_pad, int out_valid,
                                                      int red_pad, int red_valid, double beta, double l1, double l2, int form, int force_slabs, const double* dsum,
                                                      double* t_frob, double* t_div, double* sumsq_part, double* sum_part, int* slabs);
+/* The update launch of the minibatch update on caller-built arrays (kernels_beta_online.hip; docs/DIVERGENCE.md, "Minibatch update"): P [out_pad][RP] the panel,
+ * num_part / den_part [slabs][out_pad][RP] the slabs' partial numerators / denominators (added in slab order; den_part unused at beta = 1, where dsum holds the RP
+ * denominators), den = their sum + eps + l1 + l2 P.  online = 0: P <- P (num / den)^gamma.  online = 1: Aacc <- rho Aacc + P^(1 / gamma) num, Bacc <- rho Bacc + den,
+ * P <- (Aacc / Bacc)^gamma (Aacc, Bacc: [out_pad][RP], replaced on the valid coordinates; 0 <= rho <= 1).  flush = 1: new values below eps become 0.  Rows
+ * o >= out_valid and coordinates c >= r of P are 0 afterwards.  sum_part (optional, (out_pad / 16) * RP values): the sums of the new values over each 16 rows.
+ * out_pad a multiple of 128, RP 64 / 128 / 256, at most 16 slabs. */
+NMFAMD_API int nmfamd_op_beta_update_rows_f32(float* P, float* Aacc, float* Bacc, const float* num_part, const float* den_part, int slabs, const float* dsum, int RP,
+                                              int r, int out_pad, int out_valid, double beta, double l1, double l2, int online, double rho, int flush, float* sum_part);
+NMFAMD_API int nmfamd_op_beta_update_rows_f64(double* P, double* Aacc, double* Bacc, const double* num_part, const double* den_part, int slabs, const double* dsum, int RP,
+                                              int r, int out_pad, int out_valid, double beta, double l1, double l2, int online, double rho, int flush, double* sum_part);
 /* Test access to an engine's device intermediates in panel layout: which = 0 Wt, 1 H, 2 W^T W,
  * 3 H H^T, 4 slabs, 5 inverse, 6 V, 7 Vt; rank-256 fp32 engines also 8 W^T W as last reduced, 9 staged column sums of squares,
  * 10 / 11 the bf16 fragments of W / H as 4-byte words. */

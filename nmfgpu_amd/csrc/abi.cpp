@@ -256,6 +256,23 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		}
 	}
 	{
+		// "batchSize" = b > 0 (docs/DIVERGENCE.md, "Minibatch update"): the dense divergence update over blocks of b columns of V, one pass per iteration, with the
+		// online update of W; "forgetFactor" in [0, 1], scikit-learn's 0.7 when a "batchSize" comes without it
+		int idx = parameter_index(d.parameters, d.numParameters, "batchSize");
+		if (idx >= 0) prm.batch_size = d.parameters[idx].value;
+		idx = parameter_index(d.parameters, d.numParameters, "forgetFactor");
+		if (idx >= 0) prm.forget_factor = d.parameters[idx].value;
+		else if (prm.batch_size != 0) prm.forget_factor = 0.7;
+		if (const char* why = nmfamd::minibatch_fault(prm)) {
+			log_error((std::string("[ERROR] ") + why).c_str());
+			return ResultType::ErrorInvalidArgument;
+		}
+		if (prm.is_minibatch() && d.useConstantBasisVectors) {
+			log_error("[ERROR] The minibatch update does not support constant basis vectors (with W fixed a batch step is the full H step)!");
+			return ResultType::ErrorInvalidArgument;
+		}
+	}
+	{
 		// "l1W", "l1H", "l2W", "l2H": the penalties of scikit-learn's coordinate descent on the HALS sweeps (docs/HALS.md) and of its multiplicative update on the
 		// dense divergence updates (docs/DIVERGENCE.md: "divergence" 2, 3, and 1 with "denseCompute"); absent = 0
 		struct { const char* name; double* slot; } pen[] = {{"l1W", &prm.l1W}, {"l1H", &prm.l1H}, {"l2W", &prm.l2W}, {"l2H", &prm.l2H}};

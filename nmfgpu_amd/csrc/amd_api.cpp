@@ -169,9 +169,10 @@ int nmfamd_engine_create_blocks(int m, int n, int r, int algorithm, const nmfamd
 
 int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* params_sized, unsigned long params_size, int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out) {
 	if (params_sized != nullptr && params_size < sizeof(nmfamd_params)) return NMFAMD_INVALID_ARGUMENT;
-	nmfamd_params_v5 v5;
-	std::memset(&v5, 0, sizeof(v5));
-	if (params_sized != nullptr) std::memcpy(&v5, params_sized, params_size < sizeof(v5) ? (size_t)params_size : sizeof(v5));
+	nmfamd_params_v6 v6;
+	std::memset(&v6, 0, sizeof(v6));
+	if (params_sized != nullptr) std::memcpy(&v6, params_sized, params_size < sizeof(v6) ? (size_t)params_size : sizeof(v6));
+	const nmfamd_params_v5& v5 = v6.v5;
 	const nmfamd_params_v4& v4 = v5.v4;
 	const nmfamd_params_v3& v3 = v4.v3;
 	const nmfamd_params_v2& v2 = v3.v2;
@@ -181,7 +182,7 @@ int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* para
 	g_create_error.clear();
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	AlgorithmParams p;
-	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; p.dense_compute = v2.dense_compute; p.beta_value = v3.beta; p.weighted = v4.weighted; p.mixed_precision = v5.mixed_precision; }
+	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; p.dense_compute = v2.dense_compute; p.beta_value = v3.beta; p.weighted = v4.weighted; p.mixed_precision = v5.mixed_precision; p.batch_size = v6.batch_size; p.forget_factor = v6.forget_factor; }
 	nmfamd_engine* e = new (std::nothrow) nmfamd_engine();
 	if (!e) return NMFAMD_NO_HOST_MEMORY;
 	e->elem_bytes = elem_bytes;
@@ -949,9 +950,51 @@ int op_beta_half_step(T* A, const T* B, const T* X, long ldx, int RP, int r, int
 	if (sum_part && hipMemcpy(sum_part, (T*)dSum.p + parts, sizeof(T) * parts, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
 	return NMFAMD_OK;
 }
+
+// k_beta_update_rows on caller-built arrays: P [out_pad][RP], num_part / den_part [slabs][out_pad][RP], dsum [RP] (beta = 1), Aacc / Bacc [out_pad][RP] (online)
+template <typename T>
+int op_beta_update_rows(T* P, T* Aacc, T* Bacc, const T* num_part, const T* den_part, int slabs, const T* dsum, int RP, int r, int out_pad, int out_valid, double beta_value,
+                        double l1d, double l2d, int online, double rho, int flush, T* sum_part) {
+	const double beta = (double)(T)beta_value;
+	const T l1 = (T)l1d, l2 = (T)l2d;
+	if (!P || !num_part || !beta_half_step_available(RP) || r < 1 || r > RP || !std::isfinite(beta) || !(l1d >= 0) || !(l2d >= 0) || !std::isfinite((double)l1) ||
+	    !std::isfinite((double)l2) || out_pad < 128 || out_pad % 128 != 0 || out_valid < 0 || out_valid > out_pad || slabs < 1 || slabs > BETA_MAX_SLABS ||
+	    (beta == 1 ? !dsum : !den_part) || (online && (!Aacc || !Bacc || !(rho >= 0) || !(rho <= 1))))
+		return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const size_t panel = sizeof(T) * (size_t)out_pad * RP, sums = sizeof(T) * (size_t)(out_pad / BETA_ROWS_PER_WG) * RP;
+	DevBuf dP, dA, dB, dNum, dDen, dD, dSum;
+	if (dP.alloc(panel) != hipSuccess || dA.alloc(panel) != hipSuccess || dB.alloc(panel) != hipSuccess || dNum.alloc(panel * slabs) != hipSuccess ||
+	    dDen.alloc(panel * slabs) != hipSuccess || dD.alloc(sizeof(T) * (size_t)RP) != hipSuccess || dSum.alloc(sums) != hipSuccess)
+		return NMFAMD_NO_DEVICE_MEMORY;
+	if (hipMemcpy(dP.p, P, panel, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dNum.p, num_part, panel * slabs, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemset(dSum.p, 0, sums) != hipSuccess)
+		return NMFAMD_HIP_ERROR;
+	if (den_part && hipMemcpy(dDen.p, den_part, panel * slabs, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (dsum && hipMemcpy(dD.p, dsum, sizeof(T) * (size_t)RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (online && (hipMemcpy(dA.p, Aacc, panel, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dB.p, Bacc, panel, hipMemcpyHostToDevice) != hipSuccess)) return NMFAMD_HIP_ERROR;
+	if (launch_beta_update_rows<T>((T*)dP.p, (T*)dA.p, (T*)dB.p, (const T*)dNum.p, (const T*)dDen.p, (long)out_pad * RP, slabs, (const T*)dD.p, RP, r, out_pad, out_valid,
+	                               std::numeric_limits<T>::epsilon(), beta, l1, l2, online != 0, (T)rho, flush != 0, (T*)dSum.p, nullptr) != hipSuccess ||
+	    hipDeviceSynchronize() != hipSuccess)
+		return NMFAMD_HIP_ERROR;
+	if (hipMemcpy(P, dP.p, panel, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (online && (hipMemcpy(Aacc, dA.p, panel, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(Bacc, dB.p, panel, hipMemcpyDeviceToHost) != hipSuccess)) return NMFAMD_HIP_ERROR;
+	if (sum_part && hipMemcpy(sum_part, dSum.p, sums, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
 }
 
 extern "C" {
+
+int nmfamd_op_beta_update_rows_f32(float* P, float* Aacc, float* Bacc, const float* num_part, const float* den_part, int slabs, const float* dsum, int RP, int r, int out_pad,
+                                   int out_valid, double beta, double l1, double l2, int online, double rho, int flush, float* sum_part) {
+	return op_beta_update_rows<float>(P, Aacc, Bacc, num_part, den_part, slabs, dsum, RP, r, out_pad, out_valid, beta, l1, l2, online, rho, flush, sum_part);
+}
+
+int nmfamd_op_beta_update_rows_f64(double* P, double* Aacc, double* Bacc, const double* num_part, const double* den_part, int slabs, const double* dsum, int RP, int r,
+                                   int out_pad, int out_valid, double beta, double l1, double l2, int online, double rho, int flush, double* sum_part) {
+	return op_beta_update_rows<double>(P, Aacc, Bacc, num_part, den_part, slabs, dsum, RP, r, out_pad, out_valid, beta, l1, l2, online, rho, flush, sum_part);
+}
 
 int nmfamd_op_beta_half_step_f32(float* A, const float* B, const float* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid, int beta,
                                  int form, int force_slabs, const float* dsum, float* t_frob, float* t_div, float* sumsq_part, float* sum_part, int* slabs) {

@@ -140,7 +140,7 @@ Engine<T>::~Engine() {
 	if (inv_work_) (void)hipFree(inv_work_);
 	if (range_flag_) (void)hipFree(range_flag_);
 	{
-		void* sp[] = {csr_ptr_, csr_idx_, csc_ptr_, csc_idx_, csc_from_csr_, csr_val_, csc_val_, q_, q2_, t_vwh_, t_kl_, rowsum_part_, sW_, sH_, kl_scale_, csr_bptr_, csc_bptr_, kl_part_, kl_tpart_, msq_part_, beta_den_, beta_tpart_};
+		void* sp[] = {csr_ptr_, csr_idx_, csc_ptr_, csc_idx_, csc_from_csr_, csr_val_, csc_val_, q_, q2_, t_vwh_, t_kl_, rowsum_part_, sW_, sH_, kl_scale_, csr_bptr_, csc_bptr_, kl_part_, kl_tpart_, msq_part_, beta_den_, beta_tpart_, online_A_, online_B_};
 		for (void* b : sp) if (b) (void)hipFree(b);
 	}
 	{ void* bb[] = {Vb_, Vtb_, Wtb_, Hb_, Wx3_, Hx3_, qx3_, gram_tri_part_, Gw_raw_, Gh_raw_, colsq_}; for (void* b : bb) if (b) (void)hipFree(b); }
@@ -182,8 +182,10 @@ Status Engine<T>::allocate() {
 	if (const char* why = weighted_fault(prm_)) { last_error_ = why; return ST_INVALID; }
 	beta_dense_ = prm_.is_beta_dense();
 	if (const char* why = mixed_precision_fault(prm_, sizeof(T) == 4)) { last_error_ = why; return ST_INVALID; }
+	if (const char* why = minibatch_fault(prm_)) { last_error_ = why; return ST_INVALID; }
 	weighted_ = prm_.weighted != 0;
 	mixed_ = prm_.mixed_precision != 0;
+	minibatch_ = prm_.is_minibatch();
 	if (beta_dense_) {
 		// beta in the engine's precision, as the penalties: a value that rounds to 0 or 1 there IS the Itakura-Saito or the dense KL engine
 		beta_ = (double)(T)prm_.beta();
@@ -227,6 +229,21 @@ Status Engine<T>::allocate() {
 		betaH_ = plan_beta_half_step(pad128(n_), pad128(m_), RP_, sizeof(T), num_cus_);
 		betaW_ = plan_beta_half_step(pad128(m_), pad128(n_), RP_, sizeof(T), num_cus_);
 		planH_.splits = betaH_.slabs; planW_.splits = betaW_.slabs;
+		if (minibatch_) {
+			// the minibatch update: the same two launches on a block of columns -- a full batch and the remainder batch, each padded to 128 (the reported slab
+			// counts stay those of the full shape, which the error iterations' terms-only launch uses)
+			batch_ = (long)prm_.batch_size;
+			rho_ = (double)(T)std::pow(prm_.forget_factor, (double)std::min<long>(batch_, n_) / (double)n_);
+			const long rem = n_ % batch_;
+			if (batch_ <= n_) {
+				betaHb_ = plan_beta_half_step(batch_, pad128(m_), RP_, sizeof(T), num_cus_);
+				betaWb_ = plan_beta_half_step(pad128(m_), batch_, RP_, sizeof(T), num_cus_);
+			}
+			if (rem > 0) {
+				betaHr_ = plan_beta_half_step(pad128(rem), pad128(m_), RP_, sizeof(T), num_cus_);
+				betaWr_ = plan_beta_half_step(pad128(m_), pad128(rem), RP_, sizeof(T), num_cus_);
+			}
+		}
 	}
 	if (prm_.precision > 0) {
 		// bf16 operands for the two big products, dense (resident) V only; every algorithm, padded rank 64 or k * 128
@@ -337,7 +354,7 @@ Status Engine<T>::allocate() {
 	elemsV_ = mpad_ * npad_;     // tiled or not: every tile spans all columns
 	elemsVt_ = tiled_ ? (long)planH_.xtiles * strideVt_ : mpad_ * npad_;
 	slab_stride_ = (long)RP_ * std::max(mpad_, npad_);
-	const long slab_elems = slab_stride_ * std::max(planH_.splits, planW_.splits);
+	const long slab_elems = slab_stride_ * std::max(std::max(planH_.splits, planW_.splits), std::max(std::max(betaHb_.slabs, betaWb_.slabs), std::max(betaHr_.slabs, betaWr_.slabs)));
 	const long panelW = (long)RP_ * mpad_, panelH = (long)RP_ * npad_, rr = (long)RP_ * RP_;
 
 	auto dalloc = [&](T** p, long elems) -> hipError_t {
@@ -380,9 +397,11 @@ Status Engine<T>::allocate() {
 	if (beta_dense_) {
 		HIPX(dalloc(&t_vwh_, mpad_));
 		HIPX(dalloc(&t_kl_, mpad_));
-		HIPX(dalloc(&rowsum_part_, (std::max(mpad_, npad_) / 128) * RP_));
+		// (minibatch: k_beta_update_rows leaves one vector of sums per BETA_ROWS_PER_WG rows, not per 128)
+		HIPX(dalloc(&rowsum_part_, (std::max(mpad_, npad_) / (minibatch_ ? BETA_ROWS_PER_WG : 128)) * RP_));
 		HIPX(dalloc(&sW_, RP_));
 		HIPX(dalloc(&sH_, RP_));
+		if (minibatch_) { HIPX(dalloc(&online_A_, (long)RP_ * mpad_)); HIPX(dalloc(&online_B_, (long)RP_ * mpad_)); }
 		HIPX(dalloc(&beta_tpart_, 2l * BETA_MAX_SLABS * mpad_));
 		if (beta_ != 1 || weighted_) HIPX(dalloc(&beta_den_, slab_elems));
 		if (weighted_) { HIPX(dalloc(&Om_, elemsV_)); HIPX(dalloc(&Omt_, elemsVt_)); }
@@ -847,6 +866,7 @@ Status Engine<T>::upload_sparse_device(int format, const T* values, const int* a
 
 template <typename T>
 Status Engine<T>::set_factors(const T* W, long ldw, const T* H, long ldh) {
+	online_stale_ = true;      // (a minibatch engine starts again from A = W, B = 1, as scikit-learn does at the start of a fit)
 	if (W) {
 		if (ldw < m_) return ST_INVALID;
 		fused_ready_ = false; w_pending_ = false; f32w_pending_ = false; f64_pending_ = false; f64_product_ahead_ = false; kl_scale_pending_ = false; gram_w_ready_ = false; wx3_valid_ = false; hx3_valid_ = false; wtb_valid_ = false; tri_gw_ready_ = false; qx3_holds_g_ = false; h_product_ahead_ = false;
@@ -895,6 +915,7 @@ Status Engine<T>::get_factors(T* W, long ldw, T* H, long ldh) {
 template <typename T>
 Status Engine<T>::randomize_factors(unsigned seed, bool w, bool h, long h_first_column) {
 	// The reference seeds W's and H's generators identically (RandomValueStrategy.cpp:53-69).
+	online_stale_ = true;
 	if (w) { h_product_ahead_ = false; f64_product_ahead_ = false; kl_sw_ready_ = false; fused_ready_ = false; w_pending_ = false; f32w_pending_ = false; f64_pending_ = false; kl_scale_pending_ = false; gram_w_ready_ = false; wx3_valid_ = false; hx3_valid_ = false; wtb_valid_ = false; tri_gw_ready_ = false; qx3_holds_g_ = false; tri_scale_pending_ = false; tri_scale_from_gram_ = false; w_rows_stale_ = false; }
 	if (h) { gram_h_partials_ = false; hx3_valid_ = false; hb_valid_ = false; }
 	if (w) HIPX(launch_fill_uniform<T>(Wt_, RP_, r_, m_, mpad_, seed, stream_));
@@ -2106,6 +2127,10 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 	const T eps = std::numeric_limits<T>::epsilon();
 	timing_now_ = timing_ && (timing_iter_++ % timing_stride_ == 0);
 	if (prm_.is_masked()) return iterate_masked(compute_error, constant_w);      // (before the KL test: a masked engine never has divergence != 0, allocate())
+	if (beta_dense_ && minibatch_) {
+		if (constant_w) { last_error_ = "minibatch update: no constant-W form (with W fixed a batch step is the full H step: use the engine without 'batchSize')"; return ST_INVALID; }
+		return iterate_beta_minibatch(compute_error);
+	}
 	if (beta_dense_) return iterate_beta(compute_error, constant_w);
 	if (prm_.divergence != 0) return constant_w ? ST_INVALID : iterate_kl(compute_error);
 	if (fused_capable() && !constant_w) return iterate_mu64(compute_error);
@@ -2569,6 +2594,69 @@ Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
 		// (the weighted beta = 1: the columns of W normalised, H not rescaled, as above -- without the column sums nobody reads)
 		if (beta == 1) HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, partsW, stream_));
 		else HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, partsW, stream_));
+	}
+	return ST_OK;
+}
+
+// The minibatch (online) form (docs/DIVERGENCE.md, "Minibatch update"; scikit-learn's MiniBatchNMF): one iteration is one pass over the column ranges [0, b),
+// [b, 2 b), ... in order.  A batch J at column offset c0 takes the two fused launches of iterate_beta on offset pointers -- the H side on V_ + c0 mpad and
+// H_ + c0 RP with the batch as its output range, the W side on Vt_ + c0 (leading dimension npad) with the batch as its reduction range -- and after each the
+// fine-grained update launch of kernels_beta_online.hip: the ordinary update on H_J, the online one (A <- rho A + W^(1/gamma) num, B <- rho B + den,
+// W <- (A / B)^gamma) on W.  Values below eps become 0 in H_J at beta < 1 and in W at beta <= 1.  No normalisation (a rescale of W would have to rescale A, B and
+// every column of H); at beta = 1 the denominators are the column sums of W as it is and the row sums of H over J.  There is no single P in a pass, so the errors
+// of an error iteration are those of (W_k, H_k) AFTER the pass, from one terms-only launch over the whole of V.
+template <typename T>
+Status Engine<T>::iterate_beta_minibatch(bool compute_error) {
+	if (!beta_uploaded_) { last_error_ = "dense divergence update: no V has been uploaded"; return ST_INVALID; }
+	const T eps = std::numeric_limits<T>::epsilon();
+	const double beta = beta_;
+	const bool kl = beta == 1;
+	const T l1W = (T)prm_.l1W, l1H = (T)prm_.l1H, l2W = (T)prm_.l2W, l2H = (T)prm_.l2H;
+	const int partsW = (int)(mpad_ / BETA_ROWS_PER_WG);
+	if (online_stale_) { HIPX(launch_beta_online_reset<T>(Wt_, online_A_, online_B_, (long)RP_ * mpad_, stream_)); online_stale_ = false; }
+	if (kl && !kl_sw_ready_) { HIPX(launch_panel_rowsum<T>(Wt_, RP_, (int)mpad_, rowsum_part_, sW_, stream_)); kl_sw_ready_ = true; }
+	for (long c0 = 0; c0 < n_; c0 += batch_) {
+		const int blen = (int)std::min<long>(batch_, n_ - c0), bpad = (int)pad128(blen);
+		const bool full = blen == batch_;
+		const BetaPlan& pH = full ? betaHb_ : betaHr_;
+		const BetaPlan& pW = full ? betaWb_ : betaWr_;
+		T* HJ = H_ + c0 * RP_;
+		// H step on the batch's columns: its rows of the column-major image are the output range
+		record_begin();
+		if (mixed_)
+			HIPX(beta_fused_mixed(V_ + c0 * mpad_, mpad_, HJ, Wt_, RP_, beta, true, false, eps, pH, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0, bpad, blen, m_, stream_));
+		else
+			HIPX(launch_beta_fused<T>(V_ + c0 * mpad_, mpad_, HJ, Wt_, RP_, beta, true, false, eps, pH, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0, bpad, blen, m_, stream_));
+		record_end();
+		HIPX(launch_beta_update_rows<T>(HJ, (T*)nullptr, (T*)nullptr, slabs_, beta_den_, slab_stride_, pH.slabs, sW_, RP_, r_, bpad, blen, eps, beta, l1H, l2H, false, T(0),
+		                                beta < 1, kl ? rowsum_part_ : (T*)nullptr, stream_));
+		if (kl) HIPX(launch_kl_sums<T>(rowsum_part_, nullptr, bpad / BETA_ROWS_PER_WG, RP_, sH_, stream_));
+		// W step with the new H_J: the batch's columns of the transposed image are the reduction range
+		record_begin(1);
+		if (mixed_)
+			HIPX(beta_fused_mixed(Vt_ + c0, npad_, Wt_, HJ, RP_, beta, true, false, eps, pW, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0, (int)mpad_, m_, blen, stream_));
+		else
+			HIPX(launch_beta_fused<T>(Vt_ + c0, npad_, Wt_, HJ, RP_, beta, true, false, eps, pW, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0, (int)mpad_, m_, blen, stream_));
+		record_end();
+		HIPX(launch_beta_update_rows<T>(Wt_, online_A_, online_B_, slabs_, beta_den_, slab_stride_, pW.slabs, sH_, RP_, r_, (int)mpad_, m_, eps, beta, l1W, l2W, true, (T)rho_,
+		                                beta <= 1, kl ? rowsum_part_ : (T*)nullptr, stream_));
+		if (kl) HIPX(launch_kl_sums<T>(rowsum_part_, nullptr, partsW, RP_, sW_, stream_));
+	}
+	if (compute_error) {
+		// the terms-only form of the W-side launch over the whole of V, with the full-shape plan
+		T* tf = beta_tpart_;
+		T* td = beta_tpart_ + (long)BETA_MAX_SLABS * mpad_;
+		if (mixed_)
+			HIPX(beta_fused_mixed(Vt_, npad_, Wt_, H_, RP_, beta, false, true, eps, betaW_, slabs_, beta_den_, slab_stride_, tf, td, mpad_, (int)mpad_, m_, n_, stream_));
+		else
+			HIPX(launch_beta_fused<T>(Vt_, npad_, Wt_, H_, RP_, beta, false, true, eps, betaW_, slabs_, beta_den_, slab_stride_, tf, td, mpad_, (int)mpad_, m_, n_, stream_));
+		HIPX(launch_beta_update<T>(Wt_, slabs_, beta_den_, slab_stride_, betaW_.slabs, sH_, RP_, r_, (int)mpad_, m_, eps, beta, l1W, l2W, false, (T*)nullptr, (T*)nullptr, tf, td,
+		                           mpad_, t_vwh_, t_kl_, stream_, false));
+		finalize_error(false);      // (the pinned buffer is about to be reused; an older copy is long complete)
+		HIPX(hipMemcpyAsync(pin_kl_, t_vwh_, sizeof(T) * m_, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipMemcpyAsync(pin_kl_ + m_, t_kl_, sizeof(T) * m_, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipEventRecord(err_event_, stream_));
+		beta_pending_ = true;
 	}
 	return ST_OK;
 }

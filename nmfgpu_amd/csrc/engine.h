@@ -33,7 +33,10 @@ struct AlgorithmParams {
 	double beta_value = 0;      // divergence = 3: the beta of the divergence, any finite value (0 and 1 run the Itakura-Saito and dense KL engines as they are)
 	double weighted = 0;        // 1 on a dense divergence engine: per-entry weights uploaded beside V (upload_dense_weighted; kernels_beta_weighted.hip, docs/DIVERGENCE.md)
 	double mixed_precision = 0; // 1 on a dense divergence fp32 engine: the operands of the fused half-step's products rounded to bf16 (kernels_beta_bf16.hip, docs/DIVERGENCE.md)
+	double batch_size = 0;      // > 0 on a dense divergence engine: the minibatch (online) update over blocks of batch_size columns of V (kernels_beta_online.hip, docs/DIVERGENCE.md)
+	double forget_factor = 0;   // ... its forgetting factor in [0, 1]: rho = forget_factor^(min(batch_size, n) / n) scales the accumulated numerator and denominator of W
 	bool is_masked() const { return missing_values != 0; }
+	bool is_minibatch() const { return batch_size != 0; }
 	// the dense beta-divergence update: Itakura-Saito (beta = 0) and the general form always, generalised KL (beta = 1) with dense_compute
 	bool is_beta_dense() const { return divergence == 2 || divergence == 3 || (divergence == 1 && dense_compute != 0); }
 	double beta() const { return divergence == 2 ? 0.0 : divergence == 3 ? beta_value : 1.0; }
@@ -86,6 +89,17 @@ inline const char* mixed_precision_fault(const AlgorithmParams& p, bool fp32) {
 	if (!p.is_beta_dense()) return "mixed precision: only on a dense divergence engine ('divergence' = 2 or 3, or 1 with 'denseCompute')";
 	if (!fp32) return "mixed precision: single-precision engines only";
 	if (p.weighted != 0) return "mixed precision: does not combine with 'weighted' (the weighted kernels have no bf16 form)";
+	return nullptr;
+}
+
+// What 'batchSize' and 'forgetFactor' (nmfamd_params_v6) must satisfy, after the three above: nullptr, or why not.
+inline const char* minibatch_fault(const AlgorithmParams& p) {
+	if (!(p.forget_factor >= 0 && p.forget_factor <= 1)) return "minibatch update: 'forgetFactor' has to be a finite value in [0, 1]";
+	if (p.batch_size == 0) return p.forget_factor != 0 ? "minibatch update: 'forgetFactor' needs a 'batchSize'" : nullptr;
+	if (!(p.batch_size >= 128 && p.batch_size <= 2147483520.0) || p.batch_size != (double)(128 * (long)(p.batch_size / 128)))
+		return "minibatch update: 'batchSize' has to be a positive multiple of 128 (the padding unit of the panels, which covers every kernel's reduction tile)";
+	if (!p.is_beta_dense()) return "minibatch update: only on a dense divergence engine ('divergence' = 2 or 3, or 1 with 'denseCompute')";
+	if (p.weighted != 0) return "minibatch update: does not combine with 'weighted' (the accumulating update has no weighted form)";
 	return nullptr;
 }
 
@@ -279,6 +293,7 @@ private:
 	Status iterate_kl(bool compute_error);            // KL-divergence multiplicative update (sparse mode)
 	Status iterate_masked(bool compute_error, bool constant_w);   // multiplicative update over the stored entries only (kernels_masked.hip)
 	Status masked_refuses(const char* what);          // ST_INVALID with last_error_ set: no three-phase / sharded form of the masked update
+	Status iterate_beta_minibatch(bool compute_error);            // ... its minibatch (online) form: one pass over the batches (kernels_beta_online.hip)
 	Status iterate_beta(bool compute_error, bool constant_w);     // dense beta-divergence multiplicative update (kernels_beta.hip, docs/DIVERGENCE.md)
 	Status beta_refuses(const char* what);            // ... nor of the dense beta-divergence update
 	Status beta_check_values(const T* values, long count, long ld, long rows);   // upload: beta <= 0 needs finite values > 0, beta > 0 finite values >= 0
@@ -360,6 +375,14 @@ private:
 	// ... weighted (prm_.weighted): Om_ / Omt_ are the images of the weights in the layouts of V_ / Vt_, sum_w_ their sum (in double, on the host, at upload: rmsd's
 	// divisor); beta_den_ is allocated at beta = 1 too (the weighted KL denominator is a product)
 	bool weighted_ = false;
+	// ... minibatch (prm_.batch_size > 0): batch_ columns per step, rho_ = forget_factor^(min(batch_, n) / n) in the precision of T; the plans of the two half-steps
+	// of a full batch (betaHb_, betaWb_) and of the remainder batch (betaHr_, betaWr_); online_A_ / online_B_ the accumulated numerator and denominator panels of W
+	// ([mpad][RP], set to W and 1 before the first step after the factors were set: online_stale_)
+	bool minibatch_ = false, online_stale_ = true;
+	long batch_ = 0;
+	double rho_ = 0;
+	BetaPlan betaHb_, betaWb_, betaHr_, betaWr_;
+	T *online_A_ = nullptr, *online_B_ = nullptr;
 	// ... mixed precision (prm_.mixed_precision, fp32 only): iterate_beta launches launch_beta_fused_bf16 in place of launch_beta_fused, nothing else changes
 	bool mixed_ = false;
 	T *Om_ = nullptr, *Omt_ = nullptr;

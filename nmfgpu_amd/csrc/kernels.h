@@ -558,6 +558,19 @@ hipError_t launch_beta_fused_weighted(const T* X, const T* OX, long ldx, const T
 hipError_t launch_beta_fused_bf16(const float* X, long ldx, const float* A, const float* B, int RP, double beta, bool update, bool terms, float eps, const BetaPlan& plan,
                                   float* num_part, float* den_part, long part_stride, float* tf_part, float* td_part, long t_stride,
                                   int out_pad, int out_valid, int red_valid, hipStream_t stream);
+// The update launch of the minibatch update (kernels_beta_online.hip), on a grid of one workgroup per BETA_ROWS_PER_WG panel rows: the slabs in order, den = (their
+// den_part, or dsum(c) at beta = 1) + eps + l1 + l2 P(o, c), then for o < out_valid, c < r
+//     online = false:  P(o, c) <- P(o, c) (num / den)^gamma                                        (launch_beta_update's update; Aacc, Bacc and rho are not looked at)
+//     online = true:   Aacc <- rho Aacc + P^(1 / gamma) num,  Bacc <- rho Bacc + den,  P <- (Aacc / Bacc)^gamma        (0 <= rho <= 1; Aacc, Bacc: [out_pad][RP])
+// flush: new values below eps become 0.  P is 0 on the padding afterwards; Aacc and Bacc are not touched there.  sum_part (optional): [out_pad / BETA_ROWS_PER_WG][RP]
+// sums of the new values, what launch_kl_sums takes with parts = out_pad / BETA_ROWS_PER_WG.  part_stride >= out_pad * RP.
+constexpr int BETA_ROWS_PER_WG = 16;
+template <typename T>
+hipError_t launch_beta_update_rows(T* P, T* Aacc, T* Bacc, const T* num_part, const T* den_part, long part_stride, int slabs, const T* dsum, int RP, int r, int out_pad,
+                                   int out_valid, T eps, double beta, T l1, T l2, bool online, T rho, bool flush, T* sum_part, hipStream_t stream);
+// Aacc <- P, Bacc <- 1 on `count` elements: the accumulators of a minibatch engine whenever its factors are set
+template <typename T>
+hipError_t launch_beta_online_reset(const T* P, T* Aacc, T* Bacc, long count, hipStream_t stream);
 
 // ---- the CSR and CSC images of a sparse V built on the device (kernels_sparse_setup.hip) ----------------------------------------
 // flags (one int, zeroed by the caller): bit 0 = an entry outside the matrix or outside every pointer range, bit 1 = pointer array not ascending, bit 2 = the

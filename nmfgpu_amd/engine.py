@@ -44,6 +44,11 @@ class _ParamsV5(C.Structure):
     _fields_ = [("v4", _ParamsV4), ("mixed_precision", C.c_double)]
 
 
+class _ParamsV6(C.Structure):
+    """nmfamd_params_v6: nmfamd_params_v5 (which keeps its size) followed by the fields added since."""
+    _fields_ = [("v5", _ParamsV5), ("batch_size", C.c_double), ("forget_factor", C.c_double)]
+
+
 class _Geometry(C.Structure):
     _fields_ = [("m", C.c_int), ("n", C.c_int), ("r", C.c_int), ("padded_rank", C.c_int),
                 ("padded_m", C.c_long), ("padded_n", C.c_long), ("slabs_h", C.c_int), ("slabs_w", C.c_int),
@@ -74,7 +79,8 @@ class Engine:
     def __init__(self, m: int, n: int, r: int, algorithm: str = "mu", dtype=np.float32, stream: int = 0,
                  lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence: str = "frobenius",
                  sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False,
-                 l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None, weighted: bool = False, mixed_precision: bool = False):
+                 l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None, weighted: bool = False, mixed_precision: bool = False,
+                 batch_size=None, forget_factor=0.7):
         """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V),
         "is" (Itakura-Saito, always dense: every entry of V > 0) or "beta" (the beta-divergence at `beta`, any finite value, always dense: scikit-learn's
         solver="mu" with beta_loss=beta; beta=0.0 and beta=1.0 are the "is" and the dense "kl" engines; beta <= 0 needs every entry of V > 0) --
@@ -92,12 +98,16 @@ class Engine:
 
         mixed_precision=True: a float32 dense divergence engine multiplies with bf16 operands (W, H and the mapped V .* P^(beta - 2), P^(beta - 1) rounded to
         nearest even; V, the element-wise map, every sum and the factors themselves stay float32) -- faster, with a relative error of a few 2^-9 per update
-        (docs/DIVERGENCE.md, "Mixed precision").  Not with float64, not with weighted=True; precision="bf16" stays refused on these engines."""
-        self._lib = library()
-        self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("float32 or float64")
-        self.m, self.n, self.r = m, n, r
+        (docs/DIVERGENCE.md, "Mixed precision").  Not with float64, not with weighted=True; precision="bf16" stays refused on these engines.
+
+        batch_size=b (a positive multiple of 128): the minibatch (online) form of a dense divergence engine, scikit-learn's MiniBatchNMF with the samples as the
+        columns of V (docs/DIVERGENCE.md, "Minibatch update").  One iterate() step is one pass over the column blocks [0, b), [b, 2 b), ... in order; W moves
+        once per block, from numerator and denominator panels accumulated with rho = forget_factor^(min(b, n) / n); set_factors and randomize start them again.
+        No normalisation, no constant_w; frobenius / rmsd / divergence_value refer to (W, H) after the pass.  None or 0: the full-batch engine, where
+        forget_factor is not looked at."""
+        if not batch_size:
+            batch_size, forget_factor = 0.0, 0.0
+        self._bind(m, n, r, dtype)
         if beta is not None and divergence != "beta":
             raise ValueError('beta needs divergence="beta"')
         if divergence == "beta" and beta is None:
@@ -105,24 +115,42 @@ class Engine:
         self._ctor = dict(algorithm=algorithm, stream=stream, row_blocks=row_blocks,
                           params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0, "is": 2.0, "beta": 3.0}[divergence],
                                   float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
-                                  float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted), float(mixed_precision)],
+                                  float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted), float(mixed_precision), float(batch_size), float(forget_factor)],
                           penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)])
+        self._create()
+
+    def _bind(self, m, n, r, dtype):
+        self._lib = library()
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64")
+        self.m, self.n, self.r = m, n, r
+        self._ctor = None
         self._h = None
         self._lib.nmfamd_engine_frobenius.restype = C.c_double
         self._lib.nmfamd_engine_rmsd.restype = C.c_double
         self._lib.nmfamd_engine_kl_divergence.restype = C.c_double
         self._lib.nmfamd_engine_last_error.restype = C.c_char_p
         self._lib.nmfamd_engine_error_terms.restype = C.c_long
-        self._create()
+
+    @classmethod
+    def from_handle(cls, handle, m: int, n: int, r: int, dtype=np.float32):
+        """The wrapper around an nmfamd_engine* that the caller created through the C interface (nmfamd_engine_create*), which it owns from here on (close()
+        destroys it).  Such an engine is never recreated: an upload the C side answers with NMFAMD_VALUE_RANGE raises instead of switching the product form."""
+        self = cls.__new__(cls)
+        self._bind(m, n, r, dtype)
+        self._h = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+        return self
 
     def _create(self):
         c = self._ctor
-        p = _ParamsV5(_ParamsV4(_ParamsV3(_ParamsV2(_Params(*c["params"][:10]), c["params"][10]), c["params"][11]), c["params"][12]), c["params"][13])
+        p = _ParamsV6(_ParamsV5(_ParamsV4(_ParamsV3(_ParamsV2(_Params(*c["params"][:10]), c["params"][10]), c["params"][11]), c["params"][12]), c["params"][13]),
+                      c["params"][14], c["params"][15])
         h = C.c_void_p()
         # row_blocks > 1: the padded row count is a multiple of 128 * row_blocks (row-block form of the sharded W step)
         if not hasattr(self._lib, "nmfamd_engine_create_v2"):
             # (NMFAMD_LIBRARY names a build from before the sized entry -- tools/time_beta.py times such a build: it reads the frozen struct only)
-            st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p.v4.v3.v2.base), self.dtype.itemsize,
+            st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p.v5.v4.v3.v2.base), self.dtype.itemsize,
                                                        C.c_void_p(c["stream"]), int(c["row_blocks"]), C.byref(h))
         else:
             st = self._lib.nmfamd_engine_create_v2(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p), C.c_ulong(C.sizeof(p)), self.dtype.itemsize,
@@ -174,7 +202,7 @@ class Engine:
     def _upload(self, call, what: str):
         st = call()
         # (missing values: NaN marks a missing entry and the sparse images never see it -- no retry)
-        if st == 6 and self._ctor["params"][8] == 0.0 and self._ctor["params"][9] == 0.0:
+        if st == 6 and self._ctor is not None and self._ctor["params"][8] == 0.0 and self._ctor["params"][9] == 0.0:
             # NMFAMD_VALUE_RANGE: infinities, NaN, |v| > 2^126 or 0 < |v| < 2^-100 in V -- the split-operand product is not the
             # fp32 product there; recreate the engine on the native fp32 MFMA instructions, as nmfgpu::compute does.
             # The handle changes: anything created from the old one (a ShardedRun, w_panel_ptr()) is void -- upload V before
@@ -229,7 +257,8 @@ class Engine:
         the unpenalised iteration, normalisation included.  frobenius / rmsd / divergence_value keep reporting the unpenalised figures."""
         vals = [float(l1_w), float(l1_h), float(l2_w), float(l2_h)]
         self._check(self._lib.nmfamd_engine_set_hals_penalties(self._h, *(C.c_double(v) for v in vals)), "set_hals_penalties")
-        self._ctor["penalties"] = vals
+        if self._ctor is not None:
+            self._ctor["penalties"] = vals
 
     @property
     def frobenius(self) -> float:
@@ -736,6 +765,40 @@ def op_beta_half_step_weighted(A: np.ndarray, B: np.ndarray, X: np.ndarray, Omeg
     with weight 0 is not there, whatever X holds at it; num, den and the error terms of every other entry are scaled by its weight.  The denominator is a product
     at every beta (no dsum).  The same dict."""
     return _beta_half_step(A, B, X, r, out_valid, red_valid, float(beta), form, None, force_slabs, (float(l1), float(l2)), Omega)
+
+
+def op_beta_update_rows(P: np.ndarray, num_part: np.ndarray, den: np.ndarray, r: int, out_valid: int, beta: float, *, l1: float = 0.0, l2: float = 0.0,
+                        acc=None, rho: float = 0.0, flush: bool = False):
+    """The update launch of the minibatch update (nmfamd_op_beta_update_rows_*, kernels_beta_online.hip) on padded arrays: P (out_pad, RP) the panel, num_part
+    (slabs, out_pad, RP) the slabs' partial numerators, den either (slabs, out_pad, RP) partial denominators or, at beta = 1, the RP denominators.  acc=None:
+    P <- P (num / (den + eps + l1 + l2 P))^gamma.  acc=(A, B), two (out_pad, RP) arrays: the online update A <- rho A + P^(1 / gamma) num, B <- rho B + den + ...,
+    P <- (A / B)^gamma.  flush: new values below eps become 0.  Returns a dict: `P`, `A`, `B` (new arrays; None without acc) and `sum_part` ((out_pad // 16, RP):
+    the sums of the new values over each 16 rows)."""
+    dt = np.dtype(P.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("float32 or float64")
+    P = np.array(P, dtype=dt, order="C")
+    num_part = np.ascontiguousarray(num_part, dtype=dt)
+    den = np.ascontiguousarray(den, dtype=dt)
+    out_pad, RP = P.shape
+    if num_part.ndim != 3 or num_part.shape[1:] != (out_pad, RP):
+        raise ValueError("shapes: P (out_pad, RP); num_part (slabs, out_pad, RP)")
+    vec = den.ndim == 1
+    if (vec and den.shape != (RP,)) or (not vec and den.shape != num_part.shape):
+        raise ValueError("den: (slabs, out_pad, RP) partial denominators, or RP denominators at beta = 1")
+    A = B = None
+    if acc is not None:
+        A = np.array(acc[0], dtype=dt, order="C"); B = np.array(acc[1], dtype=dt, order="C")
+        if A.shape != P.shape or B.shape != P.shape:
+            raise ValueError("acc: two arrays of the shape of P")
+    sm = np.zeros((out_pad // 16, RP), dt)
+    fn = library().nmfamd_op_beta_update_rows_f32 if dt == np.float32 else library().nmfamd_op_beta_update_rows_f64
+    ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+    st = fn(ptr(P), ptr(A), ptr(B), ptr(num_part), None if vec else ptr(den), int(num_part.shape[0]), ptr(den) if vec else None, RP, int(r), out_pad, int(out_valid),
+            C.c_double(beta), C.c_double(l1), C.c_double(l2), int(acc is not None), C.c_double(rho), int(bool(flush)), ptr(sm))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_beta_update_rows")
+    return {"P": P, "A": A, "B": B, "sum_part": sm}
 
 
 def op_hals_normalize(Wt: np.ndarray, H: np.ndarray, sumsq_part: np.ndarray):
