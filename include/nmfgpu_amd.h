@@ -394,7 +394,9 @@ NMFAMD_API int nmfamd_op_factor_product_x3(const float* A, long lda, int X, int 
 NMFAMD_API int nmfamd_op_factor_product_x3_ytiled(const float* A, long lda, int X, int Y, const float* F, long ldf, int r, float* OUT, long ldo,
                                                   int reps, double* avg_us);
 /* Diagnostic (NMFAMD_X3_VARIANT = 10..13 builds): per wave {shader cycles, 100 MHz ticks, K-steps of the main loop; 100 MHz
- * stamps at entry, loop start, loop end, tail end, exit} of one more launch; stamps_capacity in 8-byte words; *waves receives the number of waves stamped. */
+ * stamps at entry, loop start, loop end, tail end, exit; at the first operand split (the first K-step's rows are there), at the end of an odd piece's first K-step
+ * (0: whole turns), at the first MFMA group of the loop's first turn; one unused word} = 12 words per wave of one more launch; stamps_capacity in 8-byte words;
+ * *waves receives the number of waves stamped. */
 NMFAMD_API int nmfamd_tune_factor_product_x3(int X, int Y, unsigned long long* stamps_out, long stamps_capacity, long* waves);
 /* G (r x r) = P P^T for a host r x len matrix P. */
 NMFAMD_API int nmfamd_op_gram_f32(const float* P, long ldp, int r, int len, float* G, long ldg);

@@ -626,20 +626,20 @@ int nmfamd_tune_factor_product_x3(int X, int Y, unsigned long long* stamps_out, 
 	const bool ytiled = ve != nullptr && std::atoi(ve) >= 30;
 	const FactorProductPlan& sp = ytiled ? planH : planW;
 	const long nwaves = (long)sp.xtiles * sp.splits * 4;
-	if (stamps_capacity < 8 * nwaves) return NMFAMD_INVALID_ARGUMENT;
+	if (stamps_capacity < X3_STAMP_WORDS * nwaves) return NMFAMD_INVALID_ARGUMENT;
 	DevBuf dA, dW, dH, dWx, dHx, dS, dT;
 	const long slab_stride = (long)RP * std::max(Mp, Np);
 	if (dA.alloc(sizeof(float) * Mp * Np) != hipSuccess || dW.alloc(sizeof(float) * RP * Mp) != hipSuccess || dH.alloc(sizeof(float) * RP * Np) != hipSuccess ||
 	    dWx.alloc(3 * 16 * (size_t)(ksH + 1) * (RP / 32) * 64) != hipSuccess || dHx.alloc(3 * 16 * (size_t)(ksW + 1) * (RP / 32) * 64) != hipSuccess ||
 	    dS.alloc(sizeof(float) * slab_stride * std::max(planW.splits, planH.splits)) != hipSuccess ||
-	    dT.alloc(sizeof(unsigned long long) * 8 * nwaves) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+	    dT.alloc(sizeof(unsigned long long) * X3_STAMP_WORDS * nwaves) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
 	// (any buffer of the right size is an image of random data)
 	if (launch_fill_uniform<float>((float*)dA.p, (int)Mp, (int)Mp, Np, Np, 1, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (launch_fill_uniform<float>((float*)dW.p, RP, RP, Mp, Mp, 2, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (launch_fill_uniform<float>((float*)dH.p, RP, RP, Np, Np, 3, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (launch_pack_panel_x3((const float*)dW.p, RP, X, dWx.p, ksH, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (launch_pack_panel_x3((const float*)dH.p, RP, Y, dHx.p, ksW, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
-	if (hipMemset(dT.p, 0, sizeof(unsigned long long) * 8 * nwaves) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (hipMemset(dT.p, 0, sizeof(unsigned long long) * X3_STAMP_WORDS * nwaves) != hipSuccess) return NMFAMD_HIP_ERROR;
 	const long stride = 16 * Np;
 	for (int i = 0; i < 40; ++i) {
 		const bool last = i == 39;
@@ -648,7 +648,7 @@ int nmfamd_tune_factor_product_x3(int X, int Y, unsigned long long* stamps_out, 
 		if (launch_factor_product_x3(planH, (const float*)dA.p, stride, dWx.p, RP, (float*)dS.p, slab_stride, nullptr, nullptr, sy, true, 16) != hipSuccess) return NMFAMD_HIP_ERROR;
 		if (launch_factor_product_x3(planW, (const float*)dA.p, stride, dHx.p, RP, (float*)dS.p, slab_stride, nullptr, nullptr, sx, false, 16) != hipSuccess) return NMFAMD_HIP_ERROR;
 	}
-	if (hipMemcpy(stamps_out, dT.p, sizeof(unsigned long long) * 8 * nwaves, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (hipMemcpy(stamps_out, dT.p, sizeof(unsigned long long) * X3_STAMP_WORDS * nwaves, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
 	*waves = nwaves;
 	return NMFAMD_OK;
 }

@@ -430,6 +430,8 @@ void set_factor_product_bf16_stamps(unsigned long long* stamps);      // measure
 // The streamed matrix is the x-tiled fp32 image (tile height 128); the factor panel is split into
 // three bf16 planes in fragment order, KS K-steps plus one all-zero step: 3 * 16 bytes * (KS + 1) * (RP / 32) * 64.
 hipError_t launch_pack_panel_x3(const float* P, int RP, int len, void* dst, int KS, hipStream_t stream);
+// stamps (measurement build): X3_STAMP_WORDS words per wave, the kernel's end says which (tools/stamp_x3.py)
+constexpr int X3_STAMP_WORDS = 12;
 hipError_t launch_factor_product_x3(const FactorProductPlan& p, const float* A, long tile_stride, const void* F, int RP,
                                     float* slabs, long slab_stride, hipStream_t stream, const GramReduceArgs* rg = nullptr,
                                     unsigned long long* stamps = nullptr, bool y_tiled = false, int image_tile = 128,

@@ -47,6 +47,9 @@ constexpr bool XCD_REMAP = NMFAMD_XCD_REMAP != 0;
 #ifndef X3_DEAL_TURNS
 #define X3_DEAL_TURNS 0               // (A/B switch, tools/build_variant.sh: 1 = always deal the K-steps in whole turns of the ring, as rounds 2-4 did)
 #endif
+#ifndef X3_ODD_GUARDED_LOOP
+#define X3_ODD_GUARDED_LOOP 0         // (A/B switch: 1 = the start of an odd piece as it was compiled before: a loop the compiler may skip, see the loop in k_factor_product_x3)
+#endif
 #ifndef X3_RING_Y
 #define X3_RING_Y 2                   // ... y-tiled form (its landing ring; two more steps sit in the LDS slots)
 #endif
@@ -150,7 +153,8 @@ __device__ inline void gram_reduce_block_x3(const GramReduceArgs& rg, int blk, f
 // summed through LDS in piece order; one fp32 slab per slice.
 // DIAG (measurement builds only, NMFAMD_X3_VARIANT 10..12): 1 = no ring refill (issue rate of the split + MFMA
 // stream alone), 2 = refill A only, 3 = refill F only, 4 = the production loop; all of them stamp the main loop
-// (shader cycles, 100 MHz ticks, K-steps per wave).  The production instantiation has DIAG = 0.
+// (shader cycles, 100 MHz ticks, K-steps per wave) and the start of the wave's piece (first operand split, end of an odd piece's first step, first MFMA
+// group of the loop's first turn: X3_STAMP_WORDS words per wave, see the kernel's end).  The production instantiation has DIAG = 0.
 // R32 (y-tiled form on 16-row tiles, loads straight to registers): MFMA row r of M-block b is tile row 32 b + r (as in the YLDS form) instead of 4 r + b: consecutive lanes read
 // consecutive 64-byte column chunks -- 16 cache lines per wave instruction instead of 32
 // ODD (ring depth 2): every wave piece is an ODD number of K-steps -- see the dealing below
@@ -161,7 +165,7 @@ __global__ __launch_bounds__(64 * X3_WAVES, NBW == 1 ? 2 : 1) void k_factor_prod
 	float* __restrict__ slabs, long slab_stride, int RP,
 	int steps_total, int xtiles, int splits, GramReduceArgs rg, unsigned long long* __restrict__ stamps) {
 	constexpr int TH = 128;
-	unsigned long long t_loop0 = 0, t_loop1 = 0, r_loop0 = 0, r_loop1 = 0, r_entry = 0, r_tail = 0;
+	unsigned long long t_loop0 = 0, t_loop1 = 0, r_loop0 = 0, r_loop1 = 0, r_entry = 0, r_tail = 0, r_data = 0, r_step1 = 0, r_turn0 = 0;
 	if (DIAG != 0) r_entry = __builtin_amdgcn_s_memrealtime();
 	extern __shared__ __attribute__((aligned(16))) float lds[];
 	// grid.x = xtiles * splits product blocks (x-tile fastest) followed by the GRAM_REDUCE_BLOCKS passenger blocks,
@@ -270,8 +274,9 @@ __global__ __launch_bounds__(64 * X3_WAVES, NBW == 1 ? 2 : 1) void k_factor_prod
 		f32x4 va[D][8];
 		bf16x8 fb[D][NBW][3];
 #pragma unroll
-		for (int d = 0; d < D; ++d) {
-			int st = s0 + (ODD ? (d ^ 1) : d);                      // (ODD: step s0 waits in ring slot 1, step s0 + 1 in slot 0; a piece of one step re-reads it there)
+		for (int dd = 0; dd < D; ++dd) {
+			const int d = (ODD && !X3_ODD_GUARDED_LOOP) ? (dd ^ 1) : dd;      // (ODD: slot 1 is requested first -- it holds the step that runs first)
+			int st = s0 + (ODD ? (d ^ 1) : d);                      // (ODD: step s0 waits in ring slot 1, step s0 + 1 in slot 0)
 			st = st < last ? st : last;
 			const int sa = st < kend ? st : kend, sf = st <= kend ? st : steps_total;
 #pragma unroll
@@ -317,6 +322,8 @@ __global__ __launch_bounds__(64 * X3_WAVES, NBW == 1 ? 2 : 1) void k_factor_prod
 			for (int j = 0; j < 8; ++j) v[j] = TR ? va[ODD ? D - 1 : 0][j >> 2][j & 3] : va[ODD ? D - 1 : 0][j][0];
 			split3(v, op[0][0], op[0][1], op[0][2]);
 		}
+		// (the first split has waited for the A rows of the step that runs first)
+		if (DIAG != 0) { __builtin_amdgcn_sched_barrier(0); r_data = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0); }
 		// one K-step out of ring slot d; t = the first step of the turn it belongs to
 		auto kstep = [&](auto dtag, const int t) {
 			constexpr int d = decltype(dtag)::value;
@@ -325,6 +332,12 @@ __global__ __launch_bounds__(64 * X3_WAVES, NBW == 1 ? 2 : 1) void k_factor_prod
 				for (int b = 0; b < 4; ++b) {
 					const int cur = (d * 4 + b) & 1, nxt = cur ^ 1;
 					const int nd = b == 3 ? (d + 1) % D : d, nbk = (b + 1) & 3;
+					if (DIAG != 0 && d == 0 && b == 0) {
+						// the first MFMA group of the loop's first turn (a scalar select: no branch in the loop)
+						const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+						r_turn0 = r_turn0 == 0 ? now : r_turn0;
+						__builtin_amdgcn_sched_barrier(0);
+					}
 					if (YLDS) {
 						// split the operand of the next phase (read from LDS one phase ago), then read the one after it
 						float v[8];
@@ -407,15 +420,24 @@ __global__ __launch_bounds__(64 * X3_WAVES, NBW == 1 ? 2 : 1) void k_factor_prod
 			}
 		};
 #define X3_KSTEP(dd) kstep(std::integral_constant<int, dd>{}, t)
+#define X3_TURN() do { X3_KSTEP(0); if constexpr (D > 1) X3_KSTEP(1); if constexpr (D > 2) X3_KSTEP(2); if constexpr (D > 3) X3_KSTEP(3); } while (0)
+		static_assert(D <= 4, "ring depth");
 		int t = 0;
-		if constexpr (ODD) { t = -1; X3_KSTEP(1); t = 1; }      // the piece's first step: "turn -1", slot 1 -- its refill is the step slot 1 holds in the loop's first turn
-		for (; t < steps; t += D) {
-			X3_KSTEP(0);
-			if constexpr (D > 1) X3_KSTEP(1);
-			if constexpr (D > 2) X3_KSTEP(2);
-			if constexpr (D > 3) X3_KSTEP(3);
-			static_assert(D <= 4, "ring depth");
+		if constexpr (ODD) {
+			t = -1; X3_KSTEP(1); t = 1;      // the piece's first step: "turn -1", slot 1 -- its refill is the step slot 1 holds in the loop's first turn
+			if (DIAG != 0) { r_step1 = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0); }
 		}
+		if constexpr (ODD && X3_ODD_GUARDED_LOOP == 0) {
+			// The loop of whole turns runs at least once: an odd piece is 2 a + 1 K-steps with a >= 1, because x3_odd_pieces picks this form only for
+			// steps_total >= 3 pieces (launch_fp_x3 refuses anything else).  The loop must SAY so: slot 0 and the first step's refill are read only by the turns,
+			// and ahead of a loop that may run zero times hipcc sinks those loads (const __restrict__ operands) into the loop's preheader -- past the
+			// sched_barrier above and the group barriers of the first step, which hold inside one block only.  The piece then started with 14 loads, a wait
+			// for vmcnt(0), a whole K-step with nothing in flight and a burst of 28 loads behind it.
+			do { X3_TURN(); t += D; } while (t < steps);
+		} else {
+			for (; t < steps; t += D) X3_TURN();
+		}
+#undef X3_TURN
 #undef X3_KSTEP
 		if (DIAG != 0) { __builtin_amdgcn_sched_barrier(0); t_loop1 = __builtin_amdgcn_s_memtime(); r_loop1 = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0); }
 	}
@@ -465,10 +487,12 @@ __global__ __launch_bounds__(64 * X3_WAVES, NBW == 1 ? 2 : 1) void k_factor_prod
 		__builtin_amdgcn_s_waitcnt(0);
 		const unsigned long long r_end = __builtin_amdgcn_s_memrealtime();
 		if (lane == 0) {
-			// shader cycles and 100 MHz ticks in the main loop, K-steps run there; then 100 MHz stamps of the wave's life
-			unsigned long long* o = stamps + 8 * ((long)blockIdx.x * X3_WAVES + wave);
+			// shader cycles and 100 MHz ticks in the main loop, K-steps run there; then 100 MHz stamps of the wave's life; then the start of the piece: the first
+			// step's A rows are there, the end of an odd piece's first step (0: whole turns), the first MFMA group of the loop's first turn
+			unsigned long long* o = stamps + X3_STAMP_WORDS * ((long)blockIdx.x * X3_WAVES + wave);
 			o[0] = t_loop1 - t_loop0; o[1] = r_loop1 - r_loop0; o[2] = (unsigned long long)steps;
 			o[3] = r_entry; o[4] = r_loop0; o[5] = r_loop1; o[6] = r_tail; o[7] = r_end;
+			o[8] = r_data; o[9] = r_step1; o[10] = r_turn0; o[11] = 0;
 		}
 	}
 }
@@ -504,6 +528,8 @@ static hipError_t launch_fp_x3(const FactorProductPlan& p, const float* A, long 
 	const int passengers = !with_reduce ? 0 : wide ? rg->wide_parts * ((RP / 128) * (RP / 128 + 1) / 2)
 	                                    : (rg->inv_a != nullptr ? 1 : (rg->image != nullptr && rg->ksplit > 1) ? GRAM_IMAGE_TILES * rg->ksplit : GRAM_REDUCE_BLOCKS);
 	if (NBW == 1 && RP != 64) return hipErrorInvalidValue;
+	// odd pieces: at least three K-steps each (x3_odd_pieces) -- the kernel's loop of whole turns is entered unconditionally
+	if (ODD && (long)p.steps_total < 3L * WAVES * p.splits) return hipErrorInvalidValue;
 	dim3 grid(p.xtiles * p.splits * (NBW == 1 ? 2 : 1) + passengers, NBW == 1 ? 1 : RP / (32 * NBW), 1), block(64 * WAVES);
 	const size_t lds_bytes = std::max<size_t>(std::max<size_t>(WAVES * ((X3_EPILOGUE_ONE_ROUND && NBW == 2 && !YLDS) ? 8 : 4) * 4 * 64 * sizeof(f32x4), 1024 * sizeof(float)),
 	                                          YLDS ? WAVES * 2 * 128 * 20 * sizeof(float) : 0);

@@ -12,12 +12,13 @@ from nmfgpu_amd._lib import library
 
 lib = library()
 X, Y = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (10000, 5000)
-cap = 8 * 4 * 400 * 8
+WORDS = 12      # per wave (csrc/kernels.h X3_STAMP_WORDS; the kernel's end says which)
+cap = WORDS * 4 * 400 * 8
 buf = np.zeros(cap, dtype=np.uint64)
 waves = C.c_long(0)
 st = lib.nmfamd_tune_factor_product_x3(X, Y, C.c_void_p(buf.ctypes.data), C.c_long(cap), C.byref(waves))
 assert st == 0, st
-s = buf[: 8 * waves.value].reshape(-1, 8).astype(np.float64)
+s = buf[: WORDS * waves.value].reshape(-1, WORDS).astype(np.float64)
 s = s[s[:, 2] > 0]
 cyc, ticks, steps = s[:, 0], s[:, 1], s[:, 2]
 print(f"variant {os.environ.get('NMFAMD_X3_VARIANT')}: waves {len(s)}, steps/wave {steps.mean():.1f}, cycles/K-step median {np.median(cyc / steps):.0f} "
@@ -27,9 +28,19 @@ t0 = s[:, 3].min()
 for name, col in (("entry", 3), ("loop start", 4), ("loop end", 5), ("tail end", 6), ("exit", 7)):
     v = (s[:, col] - t0) / 100
     print(f"  {name:10s}: median {np.median(v):6.2f} us  min {v.min():6.2f}  max {v.max():6.2f}")
+# the start of a piece, per wave: entry -> the first K-step's rows are there (first operand split) -> [odd pieces: that step's end] -> the first MFMA group of the
+# loop's first turn.  A ring filled ahead of the first step leaves nothing between the last two; a second fill behind the first step shows there.
+odd = s[:, 9] > 0
+print(f"  start of a piece ({int(odd.sum())} of {len(s)} waves run a first step ahead of the loop):")
+spans = [("entry -> first step's data", s[:, 8] - s[:, 3], np.ones(len(s), dtype=bool)), ("the first step", s[:, 9] - s[:, 8], odd),
+         ("first step's end -> loop start", s[:, 10] - s[:, 9], odd), ("entry -> loop start", s[:, 10] - s[:, 3], np.ones(len(s), dtype=bool))]
+for name, v, sel in spans:
+    if sel.any():
+        v = v[sel] / 100
+        print(f"    {name:30s}: median {np.median(v):5.2f} us  max {v.max():5.2f}")
 # which workgroups end the launch: exit time by x-tile, by K slice and by XCD (the kernel's placement: block b runs on XCD b % 8; each XCD takes a contiguous
 # range of (slice, x-tile) pairs -- kernels_x3.hip, XCD_REMAP)
-full = buf[: 8 * waves.value].reshape(-1, 8).astype(np.float64)
+full = buf[: WORDS * waves.value].reshape(-1, WORDS).astype(np.float64)
 nblk = len(full) // 4
 variant = int(os.environ.get("NMFAMD_X3_VARIANT", "13"))
 y_tiled = variant >= 30
