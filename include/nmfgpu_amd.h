@@ -196,6 +196,12 @@ NMFAMD_API int nmfamd_engine_synchronize(nmfamd_engine* e);
  * ||V - W H||, not the penalised objective.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error) for a negative or non-finite value, and for a
  * non-zero value on any other engine. */
 NMFAMD_API int nmfamd_engine_set_hals_penalties(nmfamd_engine* e, double l1W, double l1H, double l2W, double l2H);
+/* HALS engines: accelerated HALS (Gillis & Glineur 2012; docs/HALS.md, "Inner sweeps").  The H step computes W^T W and W^T V once and applies its sweep sweeps_h
+ * times in a row, the W step H H^T and V H^T once and its sweep sweeps_w times, each sweep from the result of the one before, in one launch; everything else
+ * (penalties, normalisation, error reporting, constant W: the H step only) is as with one sweep.  1 ... 64 each; (1, 1), the default, is the plain iteration.
+ * Valid any time between iterations; takes effect at the next nmfamd_engine_iterate.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error) for a count
+ * outside 1 ... 64, and for a count other than 1 on any other engine. */
+NMFAMD_API int nmfamd_engine_set_hals_sweeps(nmfamd_engine* e, int sweeps_h, int sweeps_w);
 /* Frobenius norm / RMSD of the most recent error iteration (IAlgorithm::frobeniusNorm / rmsd). */
 NMFAMD_API double nmfamd_engine_frobenius(nmfamd_engine* e);
 NMFAMD_API double nmfamd_engine_rmsd(nmfamd_engine* e);
@@ -438,6 +444,13 @@ NMFAMD_API int nmfamd_op_hals_sweep_pen_f32(float* P, const float* slabs, int S,
                                             float* ps, float* sumsq_part, int* parts, float l1, float l2);
 NMFAMD_API int nmfamd_op_hals_sweep_pen_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid,
                                             double* ps, double* sumsq_part, int* parts, double l1, double l2);
+/* `sweeps` penalised sweeps in a row against the same G and slabs, each from the result of the one before, in one launch (kernels_hals_multi.hip); ps and
+ * sumsq_part from the final state, copied in and out as above.  sweeps = 1 is the launch of nmfamd_op_hals_sweep_pen_*.  NMFAMD_INVALID_ARGUMENT also for
+ * sweeps outside 1 ... 64. */
+NMFAMD_API int nmfamd_op_hals_sweeps_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid,
+                                         float* ps, float* sumsq_part, int* parts, float l1, float l2, int sweeps);
+NMFAMD_API int nmfamd_op_hals_sweeps_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid,
+                                         double* ps, double* sumsq_part, int* parts, double l1, double l2, int sweeps);
 /* The HALS column normalisation on host panels Wt [mpad][RP] and H [npad][RP] (both updated in place) from parts x RP partial sums of squares:
  * d(c) = sqrt(sum of the parts); where d(c) > 0, Wt(:, c) / d(c) and H(:, c) * d(c). */
 NMFAMD_API int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad, const float* sumsq_part, int parts);

@@ -288,6 +288,18 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		}
 	}
 	{
+		// "sweepsH", "sweepsW": sweeps per product of accelerated HALS (docs/HALS.md, "Inner sweeps"); absent = 1, integers in 1 ... 64, other than 1 only with HALS
+		int idx = parameter_index(d.parameters, d.numParameters, "sweepsH");
+		if (idx >= 0) prm.sweeps_h = d.parameters[idx].value;
+		idx = parameter_index(d.parameters, d.numParameters, "sweepsW");
+		if (idx >= 0) prm.sweeps_w = d.parameters[idx].value;
+		// (the engine's own rule, asked here so that a refusal comes before any device work)
+		if (const char* why = nmfamd::hals_sweeps_fault(prm.sweeps_h, prm.sweeps_w, d.algorithm == NmfAlgorithm::HALS)) {
+			log_error((std::string("[ERROR] ") + why).c_str());
+			return ResultType::ErrorInvalidArgument;
+		}
+	}
+	{
 		// "missingValues" = 1 (docs/MISSING.md): the objective over the observed entries only -- the stored entries of a sparse V, the non-NaN entries of a dense
 		// one.  Multiplicative with the Frobenius objective, one GPU, padded rank <= 256 (the sparse kernels), and a start that does not read V as if a missing
 		// entry were a zero (the host-side k-means, mean-column, EInNMF and NNDSVD starts do)

@@ -333,6 +333,11 @@ int nmfamd_engine_set_hals_penalties(nmfamd_engine* e, double l1W, double l1H, d
 	return dispatch(e, set, set);
 }
 
+int nmfamd_engine_set_hals_sweeps(nmfamd_engine* e, int sweeps_h, int sweeps_w) {
+	auto set = [&](auto& g) { return g.set_hals_sweeps(sweeps_h, sweeps_w); };
+	return dispatch(e, set, set);
+}
+
 int nmfamd_engine_synchronize(nmfamd_engine* e) {
 	if (!e) return NMFAMD_INVALID_ARGUMENT;
 	hipStream_t s = e->elem_bytes == 4 ? e->f->stream() : e->d->stream();
@@ -851,7 +856,9 @@ int nmfamd_op_factor_passes_f32(const float* P, long ldp, int r, int len, const 
 // they like into the padding.  No argument checks beyond the buffer sizes: the launchers decide what they accept.
 namespace {
 template <typename T>
-int op_hals_sweep(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part, int* parts, T l1 = T(0), T l2 = T(0)) {
+int op_hals_sweep(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part, int* parts, T l1 = T(0), T l2 = T(0),
+                  int sweeps = 0) {
+	// sweeps == 0: the single-sweep launcher itself (nmfamd_op_hals_sweep_*, _pen_*); otherwise launch_panel_sweeps_hals, which decides about the count
 	if (!P || !slabs || !G || !parts || S < 1 || RP < 1 || RP > 4096 || len_pad < 1 || slab_stride < (long)len_pad * RP) return NMFAMD_INVALID_ARGUMENT;
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	const int np = panel_sweep_hals_parts(RP, sizeof(T), len_pad);
@@ -863,8 +870,10 @@ int op_hals_sweep(T* P, const T* slabs, int S, long slab_stride, const T* G, int
 	    hipMemcpy(dG.p, G, sizeof(T) * (size_t)RP * RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (ps && hipMemcpy(dPs.p, ps, sizeof(T) * (size_t)len_pad, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (sumsq_part && np > 0 && hipMemcpy(dSq.p, sumsq_part, sizeof(T) * (size_t)np * RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
-	const hipError_t err = launch_panel_sweep_hals<T>((T*)dP.p, (const T*)dS.p, S, slab_stride, (const T*)dG.p, RP, r, len_pad, len_valid,
-	                                                  ps ? (T*)dPs.p : nullptr, sumsq_part ? (T*)dSq.p : nullptr, nullptr, l1, l2);
+	const hipError_t err = sweeps == 0 ? launch_panel_sweep_hals<T>((T*)dP.p, (const T*)dS.p, S, slab_stride, (const T*)dG.p, RP, r, len_pad, len_valid,
+	                                                                ps ? (T*)dPs.p : nullptr, sumsq_part ? (T*)dSq.p : nullptr, nullptr, l1, l2)
+	                                   : launch_panel_sweeps_hals<T>((T*)dP.p, (const T*)dS.p, S, slab_stride, (const T*)dG.p, RP, r, len_pad, len_valid,
+	                                                                 ps ? (T*)dPs.p : nullptr, sumsq_part ? (T*)dSq.p : nullptr, nullptr, l1, l2, sweeps);
 	if (err == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
 	if (err != hipSuccess || hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (hipMemcpy(P, dP.p, panel, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
@@ -1059,6 +1068,18 @@ int nmfamd_op_hals_sweep_pen_f32(float* P, const float* slabs, int S, long slab_
 int nmfamd_op_hals_sweep_pen_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid, double* ps,
                                  double* sumsq_part, int* parts, double l1, double l2) {
 	return op_hals_sweep<double>(P, slabs, S, slab_stride, G, RP, r, len_pad, len_valid, ps, sumsq_part, parts, l1, l2);
+}
+
+int nmfamd_op_hals_sweeps_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid, float* ps,
+                              float* sumsq_part, int* parts, float l1, float l2, int sweeps) {
+	if (sweeps == 0) return NMFAMD_INVALID_ARGUMENT;      // (0 is op_hals_sweep's own mark for the single-sweep launcher)
+	return op_hals_sweep<float>(P, slabs, S, slab_stride, G, RP, r, len_pad, len_valid, ps, sumsq_part, parts, l1, l2, sweeps);
+}
+
+int nmfamd_op_hals_sweeps_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid, double* ps,
+                              double* sumsq_part, int* parts, double l1, double l2, int sweeps) {
+	if (sweeps == 0) return NMFAMD_INVALID_ARGUMENT;
+	return op_hals_sweep<double>(P, slabs, S, slab_stride, G, RP, r, len_pad, len_valid, ps, sumsq_part, parts, l1, l2, sweeps);
 }
 
 int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad, const float* sumsq_part, int parts) {

@@ -178,6 +178,7 @@ Status Engine<T>::allocate() {
 	if (m_ <= 0 || n_ <= 0 || r_ <= 0 || alg_ < 0 || alg_ > ALG_HALS) return ST_INVALID;
 	if (alg_ == ALG_HALS && !panel_sweep_hals_available(RP_, sizeof(T))) { last_error_ = "HALS: no sweep kernel for this padded rank (fp32: 64 ... 512, fp64: multiples of 64 up to 512)"; return ST_INVALID; }
 	if (Status s = set_hals_penalties(prm_.l1W, prm_.l1H, prm_.l2W, prm_.l2H)) return s;      // (values that came with the parameters: the setter's checks, and its rounding of prm_ to T)
+	if (const char* why = hals_sweeps_fault(prm_.sweeps_h, prm_.sweeps_w, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = beta_dense_fault(prm_, alg_ == ALG_MU, r_, row_blocks_)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = weighted_fault(prm_)) { last_error_ = why; return ST_INVALID; }
 	beta_dense_ = prm_.is_beta_dense();
@@ -1377,7 +1378,9 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 		// writes them.  No split image of the new H: the next product packs its operand itself.
 		if (Status s = product_h(F, nullptr, x3_ && wx3_valid_ && F == Wt_)) return s;
 		// (penalties: G and the slabs stay raw -- ps and the trace of the error term read them)
-		HIPX(launch_panel_sweep_hals<T>(H_, slabs_, S, slab_stride_, G_, RP_, r_, (int)npad_, n_, compute_error ? psN_ : nullptr, nullptr, stream_, (T)prm_.l1H, (T)prm_.l2H));
+		// (sweeps_h sweeps against this one G and these slabs, in one launch; one sweep is launch_panel_sweep_hals)
+		HIPX(launch_panel_sweeps_hals<T>(H_, slabs_, S, slab_stride_, G_, RP_, r_, (int)npad_, n_, compute_error ? psN_ : nullptr, nullptr, stream_, (T)prm_.l1H, (T)prm_.l2H,
+		                                 (int)prm_.sweeps_h));
 		hx3_valid_ = false;
 		return ST_OK;
 	}
@@ -2123,6 +2126,13 @@ Status Engine<T>::set_hals_penalties(double l1W, double l1H, double l2W, double 
 }
 
 template <typename T>
+Status Engine<T>::set_hals_sweeps(int h, int w) {
+	if (const char* why = hals_sweeps_fault((double)h, (double)w, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
+	prm_.sweeps_h = h; prm_.sweeps_w = w;
+	return ST_OK;
+}
+
+template <typename T>
 Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 	const T eps = std::numeric_limits<T>::epsilon();
 	timing_now_ = timing_ && (timing_iter_++ % timing_stride_ == 0);
@@ -2221,9 +2231,9 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				wx3_valid_ = false;
 				gram_w_ready_ = false;
 				if (prm_.hals_penalised()) {
-					HIPX(launch_panel_sweep_hals<T>(Wt_, slabs_, S, slab_stride_, HHt_, RP_, r_, (int)mpad_, m_, nullptr, nullptr, stream_, (T)prm_.l1W, (T)prm_.l2W));
+					HIPX(launch_panel_sweeps_hals<T>(Wt_, slabs_, S, slab_stride_, HHt_, RP_, r_, (int)mpad_, m_, nullptr, nullptr, stream_, (T)prm_.l1W, (T)prm_.l2W, (int)prm_.sweeps_w));
 				} else {
-					HIPX(launch_panel_sweep_hals<T>(Wt_, slabs_, S, slab_stride_, HHt_, RP_, r_, (int)mpad_, m_, nullptr, sumsq_part_, stream_));
+					HIPX(launch_panel_sweeps_hals<T>(Wt_, slabs_, S, slab_stride_, HHt_, RP_, r_, (int)mpad_, m_, nullptr, sumsq_part_, stream_, T(0), T(0), (int)prm_.sweeps_w));
 					HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, panel_sweep_hals_parts(RP_, sizeof(T), (int)mpad_), stream_));
 				}
 			} else if (!ls_family) {

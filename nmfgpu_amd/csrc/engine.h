@@ -29,7 +29,10 @@ struct AlgorithmParams {
 	// L1 / L2 penalties on W and on H; all 0: the unpenalised iteration.  HALS (docs/HALS.md: scikit-learn's coordinate descent) and the dense divergence updates
 	// (docs/DIVERGENCE.md: scikit-learn's solver="mu") take them, no other engine.  Engine::set_hals_penalties changes them between iterations.
 	double l1W = 0, l1H = 0, l2W = 0, l2H = 0;
-	double dense_compute = 0;   // 1 with divergence = 1: the KL update on a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) instead of over the stored entries
+	// HALS: sweeps per product in the H step and in the W step (accelerated HALS, docs/HALS.md "Inner sweeps"); integers in 1 ... 64, (1, 1): the plain iteration.
+	// Engine::set_hals_sweeps changes them between iterations.
+	double sweeps_h = 1, sweeps_w = 1;
+	double dense_compute = 0;  // 1 with divergence = 1: the KL update on a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) instead of over the stored entries
 	double beta_value = 0;      // divergence = 3: the beta of the divergence, any finite value (0 and 1 run the Itakura-Saito and dense KL engines as they are)
 	double weighted = 0;        // 1 on a dense divergence engine: per-entry weights uploaded beside V (upload_dense_weighted; kernels_beta_weighted.hip, docs/DIVERGENCE.md)
 	double mixed_precision = 0; // 1 on a dense divergence fp32 engine: the operands of the fused half-step's products rounded to bf16 (kernels_beta_bf16.hip, docs/DIVERGENCE.md)
@@ -56,6 +59,16 @@ inline const char* hals_penalties_fault(double l1W, double l1H, double l2W, doub
 		any = any || x != 0;
 	}
 	if (any && !takes_penalties) return "HALS penalties: only the HALS algorithm takes l1W / l1H / l2W / l2H";
+	return nullptr;
+}
+
+// What the sweep counts of accelerated HALS must satisfy, stated once for Engine::set_hals_sweeps and nmfgpu::compute (which reads them from Parameters, as
+// doubles): nullptr, or why not.
+inline const char* hals_sweeps_fault(double sweeps_h, double sweeps_w, bool is_hals) {
+	for (double x : {sweeps_h, sweeps_w}) {
+		if (!(x >= HALS_SWEEPS_MIN && x <= HALS_SWEEPS_MAX) || x != (double)(int)x) return "HALS sweeps: sweepsH and sweepsW must be integers in 1 ... 64";
+	}
+	if ((sweeps_h != 1 || sweeps_w != 1) && !is_hals) return "HALS sweeps: only the HALS algorithm takes sweepsH / sweepsW other than 1";
 	return nullptr;
 }
 
@@ -158,6 +171,9 @@ public:
 	// HALS: the penalties of the iterations that follow (>= 0 and finite; all 0: the unpenalised iteration, normalisation included).  Valid any time
 	// between iterations.  ST_INVALID with last_error() for a bad value, and for a non-zero one on an engine of another algorithm.
 	Status set_hals_penalties(double l1W, double l1H, double l2W, double l2H);
+	// HALS: sweeps per product of the iterations that follow, h in the H step and w in the W step (1 ... 64; (1, 1): the plain iteration).  Valid any time between
+	// iterations.  ST_INVALID with last_error() for a count out of range, and for a count other than 1 on an engine of another algorithm.
+	Status set_hals_sweeps(int h, int w);
 
 	// Split form for column-sharded multi-GPU runs (exchange = device buffer of exchange_count()
 	// elements: the local (V H^T)^T panel followed by the local H H^T):

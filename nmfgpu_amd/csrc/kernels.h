@@ -275,6 +275,13 @@ int panel_sweep_hals_parts(int RP, size_t elem, int len_pad);
 template <typename T>
 hipError_t launch_panel_sweep_hals(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part,
                                    hipStream_t stream, T l1 = T(0), T l2 = T(0));
+// Accelerated HALS (kernels_hals_multi.hip; docs/HALS.md, "Inner sweeps"): `sweeps` sweeps in a row against the same G and slabs, each from the result of the one
+// before, in one launch; ps and sumsq_part from the final state.  sweeps outside HALS_SWEEPS_MIN ... HALS_SWEEPS_MAX: hipErrorInvalidValue; sweeps == 1 is
+// launch_panel_sweep_hals, the same kernel as before the counts existed.
+constexpr int HALS_SWEEPS_MIN = 1, HALS_SWEEPS_MAX = 64;
+template <typename T>
+hipError_t launch_panel_sweeps_hals(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part,
+                                    hipStream_t stream, T l1, T l2, int sweeps);
 // W(:, c) <- W(:, c) / d(c), H(c, :) <- H(c, :) d(c) where d(c) = ||W(:, c)|| > 0, d from `parts` vectors of partial sums of squares (W H unchanged);
 // sumsq_part needs RP elements of scratch behind the partials
 template <typename T>

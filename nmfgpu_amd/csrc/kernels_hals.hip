@@ -23,28 +23,11 @@
 
 #include <cmath>
 
+#include "hals_geom.h"
 #include "kernels.h"
 #include "split3.h"
 
 namespace nmfamd {
-
-template <typename T, int RP>
-struct HalsShape;
-// L: lanes per column (a power of two, E = RP / L entries per lane: 8 ... 16); C: columns per lane group
-template <int RP> struct HalsShape<float, RP> { static constexpr int L = RP <= 64 ? 4 : RP <= 128 ? 8 : RP <= 256 ? 16 : 32; static constexpr int C = RP <= 128 ? 1 : 2; };
-template <int RP> struct HalsShape<double, RP> { static constexpr int L = RP <= 64 ? 4 : RP <= 128 ? 8 : RP <= 256 ? 16 : 32; static constexpr int C = RP <= 128 ? 1 : 2; };
-
-constexpr int HALS_THREADS = 256;
-
-template <typename T, int RP>
-struct HalsGeom {
-	static constexpr int L = HalsShape<T, RP>::L, C = HalsShape<T, RP>::C, E = RP / L;
-	static constexpr int GROUPS = HALS_THREADS / L, COLS = GROUPS * C;
-	// rows of G per LDS chunk: all of G where it fits 64 KiB
-	static constexpr int KC = (int)(65536 / (RP * sizeof(T))) < RP ? (int)(65536 / (RP * sizeof(T))) : RP;
-	static_assert(RP % L == 0 && E <= 16, "entries per lane");
-	static_assert(COLS <= KC && 128 % COLS == 0, "the sum-of-squares staging reuses the G chunk; workgroups tile 128-column panels");
-};
 
 template <typename T, int RP, bool PEN>
 __global__ __launch_bounds__(HALS_THREADS) void k_sweep_hals(T* __restrict__ P, const T* __restrict__ slabs, int S, long slab_stride, const T* __restrict__ G,

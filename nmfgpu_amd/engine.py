@@ -73,6 +73,13 @@ def _ld(a: np.ndarray) -> int:
     return a.strides[1] // a.itemsize if a.shape[1] > 1 else max(a.shape[0], 1)
 
 
+def _count(v) -> int:
+    """A sweep count as the C int it travels as; anything that is not a whole number is refused here, since the C side would only see it truncated."""
+    if isinstance(v, bool) or int(v) != v:
+        raise ValueError(f"a sweep count must be an integer, got {v!r}")
+    return int(v)
+
+
 class Engine:
     """One factorisation resident on the current HIP device (see include/nmfgpu_amd.h)."""
 
@@ -80,7 +87,7 @@ class Engine:
                  lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence: str = "frobenius",
                  sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False,
                  l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None, weighted: bool = False, mixed_precision: bool = False,
-                 batch_size=None, forget_factor=0.7):
+                 batch_size=None, forget_factor=0.7, sweeps_h: int = 1, sweeps_w: int = 1):
         """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V),
         "is" (Itakura-Saito, always dense: every entry of V > 0) or "beta" (the beta-divergence at `beta`, any finite value, always dense: scikit-learn's
         solver="mu" with beta_loss=beta; beta=0.0 and beta=1.0 are the "is" and the dense "kl" engines; beta <= 0 needs every entry of V > 0) --
@@ -104,7 +111,10 @@ class Engine:
         columns of V (docs/DIVERGENCE.md, "Minibatch update").  One iterate() step is one pass over the column blocks [0, b), [b, 2 b), ... in order; W moves
         once per block, from numerator and denominator panels accumulated with rho = forget_factor^(min(b, n) / n); set_factors and randomize start them again.
         No normalisation, no constant_w; frobenius / rmsd / divergence_value refer to (W, H) after the pass.  None or 0: the full-batch engine, where
-        forget_factor is not looked at."""
+        forget_factor is not looked at.
+
+        sweeps_h, sweeps_w ("hals" only; 1 ... 64): accelerated HALS, that many sweeps per product in the H step and in the W step (docs/HALS.md, "Inner
+        sweeps"); see set_sweeps."""
         if not batch_size:
             batch_size, forget_factor = 0.0, 0.0
         self._bind(m, n, r, dtype)
@@ -116,7 +126,7 @@ class Engine:
                           params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0, "is": 2.0, "beta": 3.0}[divergence],
                                   float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
                                   float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted), float(mixed_precision), float(batch_size), float(forget_factor)],
-                          penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)])
+                          penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)], sweeps=[_count(sweeps_h), _count(sweeps_w)])
         self._create()
 
     def _bind(self, m, n, r, dtype):
@@ -161,6 +171,8 @@ class Engine:
         # (the penalties are engine state, not part of nmfamd_params: an engine recreated by _upload gets them again)
         try:
             self.set_penalties(*c["penalties"])
+            if c["sweeps"] != [1, 1]:      # (the default needs no call: a library from before the counts has no such entry)
+                self.set_sweeps(*c["sweeps"])
         except EngineError:
             self.close()
             raise
@@ -259,6 +271,15 @@ class Engine:
         self._check(self._lib.nmfamd_engine_set_hals_penalties(self._h, *(C.c_double(v) for v in vals)), "set_hals_penalties")
         if self._ctor is not None:
             self._ctor["penalties"] = vals
+
+    def set_sweeps(self, h: int = 1, w: int = 1):
+        """HALS: the iterations that follow run h sweeps per H step and w sweeps per W step against one set of products each (accelerated HALS,
+        nmfamd_engine_set_hals_sweeps; docs/HALS.md, "Inner sweeps").  Integers in 1 ... 64; (1, 1) restores the plain iteration.  Valid between
+        iterations; with constant_w only h matters."""
+        vals = [_count(h), _count(w)]
+        self._check(self._lib.nmfamd_engine_set_hals_sweeps(self._h, *(C.c_int(v) for v in vals)), "set_hals_sweeps")
+        if self._ctor is not None:
+            self._ctor["sweeps"] = vals
 
     @property
     def frobenius(self) -> float:
@@ -653,7 +674,7 @@ def op_tri_update(P: np.ndarray, num: np.ndarray, Q: np.ndarray, *, old_colsq: O
 
 
 def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_valid: int, *, ps: Optional[np.ndarray] = None,
-                  sumsq_part: Optional[np.ndarray] = None, penalties: Optional[tuple] = None):
+                  sumsq_part: Optional[np.ndarray] = None, penalties: Optional[tuple] = None, _sweeps: Optional[int] = None):
     """One launch of the HALS sweep (nmfamd_op_hals_sweep_*; with penalties = (l1, l2) through nmfamd_op_hals_sweep_pen_*, zeros included) on padded arrays: P (len_pad, RP) panel columns, slabs (S, slab_stride) with
     slab_stride >= len_pad * RP (slab s is the first len_pad * RP values of row s; the rest of the row is a gap the kernel must not read), G (RP, RP).
     ps (len_pad values) and sumsq_part ((len_pad // 16) * RP values), when given, are copied in before the launch, so entries the kernel leaves
@@ -677,7 +698,9 @@ def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_v
             raise ValueError("sumsq_part must hold (len_pad // 16) * RP values")
     parts = C.c_int(0)
     lib, real = library(), (C.c_float if dt == np.float32 else C.c_double)
-    if penalties is None:
+    if _sweeps is not None:      # (op_hals_sweeps)
+        fn, extra = (lib.nmfamd_op_hals_sweeps_f32 if dt == np.float32 else lib.nmfamd_op_hals_sweeps_f64), (real(penalties[0]), real(penalties[1]), C.c_int(_sweeps))
+    elif penalties is None:
         fn, extra = (lib.nmfamd_op_hals_sweep_f32 if dt == np.float32 else lib.nmfamd_op_hals_sweep_f64), ()
     else:
         fn, extra = (lib.nmfamd_op_hals_sweep_pen_f32 if dt == np.float32 else lib.nmfamd_op_hals_sweep_pen_f64), (real(penalties[0]), real(penalties[1]))
@@ -688,6 +711,13 @@ def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_v
         raise EngineError(st, "nmfamd_op_hals_sweep")
     k = parts.value
     return {"P": P, "ps": ps, "sumsq_part": None if sumsq_part is None else sumsq_part[:k * RP].reshape(k, RP), "parts": k}
+
+
+def op_hals_sweeps(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_valid: int, sweeps: int, *, l1=0.0, l2=0.0, ps: Optional[np.ndarray] = None,
+                   sumsq_part: Optional[np.ndarray] = None):
+    """One launch of `sweeps` HALS sweeps in a row with the penalties (l1, l2) (nmfamd_op_hals_sweeps_*; kernels_hals_multi.hip), on the arrays of op_hals_sweep
+    and with its result; ps and sumsq_part describe the final state.  sweeps = 1 is op_hals_sweep's launch; outside 1 ... 64 it is refused."""
+    return op_hals_sweep(P, slabs, G, r, len_valid, ps=ps, sumsq_part=sumsq_part, penalties=(l1, l2), _sweeps=_count(sweeps))
 
 
 def op_beta_half_step(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: int, out_valid: int, red_valid: int, beta: int, form: int = 0, *,

@@ -3,9 +3,10 @@
 
 Prints, per algorithm: the wall time per iteration of plain iterations and of error iterations (stream synchronised around each timed block), the
 event-timed H-side / W-side product launches (nmfamd_engine_kernel_timing_read3), and the relative error ||V - W H|| / ||V|| after 10 and 100
-iterations.  "hals-pen" is HALS with l1W = l1H = 0.05, l2W = l2H = 0.01.
+iterations.  "hals-pen" is HALS with l1W = l1H = 0.05, l2W = l2H = 0.01.  --sweeps-h / --sweeps-w (default 1 / 1) other than 1 add a row "sparse hals h,w":
+accelerated HALS with that many sweeps per product (docs/HALS.md, "Inner sweeps").
 
-    python tools/time_hals_sparse.py [--iters 50] [--warmup 10] [--rows 100000] [--cols 20000]
+    python tools/time_hals_sparse.py [--iters 50] [--warmup 10] [--rows 100000] [--cols 20000] [--sweeps-h 4 --sweeps-w 4]
     python tools/time_hals_sparse.py --kernels      a child run of 40 plain sparse HALS iterations under `rocprofv3 --kernel-trace`: launches and
                                                     median duration per kernel and grid size (set-up launches included: they show once or twice)
 """
@@ -70,6 +71,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--rows", type=int, default=bench.C3["rows"])
     ap.add_argument("--cols", type=int, default=bench.C3["columns"])
+    ap.add_argument("--sweeps-h", type=int, default=1)
+    ap.add_argument("--sweeps-w", type=int, default=1)
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--trace-child", action="store_true")
     a = ap.parse_args()
@@ -81,8 +84,10 @@ def main():
     m, n, r = W.shape[0], H.shape[1], W.shape[1]
     norm_v = float(np.sqrt((val.astype(np.float64) ** 2).sum()))
     print(f"CSR {m} x {n}, nnz {len(val)} ({100.0 * len(val) / m / n:.2f} %), r = {r}, fp32, ||V|| = {norm_v:.4f}")
-    for name, alg, kw in (("sparse-frobenius mu", "mu", {}), ("sparse hals", "hals", {}),
-                          ("sparse hals-pen", "hals", dict(l1_w=0.05, l1_h=0.05, l2_w=0.01, l2_h=0.01))):
+    runs = [("sparse-frobenius mu", "mu", {}), ("sparse hals", "hals", {}), ("sparse hals-pen", "hals", dict(l1_w=0.05, l1_h=0.05, l2_w=0.01, l2_h=0.01))]
+    if (a.sweeps_h, a.sweeps_w) != (1, 1):
+        runs.append((f"sparse hals {a.sweeps_h},{a.sweeps_w}", "hals", dict(sweeps_h=a.sweeps_h, sweeps_w=a.sweeps_w)))
+    for name, alg, kw in runs:
         eng = na.Engine(m, n, r, alg, sparse_compute=True, **kw)
         eng.upload_sparse(1, val, ptr, idx, 0)
         eng.set_factors(W, H)
