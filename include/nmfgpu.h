@@ -95,7 +95,7 @@ enum class NmfAlgorithm {
 	ACLS,            // ALS with ridge terms lambdaW / lambdaH
 	AHCLS,           // ACLS with Hoyer sparseness terms alphaW / alphaH
 	nsNMF,           // non-smooth NMF (theta)
-	HALS,            // hierarchical alternating least squares / coordinate descent (extension: optional penalties "l1W", "l1H", "l2W", "l2H", sweeps per product "sweepsH", "sweepsW", "sparseCompute"; single GPU)
+	HALS,            // hierarchical alternating least squares / coordinate descent (extension: optional penalties "l1W", "l1H", "l2W", "l2H", sweeps per product "sweepsH", "sweepsW", their per-column stopping tolerance "sweepsTolerance", "sparseCompute"; single GPU)
 };
 
 // ref: include/nmfgpu.h:117-126.  Console output level (process wide).

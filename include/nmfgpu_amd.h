@@ -202,6 +202,17 @@ NMFAMD_API int nmfamd_engine_set_hals_penalties(nmfamd_engine* e, double l1W, do
  * Valid any time between iterations; takes effect at the next nmfamd_engine_iterate.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error) for a count
  * outside 1 ... 64, and for a count other than 1 on any other engine. */
 NMFAMD_API int nmfamd_engine_set_hals_sweeps(nmfamd_engine* e, int sweeps_h, int sweeps_w);
+/* HALS engines: per-column dynamic stopping of the inner sweeps (docs/HALS.md, "Dynamic stopping").  With delta in (0, 1) the counts of
+ * nmfamd_engine_set_hals_sweeps become maximum counts: within one step a column of the swept panel is frozen after its sweep t when the squared step of that
+ * sweep is at most delta^2 times the squared step of its first sweep, and is not stepped again.  0, the default, runs the static counts, bit for bit.  Valid any
+ * time between iterations; takes effect at the next nmfamd_engine_iterate.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error) for a negative or
+ * non-finite value, for a value of 1 or more, and for a non-zero value on any other engine. */
+NMFAMD_API int nmfamd_engine_set_hals_sweep_tolerance(nmfamd_engine* e, double delta);
+/* HALS engines: the sweeps applied to each column of H (which = 0: n entries) or row of W (which = 1: m entries) by the most recent step of that factor, 1 ...
+ * the maximum count (the maximum itself for every entry while the tolerance is 0).  Synchronises.  Returns the number of entries copied, or a negative value: on
+ * an engine of another algorithm, for another `which`, for capacity below n (m), and before any step of that factor -- with constant W no W step runs, so
+ * which = 1 keeps returning what it returned before. */
+NMFAMD_API long nmfamd_engine_hals_sweep_counts(nmfamd_engine* e, int which, int* out, long capacity);
 /* Frobenius norm / RMSD of the most recent error iteration (IAlgorithm::frobeniusNorm / rmsd). */
 NMFAMD_API double nmfamd_engine_frobenius(nmfamd_engine* e);
 NMFAMD_API double nmfamd_engine_rmsd(nmfamd_engine* e);
@@ -451,6 +462,13 @@ NMFAMD_API int nmfamd_op_hals_sweeps_f32(float* P, const float* slabs, int S, lo
                                          float* ps, float* sumsq_part, int* parts, float l1, float l2, int sweeps);
 NMFAMD_API int nmfamd_op_hals_sweeps_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid,
                                          double* ps, double* sumsq_part, int* parts, double l1, double l2, int sweeps);
+/* At most `sweeps` sweeps with per-column dynamic stopping at the tolerance tol (kernels_hals_dyn.hip; docs/HALS.md, "Dynamic stopping"), always through
+ * k_sweeps_hals_dyn, one sweep included.  counts (len_pad values, may be NULL): the sweeps applied to each column, 0 on padding.  NMFAMD_INVALID_ARGUMENT also
+ * for tol outside (0, 1), NaN included. */
+NMFAMD_API int nmfamd_op_hals_sweeps_dyn_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid,
+                                             float* ps, float* sumsq_part, int* parts, float l1, float l2, int sweeps, double tol, int* counts);
+NMFAMD_API int nmfamd_op_hals_sweeps_dyn_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid,
+                                             double* ps, double* sumsq_part, int* parts, double l1, double l2, int sweeps, double tol, int* counts);
 /* The HALS column normalisation on host panels Wt [mpad][RP] and H [npad][RP] (both updated in place) from parts x RP partial sums of squares:
  * d(c) = sqrt(sum of the parts); where d(c) > 0, Wt(:, c) / d(c) and H(:, c) * d(c). */
 NMFAMD_API int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad, const float* sumsq_part, int parts);

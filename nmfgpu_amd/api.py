@@ -265,7 +265,8 @@ def compute(V, W: np.ndarray, H: np.ndarray, *, algorithm: NmfAlgorithm = NmfAlg
     start, one GPU, at most 256 features; the reported Frobenius error / RMSD are those over the observed entries.
 
     ``parameters={"sweepsH": 3, "sweepsW": 2}`` with the HALS algorithm: accelerated HALS, that many sweeps per product in the H and in the W
-    step (integers in 1 ... 64, absent = 1; docs/HALS.md, "Inner sweeps"), next to the penalties "l1W", "l1H", "l2W", "l2H"."""
+    step (integers in 1 ... 64, absent = 1; docs/HALS.md, "Inner sweeps"), next to the penalties "l1W", "l1H", "l2W", "l2H".  ``"sweepsTolerance": 0.1``
+    makes the counts maximum counts: every column stops sweeping by itself (docs/HALS.md, "Dynamic stopping"; in [0, 1), absent = 0)."""
     if W.dtype != H.dtype:
         raise TypeError("W and H must share a dtype")
     d = NmfDescription()

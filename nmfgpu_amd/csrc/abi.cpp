@@ -298,6 +298,14 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 			log_error((std::string("[ERROR] ") + why).c_str());
 			return ResultType::ErrorInvalidArgument;
 		}
+		// "sweepsTolerance": the tolerance of the per-column dynamic stopping rule (docs/HALS.md, "Dynamic stopping"); absent = 0 (static counts), in [0, 1),
+		// other than 0 only with HALS -- the counts above are then maximum counts
+		idx = parameter_index(d.parameters, d.numParameters, "sweepsTolerance");
+		if (idx >= 0) prm.sweep_tolerance = d.parameters[idx].value;
+		if (const char* why = nmfamd::hals_sweep_tolerance_fault(prm.sweep_tolerance, d.algorithm == NmfAlgorithm::HALS)) {
+			log_error((std::string("[ERROR] ") + why).c_str());
+			return ResultType::ErrorInvalidArgument;
+		}
 	}
 	{
 		// "missingValues" = 1 (docs/MISSING.md): the objective over the observed entries only -- the stored entries of a sparse V, the non-NaN entries of a dense

@@ -138,6 +138,8 @@ Engine<T>::~Engine() {
 	T* bufs[] = {V_, Vt_, Om_, Omt_, Wt_, H_, Ws_, Hs_, slabs_, numW_, Wold_, G_, G2_, HHt_, Qinv_, gram_part_, sumsq_part_, psN_, stage_};   // (psR_ lives behind psN_)
 	for (T* b : bufs) if (b) (void)hipFree(b);
 	if (inv_work_) (void)hipFree(inv_work_);
+	if (hals_counts_h_) (void)hipFree(hals_counts_h_);
+	if (hals_counts_w_) (void)hipFree(hals_counts_w_);
 	if (range_flag_) (void)hipFree(range_flag_);
 	{
 		void* sp[] = {csr_ptr_, csr_idx_, csc_ptr_, csc_idx_, csc_from_csr_, csr_val_, csc_val_, q_, q2_, t_vwh_, t_kl_, rowsum_part_, sW_, sH_, kl_scale_, csr_bptr_, csc_bptr_, kl_part_, kl_tpart_, msq_part_, beta_den_, beta_tpart_, online_A_, online_B_};
@@ -179,6 +181,7 @@ Status Engine<T>::allocate() {
 	if (alg_ == ALG_HALS && !panel_sweep_hals_available(RP_, sizeof(T))) { last_error_ = "HALS: no sweep kernel for this padded rank (fp32: 64 ... 512, fp64: multiples of 64 up to 512)"; return ST_INVALID; }
 	if (Status s = set_hals_penalties(prm_.l1W, prm_.l1H, prm_.l2W, prm_.l2H)) return s;      // (values that came with the parameters: the setter's checks, and its rounding of prm_ to T)
 	if (const char* why = hals_sweeps_fault(prm_.sweeps_h, prm_.sweeps_w, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
+	if (const char* why = hals_sweep_tolerance_fault(prm_.sweep_tolerance, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = beta_dense_fault(prm_, alg_ == ALG_MU, r_, row_blocks_)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = weighted_fault(prm_)) { last_error_ = why; return ST_INVALID; }
 	beta_dense_ = prm_.is_beta_dense();
@@ -427,6 +430,13 @@ Status Engine<T>::allocate() {
 	HIPX(dalloc(&gram_part_, rr * gram_parts_));
 	HIPX(dalloc(&sumsq_part_, ((long)std::max({panel_update_parts(RP_, sizeof(T), (int)mpad_), (int)(mpad_ / panel_update_rows(RP_, sizeof(T))),
 	                                           alg_ == ALG_HALS ? panel_sweep_hals_parts(RP_, sizeof(T), (int)mpad_) : 0}) + 16) * RP_));
+	if (alg_ == ALG_HALS) {
+		// the sweep counts of the most recent H and W step (dynamic stopping, docs/HALS.md)
+		HIPX(hipMalloc((void**)&hals_counts_h_, sizeof(int) * (size_t)npad_));
+		HIPX(hipMemsetAsync(hals_counts_h_, 0, sizeof(int) * (size_t)npad_, stream_));
+		HIPX(hipMalloc((void**)&hals_counts_w_, sizeof(int) * (size_t)mpad_));
+		HIPX(hipMemsetAsync(hals_counts_w_, 0, sizeof(int) * (size_t)mpad_, stream_));
+	}
 	// the two error-term vectors share one allocation (and one pinned landing buffer): ONE device-to-host copy per error iteration
 	ps_stride_ = std::max<long>(npad_, RP_);
 	HIPX(dalloc(&psN_, ps_stride_ + RP_));
@@ -1379,8 +1389,8 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 		if (Status s = product_h(F, nullptr, x3_ && wx3_valid_ && F == Wt_)) return s;
 		// (penalties: G and the slabs stay raw -- ps and the trace of the error term read them)
 		// (sweeps_h sweeps against this one G and these slabs, in one launch; one sweep is launch_panel_sweep_hals)
-		HIPX(launch_panel_sweeps_hals<T>(H_, slabs_, S, slab_stride_, G_, RP_, r_, (int)npad_, n_, compute_error ? psN_ : nullptr, nullptr, stream_, (T)prm_.l1H, (T)prm_.l2H,
-		                                 (int)prm_.sweeps_h));
+		// (a sweep tolerance: the counts are maximum counts and every column stops by itself, kernels_hals_dyn.hip)
+		if (Status s = hals_sweeps(false, H_, G_, S, (int)npad_, n_, compute_error ? psN_ : nullptr, nullptr, (T)prm_.l1H, (T)prm_.l2H)) return s;
 		hx3_valid_ = false;
 		return ST_OK;
 	}
@@ -2133,6 +2143,49 @@ Status Engine<T>::set_hals_sweeps(int h, int w) {
 }
 
 template <typename T>
+Status Engine<T>::set_hals_sweep_tolerance(double delta) {
+	if (const char* why = hals_sweep_tolerance_fault(delta, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
+	prm_.sweep_tolerance = delta;
+	return ST_OK;
+}
+
+// The sweeps of one HALS step against slabs_ and G.  Tolerance 0: launch_panel_sweeps_hals, as before the tolerance existed -- the counts of the step are then
+// the static count, which nobody has to launch anything for: they are written when somebody asks (hals_sweep_counts).  Tolerance > 0 and a maximum of one sweep:
+// the same launch (there is nothing to decide) and counts of 1.  Otherwise the dynamic kernel, which writes the counts itself.
+template <typename T>
+Status Engine<T>::hals_sweeps(bool w_step, T* P, const T* G, int S, int len_pad, int len_valid, T* ps, T* sumsq_part, T l1, T l2) {
+	const int sweeps = (int)(w_step ? prm_.sweeps_w : prm_.sweeps_h);
+	int* counts = w_step ? hals_counts_w_ : hals_counts_h_;
+	(w_step ? hals_counts_w_valid_ : hals_counts_h_valid_) = true;
+	if (prm_.sweep_tolerance > 0 && sweeps > 1) {
+		HIPX(launch_panel_sweeps_hals_dyn<T>(P, slabs_, S, slab_stride_, G, RP_, r_, len_pad, len_valid, ps, sumsq_part, stream_, l1, l2, sweeps, prm_.sweep_tolerance, counts));
+		(w_step ? hals_static_w_ : hals_static_h_) = 0;
+		return ST_OK;
+	}
+	HIPX(launch_panel_sweeps_hals<T>(P, slabs_, S, slab_stride_, G, RP_, r_, len_pad, len_valid, ps, sumsq_part, stream_, l1, l2, sweeps));
+	(w_step ? hals_static_w_ : hals_static_h_) = sweeps;
+	return ST_OK;
+}
+
+template <typename T>
+long Engine<T>::hals_sweep_counts(int which, int* out, long capacity) {
+	if (alg_ != ALG_HALS) { last_error_ = "HALS sweep counts: only a HALS engine has them"; return -1; }
+	if (which != 0 && which != 1) { last_error_ = "HALS sweep counts: which has to be 0 (H) or 1 (W)"; return -1; }
+	const long len = which == 0 ? n_ : m_;
+	if (!(which == 0 ? hals_counts_h_valid_ : hals_counts_w_valid_)) { last_error_ = "HALS sweep counts: no step of this factor has run yet"; return -1; }
+	if (out == nullptr || capacity < len) { last_error_ = "HALS sweep counts: the output holds fewer than n (m) entries"; return -1; }
+	const int fixed = which == 0 ? hals_static_h_ : hals_static_w_;
+	if (fixed > 0) {      // (the step ran a fixed number of sweeps: nothing was written on the device)
+		if (hipStreamSynchronize(stream_) != hipSuccess) return -1;
+		for (long i = 0; i < len; ++i) out[i] = fixed;
+		return len;
+	}
+	if (hipMemcpyAsync(out, which == 0 ? hals_counts_h_ : hals_counts_w_, sizeof(int) * (size_t)len, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
+	    hipStreamSynchronize(stream_) != hipSuccess) { last_error_ = "HALS sweep counts: copy failed"; return -1; }
+	return len;
+}
+
+template <typename T>
 Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 	const T eps = std::numeric_limits<T>::epsilon();
 	timing_now_ = timing_ && (timing_iter_++ % timing_stride_ == 0);
@@ -2231,9 +2284,9 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				wx3_valid_ = false;
 				gram_w_ready_ = false;
 				if (prm_.hals_penalised()) {
-					HIPX(launch_panel_sweeps_hals<T>(Wt_, slabs_, S, slab_stride_, HHt_, RP_, r_, (int)mpad_, m_, nullptr, nullptr, stream_, (T)prm_.l1W, (T)prm_.l2W, (int)prm_.sweeps_w));
+					if (Status s = hals_sweeps(true, Wt_, HHt_, S, (int)mpad_, m_, nullptr, nullptr, (T)prm_.l1W, (T)prm_.l2W)) return s;
 				} else {
-					HIPX(launch_panel_sweeps_hals<T>(Wt_, slabs_, S, slab_stride_, HHt_, RP_, r_, (int)mpad_, m_, nullptr, sumsq_part_, stream_, T(0), T(0), (int)prm_.sweeps_w));
+					if (Status s = hals_sweeps(true, Wt_, HHt_, S, (int)mpad_, m_, nullptr, sumsq_part_, T(0), T(0))) return s;
 					HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, panel_sweep_hals_parts(RP_, sizeof(T), (int)mpad_), stream_));
 				}
 			} else if (!ls_family) {

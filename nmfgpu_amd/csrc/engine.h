@@ -32,6 +32,9 @@ struct AlgorithmParams {
 	// HALS: sweeps per product in the H step and in the W step (accelerated HALS, docs/HALS.md "Inner sweeps"); integers in 1 ... 64, (1, 1): the plain iteration.
 	// Engine::set_hals_sweeps changes them between iterations.
 	double sweeps_h = 1, sweeps_w = 1;
+	// HALS: the tolerance delta of the per-column dynamic stopping rule (docs/HALS.md, "Dynamic stopping"), in [0, 1); 0: static counts.  With delta > 0 the
+	// counts above are maximum counts.  Engine::set_hals_sweep_tolerance changes it between iterations.
+	double sweep_tolerance = 0;
 	double dense_compute = 0;  // 1 with divergence = 1: the KL update on a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) instead of over the stored entries
 	double beta_value = 0;      // divergence = 3: the beta of the divergence, any finite value (0 and 1 run the Itakura-Saito and dense KL engines as they are)
 	double weighted = 0;        // 1 on a dense divergence engine: per-entry weights uploaded beside V (upload_dense_weighted; kernels_beta_weighted.hip, docs/DIVERGENCE.md)
@@ -69,6 +72,13 @@ inline const char* hals_sweeps_fault(double sweeps_h, double sweeps_w, bool is_h
 		if (!(x >= HALS_SWEEPS_MIN && x <= HALS_SWEEPS_MAX) || x != (double)(int)x) return "HALS sweeps: sweepsH and sweepsW must be integers in 1 ... 64";
 	}
 	if ((sweeps_h != 1 || sweeps_w != 1) && !is_hals) return "HALS sweeps: only the HALS algorithm takes sweepsH / sweepsW other than 1";
+	return nullptr;
+}
+
+// What the tolerance of the dynamic stopping rule must satisfy, stated once for Engine::set_hals_sweep_tolerance and nmfgpu::compute: nullptr, or why not.
+inline const char* hals_sweep_tolerance_fault(double delta, bool is_hals) {
+	if (!(delta >= 0 && delta < 1)) return "HALS sweep tolerance: sweepsTolerance must be a finite value in [0, 1)";      // (NaN fails both comparisons)
+	if (delta != 0 && !is_hals) return "HALS sweep tolerance: only the HALS algorithm takes a sweepsTolerance other than 0";
 	return nullptr;
 }
 
@@ -174,6 +184,13 @@ public:
 	// HALS: sweeps per product of the iterations that follow, h in the H step and w in the W step (1 ... 64; (1, 1): the plain iteration).  Valid any time between
 	// iterations.  ST_INVALID with last_error() for a count out of range, and for a count other than 1 on an engine of another algorithm.
 	Status set_hals_sweeps(int h, int w);
+	// HALS: the tolerance delta of the per-column dynamic stopping rule for the iterations that follow (docs/HALS.md, "Dynamic stopping"); 0: the static counts,
+	// bit for bit.  Valid any time between iterations.  ST_INVALID with last_error() for a value outside [0, 1), NaN included, and for a non-zero one on an engine
+	// of another algorithm.
+	Status set_hals_sweep_tolerance(double delta);
+	// HALS: the sweeps applied per column of H (which = 0, n entries) or row of W (which = 1, m entries) in the most recent step of that factor.  Waits for the
+	// stream.  The number of entries copied; negative on another engine, for another `which`, for a capacity too small and before any such step.
+	long hals_sweep_counts(int which, int* out, long capacity);
 
 	// Split form for column-sharded multi-GPU runs (exchange = device buffer of exchange_count()
 	// elements: the local (V H^T)^T panel followed by the local H H^T):
@@ -344,6 +361,13 @@ private:
 	T *rowdot_part_ = nullptr;                // ... and the per-workgroup partial vectors of launch_row_dot's coalesced form
 	T *G_ = nullptr, *G2_ = nullptr, *HHt_ = nullptr, *Qinv_ = nullptr, *gram_part_ = nullptr;
 	T *sumsq_part_ = nullptr;
+	// HALS: the sweeps applied per column of H (npad) and per row of W (mpad) in the most recent H and W step of the dynamic kernel (0 on padding); *_valid_: a
+	// step of that factor has run
+	int *hals_counts_h_ = nullptr, *hals_counts_w_ = nullptr;
+	bool hals_counts_h_valid_ = false, hals_counts_w_valid_ = false;
+	int hals_static_h_ = 0, hals_static_w_ = 0;      // > 0: that step ran this fixed number of sweeps (tolerance 0, or a maximum of 1) and wrote no counts
+	// one panel sweep launch of an HALS step, static or dynamic by prm_.sweep_tolerance, and the counts of the step
+	Status hals_sweeps(bool w_step, T* P, const T* G, int S, int len_pad, int len_valid, T* ps, T* sumsq_part, T l1, T l2);
 	// bf16-operand products (kernels_bf16.hip): fragment-ordered bf16 images of V, Vt and of the two factor panels
 	bool bf16_ = false;
 	void *Vb_ = nullptr, *Vtb_ = nullptr, *Wtb_ = nullptr, *Hb_ = nullptr;

@@ -282,6 +282,12 @@ constexpr int HALS_SWEEPS_MIN = 1, HALS_SWEEPS_MAX = 64;
 template <typename T>
 hipError_t launch_panel_sweeps_hals(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part,
                                     hipStream_t stream, T l1, T l2, int sweeps);
+// ... with per-column dynamic stopping (kernels_hals_dyn.hip; docs/HALS.md, "Dynamic stopping"): `sweeps` is the maximum; a column is frozen after sweep t when
+// d_t <= tol^2 d_1, d_t the squared step of sweep t, and never stepped again.  counts (optional, len_pad ints): sweeps applied per column, 0 on padding.
+// Always the dynamic kernel, one sweep included; tol outside (0, 1), NaN included: hipErrorInvalidValue, beside what launch_panel_sweeps_hals refuses.
+template <typename T>
+hipError_t launch_panel_sweeps_hals_dyn(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part,
+                                        hipStream_t stream, T l1, T l2, int sweeps, double tol, int* counts);
 // W(:, c) <- W(:, c) / d(c), H(c, :) <- H(c, :) d(c) where d(c) = ||W(:, c)|| > 0, d from `parts` vectors of partial sums of squares (W H unchanged);
 // sumsq_part needs RP elements of scratch behind the partials
 template <typename T>

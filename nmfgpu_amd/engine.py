@@ -87,7 +87,7 @@ class Engine:
                  lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence: str = "frobenius",
                  sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False,
                  l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None, weighted: bool = False, mixed_precision: bool = False,
-                 batch_size=None, forget_factor=0.7, sweeps_h: int = 1, sweeps_w: int = 1):
+                 batch_size=None, forget_factor=0.7, sweeps_h: int = 1, sweeps_w: int = 1, sweep_tolerance: float = 0.0):
         """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V),
         "is" (Itakura-Saito, always dense: every entry of V > 0) or "beta" (the beta-divergence at `beta`, any finite value, always dense: scikit-learn's
         solver="mu" with beta_loss=beta; beta=0.0 and beta=1.0 are the "is" and the dense "kl" engines; beta <= 0 needs every entry of V > 0) --
@@ -114,7 +114,10 @@ class Engine:
         forget_factor is not looked at.
 
         sweeps_h, sweeps_w ("hals" only; 1 ... 64): accelerated HALS, that many sweeps per product in the H step and in the W step (docs/HALS.md, "Inner
-        sweeps"); see set_sweeps."""
+        sweeps"); see set_sweeps.
+
+        sweep_tolerance ("hals" only; in [0, 1)): per-column dynamic stopping of the inner sweeps, with sweeps_h / sweeps_w as maximum counts (docs/HALS.md, "Dynamic
+        stopping"); 0 keeps the static counts; see set_sweep_tolerance."""
         if not batch_size:
             batch_size, forget_factor = 0.0, 0.0
         self._bind(m, n, r, dtype)
@@ -126,7 +129,8 @@ class Engine:
                           params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0, "is": 2.0, "beta": 3.0}[divergence],
                                   float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
                                   float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted), float(mixed_precision), float(batch_size), float(forget_factor)],
-                          penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)], sweeps=[_count(sweeps_h), _count(sweeps_w)])
+                          penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)], sweeps=[_count(sweeps_h), _count(sweeps_w)],
+                          sweep_tolerance=float(sweep_tolerance))
         self._create()
 
     def _bind(self, m, n, r, dtype):
@@ -173,6 +177,8 @@ class Engine:
             self.set_penalties(*c["penalties"])
             if c["sweeps"] != [1, 1]:      # (the default needs no call: a library from before the counts has no such entry)
                 self.set_sweeps(*c["sweeps"])
+            if c["sweep_tolerance"] != 0.0:      # (likewise)
+                self.set_sweep_tolerance(c["sweep_tolerance"])
         except EngineError:
             self.close()
             raise
@@ -280,6 +286,27 @@ class Engine:
         self._check(self._lib.nmfamd_engine_set_hals_sweeps(self._h, *(C.c_int(v) for v in vals)), "set_hals_sweeps")
         if self._ctor is not None:
             self._ctor["sweeps"] = vals
+
+    def set_sweep_tolerance(self, tol: float = 0.0):
+        """HALS: per-column dynamic stopping of the inner sweeps in the iterations that follow (nmfamd_engine_set_hals_sweep_tolerance; docs/HALS.md, "Dynamic
+        stopping").  With tol in (0, 1) the counts of set_sweeps are maximum counts: within a step a column is frozen after its sweep t when the squared step of
+        that sweep is at most tol^2 times the squared step of its first sweep.  0 restores the static counts, bit for bit.  Valid between iterations."""
+        tol = float(tol)
+        self._check(self._lib.nmfamd_engine_set_hals_sweep_tolerance(self._h, C.c_double(tol)), "set_hals_sweep_tolerance")
+        if self._ctor is not None:
+            self._ctor["sweep_tolerance"] = tol
+
+    def sweep_counts(self, which: int) -> np.ndarray:
+        """HALS: the sweeps applied to each column of H (which = 0, n values) or row of W (which = 1, m values) by the most recent step of that factor, as np.int32
+        (nmfamd_engine_hals_sweep_counts; synchronises).  Raises EngineError on an engine of another algorithm and before any step of that factor -- with
+        constant_w no W step runs, so which = 1 keeps what the last W step left, or raises if there was none."""
+        out = np.zeros(self.n if which == 0 else self.m, dtype=np.int32)
+        fn = self._lib.nmfamd_engine_hals_sweep_counts
+        fn.restype = C.c_long
+        got = fn(self._h, int(which), C.c_void_p(out.ctypes.data), C.c_long(out.size))
+        if got < 0:
+            raise EngineError(1, "hals_sweep_counts", (self._lib.nmfamd_engine_last_error(self._h) or b"").decode())
+        return out[:got]
 
     @property
     def frobenius(self) -> float:
@@ -674,7 +701,7 @@ def op_tri_update(P: np.ndarray, num: np.ndarray, Q: np.ndarray, *, old_colsq: O
 
 
 def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_valid: int, *, ps: Optional[np.ndarray] = None,
-                  sumsq_part: Optional[np.ndarray] = None, penalties: Optional[tuple] = None, _sweeps: Optional[int] = None):
+                  sumsq_part: Optional[np.ndarray] = None, penalties: Optional[tuple] = None, _sweeps: Optional[int] = None, _tol: Optional[float] = None):
     """One launch of the HALS sweep (nmfamd_op_hals_sweep_*; with penalties = (l1, l2) through nmfamd_op_hals_sweep_pen_*, zeros included) on padded arrays: P (len_pad, RP) panel columns, slabs (S, slab_stride) with
     slab_stride >= len_pad * RP (slab s is the first len_pad * RP values of row s; the rest of the row is a gap the kernel must not read), G (RP, RP).
     ps (len_pad values) and sumsq_part ((len_pad // 16) * RP values), when given, are copied in before the launch, so entries the kernel leaves
@@ -698,7 +725,12 @@ def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_v
             raise ValueError("sumsq_part must hold (len_pad // 16) * RP values")
     parts = C.c_int(0)
     lib, real = library(), (C.c_float if dt == np.float32 else C.c_double)
-    if _sweeps is not None:      # (op_hals_sweeps)
+    counts = None
+    if _tol is not None:         # (op_hals_sweeps_dyn)
+        counts = np.full(len_pad, -1, dtype=np.int32)
+        fn = lib.nmfamd_op_hals_sweeps_dyn_f32 if dt == np.float32 else lib.nmfamd_op_hals_sweeps_dyn_f64
+        extra = (real(penalties[0]), real(penalties[1]), C.c_int(_sweeps), C.c_double(_tol), C.c_void_p(counts.ctypes.data))
+    elif _sweeps is not None:    # (op_hals_sweeps)
         fn, extra = (lib.nmfamd_op_hals_sweeps_f32 if dt == np.float32 else lib.nmfamd_op_hals_sweeps_f64), (real(penalties[0]), real(penalties[1]), C.c_int(_sweeps))
     elif penalties is None:
         fn, extra = (lib.nmfamd_op_hals_sweep_f32 if dt == np.float32 else lib.nmfamd_op_hals_sweep_f64), ()
@@ -710,7 +742,10 @@ def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_v
     if st != 0:
         raise EngineError(st, "nmfamd_op_hals_sweep")
     k = parts.value
-    return {"P": P, "ps": ps, "sumsq_part": None if sumsq_part is None else sumsq_part[:k * RP].reshape(k, RP), "parts": k}
+    out = {"P": P, "ps": ps, "sumsq_part": None if sumsq_part is None else sumsq_part[:k * RP].reshape(k, RP), "parts": k}
+    if counts is not None:
+        out["counts"] = counts
+    return out
 
 
 def op_hals_sweeps(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_valid: int, sweeps: int, *, l1=0.0, l2=0.0, ps: Optional[np.ndarray] = None,
@@ -718,6 +753,14 @@ def op_hals_sweeps(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_
     """One launch of `sweeps` HALS sweeps in a row with the penalties (l1, l2) (nmfamd_op_hals_sweeps_*; kernels_hals_multi.hip), on the arrays of op_hals_sweep
     and with its result; ps and sumsq_part describe the final state.  sweeps = 1 is op_hals_sweep's launch; outside 1 ... 64 it is refused."""
     return op_hals_sweep(P, slabs, G, r, len_valid, ps=ps, sumsq_part=sumsq_part, penalties=(l1, l2), _sweeps=_count(sweeps))
+
+
+def op_hals_sweeps_dyn(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_valid: int, sweeps: int, tol: float, *, l1=0.0, l2=0.0,
+                       ps: Optional[np.ndarray] = None, sumsq_part: Optional[np.ndarray] = None):
+    """One launch of at most `sweeps` HALS sweeps with per-column dynamic stopping at the tolerance tol (nmfamd_op_hals_sweeps_dyn_*; kernels_hals_dyn.hip,
+    docs/HALS.md "Dynamic stopping"), on the arrays of op_hals_sweep.  Returns what op_hals_sweeps returns plus `counts` (len_pad np.int32 values: the sweeps applied
+    to each column, 0 on padding).  Always the dynamic kernel, one sweep included; tol outside (0, 1) is refused."""
+    return op_hals_sweep(P, slabs, G, r, len_valid, ps=ps, sumsq_part=sumsq_part, penalties=(l1, l2), _sweeps=int(sweeps), _tol=float(tol))
 
 
 def op_beta_half_step(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: int, out_valid: int, red_valid: int, beta: int, form: int = 0, *,

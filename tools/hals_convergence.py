@@ -1,11 +1,14 @@
-"""usage: python tools/hals_convergence.py [ITERS] [--sweeps-h 1,2,4 --sweeps-w 1,2,4]      (on the GPU box)
+"""usage: python tools/hals_convergence.py [ITERS] [--sweeps-h 1,2,4 --sweeps-w 1,2,4] [--sweep-tolerance 0.3,0.1]      (on the GPU box)
 HALS against the multiplicative update from the same start: the relative error ||V - W H|| / ||V|| every 10th iteration up to ITERS (default 1000), the
 iterations each algorithm needs to reach the error MU has after ITERS, and the unprofiled wall time per iteration (200 iterations without error terms) -- so
 the time to that error.  Two problems: planted (V = W0 H0 + 0.01 noise, 2 000 x 1 500, r = 20) and config 2's random shape (10 000 x 5 000, r = 64).
 --sweeps-h / --sweeps-w: comma lists of equal length, one HALS row per pair of sweep counts (accelerated HALS, docs/HALS.md "Inner sweeps"; default 1 / 1).
 Per problem the tool also times an iteration at (1, 1), (2, 1), (1, 2), (5, 1) and (1, 5): the differences are what one more H sweep and one more W sweep cost
 inside the launch, the figures Gillis & Glineur's rule s = 1 + alpha rho (--alpha, default 0.5) takes its rho from; one more HALS row runs at the counts the
-rule gives, rounded to the nearest integer, unless they are among the given pairs.  docs/HALS.md records the output."""
+rule gives, rounded to the nearest integer, unless they are among the given pairs.
+--sweep-tolerance: a comma list of tolerances delta of the per-column dynamic stopping rule (docs/HALS.md, "Dynamic stopping"); every given pair of counts is run
+once more per delta as MAXIMUM counts, and the row shows the mean number of sweeps a column of H and a row of W took per step (sampled at every 10th iteration,
+up to the iteration that reaches the target) next to the timings.  docs/HALS.md records the output."""
 import argparse
 import os
 import sys
@@ -41,16 +44,21 @@ def sweep_costs(V, W, H):
     return base, out[1] - base, out[2] - base, (out[3] - base) / 4, (out[4] - base) / 4
 
 
-def curve(alg, V, W, H, iters, sweeps=(1, 1)):
+def curve(alg, V, W, H, iters, sweeps=(1, 1), tol=0.0, target=None):
+    """([(iteration, relative error)], microseconds per iteration, [(mean H count, mean W count)] per error point or None without a tolerance, and with a target
+    the wall time in ms of a run from the start to the first error point at or below it, without error terms: median of three -- with a tolerance the
+    iterations of a run do not cost the same, so iterations x time per iteration is only an estimate there)"""
     m, n = V.shape
-    eng = na.Engine(m, n, W.shape[1], alg, sweeps_h=sweeps[0], sweeps_w=sweeps[1])
+    eng = na.Engine(m, n, W.shape[1], alg, sweeps_h=sweeps[0], sweeps_w=sweeps[1], sweep_tolerance=tol)
     eng.upload(V)
     eng.set_factors(W, H)
     nv = float(np.linalg.norm(V.astype(np.float64)))
-    out = []
+    out, counts = [], [] if tol > 0 else None
     for it in range(10, iters + 1, 10):
         eng.iterate(10, first_iteration=it - 9, error_every=10)
         out.append((it, eng.frobenius / nv))
+        if tol > 0:
+            counts.append((float(eng.sweep_counts(0).mean()), float(eng.sweep_counts(1).mean())))
     eng.set_factors(W, H)
     eng.iterate(20, error_every=0)
     eng.synchronize()
@@ -58,8 +66,20 @@ def curve(alg, V, W, H, iters, sweeps=(1, 1)):
     eng.iterate(200, first_iteration=21, error_every=0)
     eng.synchronize()
     us = (time.perf_counter() - t0) / 200 * 1e6
+    direct = None
+    it = first_below(out, target) if target is not None else None
+    if it:
+        runs = []
+        for _ in range(3):
+            eng.set_factors(W, H)
+            eng.synchronize()
+            t0 = time.perf_counter()
+            eng.iterate(it, first_iteration=1, error_every=0)
+            eng.synchronize()
+            runs.append((time.perf_counter() - t0) * 1e3)
+        direct = float(np.median(runs))
     eng.close()
-    return out, us
+    return out, us, counts, direct
 
 
 def first_below(c, target):
@@ -71,12 +91,14 @@ def main():
     ap.add_argument("iters", nargs="?", type=int, default=1000)
     ap.add_argument("--sweeps-h", default="1")
     ap.add_argument("--sweeps-w", default="1")
+    ap.add_argument("--sweep-tolerance", default="", help="comma list of tolerances of the dynamic stopping rule; each pair of counts runs once more per value, as maximum counts")
     ap.add_argument("--alpha", type=float, default=0.5, help="the alpha of Gillis & Glineur's rule s = 1 + alpha rho; one more HALS row runs at the counts it gives")
     a = ap.parse_args()
     iters = a.iters
     pairs = list(zip((int(x) for x in a.sweeps_h.split(",")), (int(x) for x in a.sweeps_w.split(","))))
     if len(a.sweeps_h.split(",")) != len(a.sweeps_w.split(",")):
         raise SystemExit("--sweeps-h and --sweeps-w need lists of equal length")
+    tols = [float(x) for x in a.sweep_tolerance.split(",") if x]
     na.initialize()
     na.set_verbosity(na.Verbosity.Nothing)
     rng = np.random.default_rng(21)
@@ -90,12 +112,15 @@ def main():
         m, n = V.shape
         W = np.asfortranarray(rng.random((m, r)).astype(np.float32))
         H = np.asfortranarray(rng.random((r, n)).astype(np.float32))
-        cm, us_mu = curve("mu", V, W, H, iters)
-        rows = [("MU", cm, us_mu)]
-        for sw in pairs:
-            ch, us_h = curve("hals", V, W, H, iters, sw)
-            rows.append(("HALS" if sw == (1, 1) else f"HALS {sw[0]},{sw[1]}", ch, us_h))
+        cm, us_mu, _, _ = curve("mu", V, W, H, iters)
         target = cm[-1][1]
+        rows = [("MU", cm, us_mu, None, None)]
+        for sw in pairs:
+            ch, us_h, _, direct = curve("hals", V, W, H, iters, sw, target=target)
+            rows.append(("HALS" if sw == (1, 1) else f"HALS {sw[0]},{sw[1]}", ch, us_h, None, direct))
+            for tol in tols if sw != (1, 1) else []:
+                ch, us_h, counts, direct = curve("hals", V, W, H, iters, sw, tol, target)
+                rows.append((f"HALS <={sw[0]},<={sw[1]} delta {tol:g}", ch, us_h, counts, direct))
         print(f"== {name}: relative error of MU after {iters} iterations {target:.6e}")
         base, dh, dw, dh4, dw4 = sweep_costs(V, W, H)
         print(f"  HALS iteration at (1, 1) {base:.1f} us; one more H sweep {dh:+.1f} us (mean of four more {dh4:+.1f}), one more W sweep {dw:+.1f} us (mean of four more {dw4:+.1f})")
@@ -105,13 +130,18 @@ def main():
         rule = tuple(int(min(64, max(1, round(1 + a.alpha * rest / max(d, 1e-3))))) for d in (dh4, dw4))
         print(f"  rule (alpha = {a.alpha}): rho_H = {rest / max(dh4, 1e-3):.2f}, rho_W = {rest / max(dw4, 1e-3):.2f} -> sweeps ({rule[0]}, {rule[1]})")
         if rule not in pairs:
-            ch, us_h = curve("hals", V, W, H, iters, rule)
-            rows.append((f"HALS {rule[0]},{rule[1]}", ch, us_h))
-        for alg, c, us in rows:
+            ch, us_h, _, direct = curve("hals", V, W, H, iters, rule, target=target)
+            rows.append((f"HALS {rule[0]},{rule[1]}", ch, us_h, None, direct))
+        for alg, c, us, counts, direct in rows:
             it = first_below(c, target)
             at = {k: e for k, e in c}
             pts = " ".join(f"{k}:{at[k]:.5e}" for k in (10, 20, 50, 100, 200, 500, 1000) if k in at)
-            print(f"  {alg:10s} {us:8.1f} us/iteration; reaches it after {it} iterations = {it * us / 1e3 if it else float('nan'):.1f} ms; {pts}")
+            mean = ""
+            if counts:
+                upto = counts[:it // 10] if it else counts
+                mean = f" mean sweeps per step H {np.mean([h for h, _ in upto]):.2f} W {np.mean([w for _, w in upto]):.2f} (last sample {counts[-1][0]:.2f} / {counts[-1][1]:.2f});"
+            timed = f" (timed from the start: {direct:.1f} ms)" if direct is not None else ""
+            print(f"  {alg:10s} {us:8.1f} us/iteration;{mean} reaches it after {it} iterations = {it * us / 1e3 if it else float('nan'):.1f} ms{timed}; {pts}")
     na.finalize()
 
 

@@ -1,5 +1,6 @@
 """usage: python tools/launches_per_iteration.py M N R ALG DTYPE [theta]      (on the GPU box; ALG mu | nsnmf | gdcls | als | acls | ahcls | hals | hals-pen, DTYPE f32 | f64;
-hals-pen: HALS with the penalties l1W = l1H = 0.5, l2W = l2H = 0.1, docs/HALS.md; hals-sN, N = 2 ... 64: accelerated HALS with N sweeps per product in both steps)
+hals-pen: HALS with the penalties l1W = l1H = 0.5, l2W = l2H = 0.1, docs/HALS.md; hals-sN, N = 2 ... 64: accelerated HALS with N sweeps per product in both steps; hals-sN-dT: the same with the sweep tolerance T, e.g. hals-s4-d1e-30 -- the
+dynamic-stopping kernel with nothing to freeze)
 Kernel launches and kernel time per steady-state iteration of the resident engine at any shape: two child runs under `rocprofv3 --kernel-trace` (100 and 300
 iterations, error terms every 10th), the difference divided by 200 -- set-up, upload and the first launches cancel; a third child without the profiler gives the wall time per iteration.  Prints the per-kernel table of the difference."""
 import collections
@@ -26,8 +27,11 @@ def child(m, n, r, alg, dtype, theta, iters):
     kw = {"nsnmf": dict(theta=theta), "gdcls": dict(lam=0.01), "acls": dict(lambda_w=0.01, lambda_h=0.01),
           "ahcls": dict(lambda_w=0.01, lambda_h=0.01, alpha_w=0.01, alpha_h=0.01),
           "hals-pen": dict(l1_w=0.5, l1_h=0.5, l2_w=0.1, l2_h=0.1)}.get(alg, {})
-    if alg.startswith("hals-s"):      # hals-sN: N sweeps per product in both steps
-        kw = dict(sweeps_h=int(alg[6:]), sweeps_w=int(alg[6:]))
+    if alg.startswith("hals-s"):      # hals-sN[-dT]: N sweeps per product in both steps [as maximum counts at the sweep tolerance T]
+        count, _, tol = alg[6:].partition("-d")
+        kw = dict(sweeps_h=int(count), sweeps_w=int(count))
+        if tol:
+            kw["sweep_tolerance"] = float(tol)
     eng = na.Engine(m, n, r, alg.split("-")[0], dtype=dt, **kw)
     eng.upload(V); eng.set_factors(W, H)
     eng.iterate(iters, first_iteration=1, error_every=10)
