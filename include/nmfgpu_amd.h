@@ -41,8 +41,10 @@ enum {
 
 /* algorithm ids = nmfgpu::NmfAlgorithm (include/nmfgpu.h:107-114; NMFAMD_HALS is an extension: coordinate descent, docs/HALS.md -- dense or
    sparse compute, L1 / L2 penalties through nmfamd_engine_set_hals_penalties, no three-phase / sharded form).  The dense divergence engines (NMFAMD_MU with
-   divergence 2, 3, or 1 with dense_compute) take the same penalties on their multiplicative update (docs/DIVERGENCE.md) */
-enum { NMFAMD_MU = 0, NMFAMD_GDCLS = 1, NMFAMD_ALS = 2, NMFAMD_ACLS = 3, NMFAMD_AHCLS = 4, NMFAMD_NSNMF = 5, NMFAMD_HALS = 6 };
+   divergence 2, 3, or 1 with dense_compute) take the same penalties on their multiplicative update (docs/DIVERGENCE.md).
+   NMFAMD_NENMF is an extension too (docs/NENMF.md): the iteration of NMFAMD_HALS with Nesterov-accelerated projected-gradient steps in place of the sweeps
+   (nmfamd_engine_set_nenmf_steps); ranks 1 ... 128 in either precision, otherwise the limits and the penalties of NMFAMD_HALS */
+enum { NMFAMD_MU = 0, NMFAMD_GDCLS = 1, NMFAMD_ALS = 2, NMFAMD_ACLS = 3, NMFAMD_AHCLS = 4, NMFAMD_NSNMF = 5, NMFAMD_HALS = 6, NMFAMD_NENMF = 7 };
 
 /* sparse formats = nmfgpu::StorageFormat (include/nmfgpu.h:177-186) */
 enum { NMFAMD_DENSE = 0, NMFAMD_CSR = 1, NMFAMD_CSC = 2, NMFAMD_COO = 3 };
@@ -213,6 +215,13 @@ NMFAMD_API int nmfamd_engine_set_hals_sweep_tolerance(nmfamd_engine* e, double d
  * an engine of another algorithm, for another `which`, for capacity below n (m), and before any step of that factor -- with constant W no W step runs, so
  * which = 1 keeps returning what it returned before. */
 NMFAMD_API long nmfamd_engine_hals_sweep_counts(nmfamd_engine* e, int which, int* out, long capacity);
+/* NeNMF engines (docs/NENMF.md): the H step computes W^T W and W^T V once and takes steps_h accelerated projected-gradient steps
+ *   H <- max(0, Y - (W^T W Y + l2H Y - W^T V + l1H) / L),  L = ||W^T W||_inf + l2H,  followed by Nesterov's extrapolation of Y,
+ * in one launch, the W step steps_w of them against H H^T and V H^T; everything else (penalties through nmfamd_engine_set_hals_penalties, normalisation, error
+ * reporting, constant W: the H step only) is as on a HALS engine.  1 ... 256 each; a new engine has (8, 8).  Valid any time between iterations; takes effect at
+ * the next nmfamd_engine_iterate.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error) for a count outside 1 ... 256, and on any other engine.  On a NeNMF
+ * engine nmfamd_engine_set_hals_sweeps refuses a count other than 1 and nmfamd_engine_set_hals_sweep_tolerance a value other than 0. */
+NMFAMD_API int nmfamd_engine_set_nenmf_steps(nmfamd_engine* e, int steps_h, int steps_w);
 /* Frobenius norm / RMSD of the most recent error iteration (IAlgorithm::frobeniusNorm / rmsd). */
 NMFAMD_API double nmfamd_engine_frobenius(nmfamd_engine* e);
 NMFAMD_API double nmfamd_engine_rmsd(nmfamd_engine* e);
@@ -469,6 +478,14 @@ NMFAMD_API int nmfamd_op_hals_sweeps_dyn_f32(float* P, const float* slabs, int S
                                              float* ps, float* sumsq_part, int* parts, float l1, float l2, int sweeps, double tol, int* counts);
 NMFAMD_API int nmfamd_op_hals_sweeps_dyn_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid,
                                              double* ps, double* sumsq_part, int* parts, double l1, double l2, int sweeps, double tol, int* counts);
+/* `steps` accelerated projected-gradient steps of NeNMF with the penalties (l1, l2) in one launch (kernels_nenmf.hip; docs/NENMF.md), on the arrays of
+ * nmfamd_op_hals_sweeps_* and with its outputs: ps and sumsq_part from the final projected iterate, *parts = len_pad / the kernel's columns per workgroup (32 in
+ * single, 16 in double precision).  Padded ranks 64 and 128.  NMFAMD_INVALID_ARGUMENT for steps outside 1 ... 256, another padded rank, a negative or
+ * non-finite penalty and wherever nmfamd_op_hals_sweeps_* refuses. */
+NMFAMD_API int nmfamd_op_apg_steps_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid,
+                                       float* ps, float* sumsq_part, int* parts, float l1, float l2, int steps);
+NMFAMD_API int nmfamd_op_apg_steps_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid,
+                                       double* ps, double* sumsq_part, int* parts, double l1, double l2, int steps);
 /* The HALS column normalisation on host panels Wt [mpad][RP] and H [npad][RP] (both updated in place) from parts x RP partial sums of squares:
  * d(c) = sqrt(sum of the parts); where d(c) > 0, Wt(:, c) / d(c) and H(:, c) * d(c). */
 NMFAMD_API int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad, const float* sumsq_part, int parts);

@@ -50,6 +50,7 @@ class NmfAlgorithm(enum.IntEnum):  # ref :107-114
     AHCLS = 4
     nsNMF = 5
     HALS = 6  # extension: coordinate descent (docs/HALS.md)
+    NeNMF = 7  # extension: the HALS iteration with accelerated projected-gradient steps (docs/NENMF.md)
 
 
 class Verbosity(enum.IntEnum):  # ref :117-126
@@ -266,7 +267,10 @@ def compute(V, W: np.ndarray, H: np.ndarray, *, algorithm: NmfAlgorithm = NmfAlg
 
     ``parameters={"sweepsH": 3, "sweepsW": 2}`` with the HALS algorithm: accelerated HALS, that many sweeps per product in the H and in the W
     step (integers in 1 ... 64, absent = 1; docs/HALS.md, "Inner sweeps"), next to the penalties "l1W", "l1H", "l2W", "l2H".  ``"sweepsTolerance": 0.1``
-    makes the counts maximum counts: every column stops sweeping by itself (docs/HALS.md, "Dynamic stopping"; in [0, 1), absent = 0)."""
+    makes the counts maximum counts: every column stops sweeping by itself (docs/HALS.md, "Dynamic stopping"; in [0, 1), absent = 0).
+
+    ``parameters={"stepsH": 16, "stepsW": 16}`` with the NeNMF algorithm: that many Nesterov-accelerated projected-gradient steps per product in the H and in
+    the W step (integers in 1 ... 256, absent = 8; docs/NENMF.md), next to the penalties and "sparseCompute" of HALS; at most 128 features."""
     if W.dtype != H.dtype:
         raise TypeError("W and H must share a dtype")
     d = NmfDescription()

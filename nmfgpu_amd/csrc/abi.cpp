@@ -132,6 +132,7 @@ const char* algorithm_name(NmfAlgorithm a) {
 	case NmfAlgorithm::AHCLS: return "Alternating Hoyer Constrained Least Squares";
 	case NmfAlgorithm::nsNMF: return "non-smooth NMF";
 	case NmfAlgorithm::HALS: return "HALS";
+	case NmfAlgorithm::NeNMF: return "NeNMF";
 	}
 	return "?";
 }
@@ -171,7 +172,7 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		return true;
 	};
 	switch (d.algorithm) {
-	case NmfAlgorithm::Multiplicative: case NmfAlgorithm::ALS: case NmfAlgorithm::HALS: break;
+	case NmfAlgorithm::Multiplicative: case NmfAlgorithm::ALS: case NmfAlgorithm::HALS: case NmfAlgorithm::NeNMF: break;
 	case NmfAlgorithm::ACLS:
 		if (!need("lambdaW", prm.lambdaW, "ACLS") || !need("lambdaH", prm.lambdaH, "ACLS")) return ResultType::ErrorInvalidArgument;
 		break;
@@ -226,7 +227,8 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 			}
 		}
 		// (HALS takes sparse compute with the Frobenius objective: its two products against V are the SpMM launches of the sparse multiplicative update)
-		const bool sparse_hals = d.algorithm == NmfAlgorithm::HALS && prm.divergence == 0;
+		// (NeNMF shares that iteration and its limits)
+		const bool sparse_hals = nmfamd::hals_family(static_cast<int>(d.algorithm)) && prm.divergence == 0;
 		if ((prm.divergence != 0 || prm.sparse_compute != 0) && d.algorithm != NmfAlgorithm::Multiplicative && !sparse_hals) {
 			log_error("[ERROR] 'divergence' is only available for the Multiplicative algorithm, 'sparseCompute' for Multiplicative and HALS!");
 			return ResultType::ErrorInvalidArgument;
@@ -282,7 +284,7 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 			*p.slot = d.parameters[idx].value;
 		}
 		// (the engine's own rule, asked here so that a refusal comes before any device work)
-		if (const char* why = nmfamd::hals_penalties_fault(prm.l1W, prm.l1H, prm.l2W, prm.l2H, sizeof(T) == 4, prm.takes_penalties(d.algorithm == NmfAlgorithm::HALS))) {
+		if (const char* why = nmfamd::hals_penalties_fault(prm.l1W, prm.l1H, prm.l2W, prm.l2H, sizeof(T) == 4, prm.takes_penalties(nmfamd::hals_family(static_cast<int>(d.algorithm))))) {
 			log_error((std::string("[ERROR] ") + why).c_str());
 			return ResultType::ErrorInvalidArgument;
 		}
@@ -304,6 +306,21 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		if (idx >= 0) prm.sweep_tolerance = d.parameters[idx].value;
 		if (const char* why = nmfamd::hals_sweep_tolerance_fault(prm.sweep_tolerance, d.algorithm == NmfAlgorithm::HALS)) {
 			log_error((std::string("[ERROR] ") + why).c_str());
+			return ResultType::ErrorInvalidArgument;
+		}
+	}
+	{
+		// "stepsH", "stepsW": projected-gradient steps per product of NeNMF (docs/NENMF.md); absent = 8, integers in 1 ... 256, with the NeNMF algorithm only
+		const int ih = parameter_index(d.parameters, d.numParameters, "stepsH"), iw = parameter_index(d.parameters, d.numParameters, "stepsW");
+		if (ih >= 0) prm.steps_h = d.parameters[ih].value;
+		if (iw >= 0) prm.steps_w = d.parameters[iw].value;
+		// (the engine's own rule, asked here so that a refusal comes before any device work)
+		if (const char* why = nmfamd::nenmf_steps_fault(prm.steps_h, prm.steps_w, ih >= 0 || iw >= 0, d.algorithm == NmfAlgorithm::NeNMF)) {
+			log_error((std::string("[ERROR] ") + why).c_str());
+			return ResultType::ErrorInvalidArgument;
+		}
+		if (d.algorithm == NmfAlgorithm::NeNMF && !nmfamd::panel_steps_apg_available(nmfamd::padded_rank((int)d.features, prm.sparse_compute != 0 ? 4 : sizeof(T)), sizeof(T))) {
+			log_error("[ERROR] The NeNMF algorithm supports 1 ... 128 features!");
 			return ResultType::ErrorInvalidArgument;
 		}
 	}
@@ -381,8 +398,8 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 			log_error("[ERROR] 'numGpus' > 1 is not available with the dense divergence update ('divergence' = 2 or 3, 'denseCompute')!");
 			return ResultType::ErrorInvalidArgument;
 		}
-		if (num_gpus > 1 && d.algorithm == NmfAlgorithm::HALS) {
-			log_error("[ERROR] 'numGpus' > 1 is not available for the HALS algorithm!");
+		if (num_gpus > 1 && nmfamd::hals_family(static_cast<int>(d.algorithm))) {
+			log_error("[ERROR] 'numGpus' > 1 is not available for the HALS and NeNMF algorithms!");
 			return ResultType::ErrorInvalidArgument;
 		}
 		if (num_gpus > 1) {
@@ -423,7 +440,7 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 	const UserInterruptCallback interrupt = d.callbackUserInterrupt;
 	const bool constW = d.useConstantBasisVectors;
 	// only W is initialised for the LS algorithms (their first step solves for H); HALS sweeps from the old H
-	const bool want_h = d.algorithm == NmfAlgorithm::Multiplicative || d.algorithm == NmfAlgorithm::nsNMF || d.algorithm == NmfAlgorithm::HALS;
+	const bool want_h = d.algorithm == NmfAlgorithm::Multiplicative || d.algorithm == NmfAlgorithm::nsNMF || nmfamd::hals_family(static_cast<int>(d.algorithm));
 
 	// IAlgorithm's seed stream: constructed from the caller's seed, one draw per run
 	std::mt19937 seed_stream(d.seed);

@@ -177,8 +177,10 @@ Engine<T>::~Engine() {
 
 template <typename T>
 Status Engine<T>::allocate() {
-	if (m_ <= 0 || n_ <= 0 || r_ <= 0 || alg_ < 0 || alg_ > ALG_HALS) return ST_INVALID;
+	if (m_ <= 0 || n_ <= 0 || r_ <= 0 || alg_ < 0 || alg_ > ALG_NENMF) return ST_INVALID;
 	if (alg_ == ALG_HALS && !panel_sweep_hals_available(RP_, sizeof(T))) { last_error_ = "HALS: no sweep kernel for this padded rank (fp32: 64 ... 512, fp64: multiples of 64 up to 512)"; return ST_INVALID; }
+	if (alg_ == ALG_NENMF && !panel_steps_apg_available(RP_, sizeof(T))) { last_error_ = "NeNMF: no step kernel for this padded rank (supported ranks: 1 ... 128, in either precision)"; return ST_INVALID; }
+	if (const char* why = nenmf_steps_fault(prm_.steps_h, prm_.steps_w, false, alg_ == ALG_NENMF)) { last_error_ = why; return ST_INVALID; }
 	if (Status s = set_hals_penalties(prm_.l1W, prm_.l1H, prm_.l2W, prm_.l2H)) return s;      // (values that came with the parameters: the setter's checks, and its rounding of prm_ to T)
 	if (const char* why = hals_sweeps_fault(prm_.sweeps_h, prm_.sweeps_w, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = hals_sweep_tolerance_fault(prm_.sweep_tolerance, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
@@ -216,8 +218,8 @@ Status Engine<T>::allocate() {
 	if (sparse_) {
 		// sparse compute: multiplicative update (either objective, masked or not) and HALS (Frobenius, not masked), padded rank 64 / 128 / 256
 		const char* why = nullptr;
-		if (alg_ == ALG_HALS && (prm_.divergence != 0 || prm_.is_masked())) why = "HALS: sparse compute with the Frobenius objective only (no 'divergence', no missing values)";
-		else if (alg_ != ALG_MU && alg_ != ALG_HALS) why = "sparse compute: multiplicative update and HALS only";
+		if (hals_family(alg_) && (prm_.divergence != 0 || prm_.is_masked())) why = "HALS: sparse compute with the Frobenius objective only (no 'divergence', no missing values)";
+		else if (alg_ != ALG_MU && !hals_family(alg_)) why = "sparse compute: multiplicative update and HALS only";
 		else if (RP_ > 256) why = "sparse compute needs rank <= 256 (the SpMM kernels gather 1, 2 or 4 values per lane)";
 		if (why != nullptr) { last_error_ = why; return ST_INVALID; }
 		tiled_ = false;
@@ -429,7 +431,7 @@ Status Engine<T>::allocate() {
 	HIPX(dalloc(&Qinv_, rr));
 	HIPX(dalloc(&gram_part_, rr * gram_parts_));
 	HIPX(dalloc(&sumsq_part_, ((long)std::max({panel_update_parts(RP_, sizeof(T), (int)mpad_), (int)(mpad_ / panel_update_rows(RP_, sizeof(T))),
-	                                           alg_ == ALG_HALS ? panel_sweep_hals_parts(RP_, sizeof(T), (int)mpad_) : 0}) + 16) * RP_));
+	                                           hals_family(alg_) ? family_parts((int)mpad_) : 0}) + 16) * RP_));
 	if (alg_ == ALG_HALS) {
 		// the sweep counts of the most recent H and W step (dynamic stopping, docs/HALS.md)
 		HIPX(hipMalloc((void**)&hals_counts_h_, sizeof(int) * (size_t)npad_));
@@ -1319,7 +1321,7 @@ Status Engine<T>::h_step(bool compute_error) {
 	if (prm_.is_masked()) return masked_refuses("h_step");
 	if (beta_dense_) return beta_refuses("h_step");
 	if (prm_.divergence != 0) { kl_err_iter_ = compute_error; return kl_h_step(); }
-	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
+	if (hals_family(alg_)) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	return h_step_impl(compute_error);
 }
 
@@ -1383,14 +1385,15 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 	if (!(gram_w_ready_ && F == Wt_)) HIPX(launch_gram<T>(F, RP_, m_, gram_parts_, gram_part_, G_, stream_));
 	gram_w_ready_ = false;      // consumed (the inverse passenger / update below read G_; W changes in the W step)
 	const int S = planH_.splits;
-	if (alg_ == ALG_HALS) {
+	if (hals_family(alg_)) {
 		// coordinate sweep over every column of H against G = W^T W and the summed slabs of W^T V; ps: the per-column terms of tr(H^T W^T V), as PANEL_MU
 		// writes them.  No split image of the new H: the next product packs its operand itself.
 		if (Status s = product_h(F, nullptr, x3_ && wx3_valid_ && F == Wt_)) return s;
 		// (penalties: G and the slabs stay raw -- ps and the trace of the error term read them)
 		// (sweeps_h sweeps against this one G and these slabs, in one launch; one sweep is launch_panel_sweep_hals)
 		// (a sweep tolerance: the counts are maximum counts and every column stops by itself, kernels_hals_dyn.hip)
-		if (Status s = hals_sweeps(false, H_, G_, S, (int)npad_, n_, compute_error ? psN_ : nullptr, nullptr, (T)prm_.l1H, (T)prm_.l2H)) return s;
+		// (NeNMF: steps_h projected-gradient steps in the same place, kernels_nenmf.hip)
+		if (Status s = family_step(false, H_, G_, S, (int)npad_, n_, compute_error ? psN_ : nullptr, nullptr, (T)prm_.l1H, (T)prm_.l2H)) return s;
 		hx3_valid_ = false;
 		return ST_OK;
 	}
@@ -1442,7 +1445,7 @@ Status Engine<T>::w_products(T* exchange) {
 	if (prm_.is_masked()) return masked_refuses("w_products");
 	if (beta_dense_) return beta_refuses("w_products");
 	if (prm_.divergence != 0) return kl_w_products(exchange, kl_err_iter_);      // (sparse Frobenius compute shards through the code below: its two products are SpMMs over the shard's images)
-	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
+	if (hals_family(alg_)) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	T* ex_hht = exchange + (long)RP_ * mpad_;
 	if constexpr (std::is_same<T, float>::value) {
 		if (fused_capable()) {
@@ -1493,7 +1496,7 @@ Status Engine<T>::w_finish(const T* exchange, bool compute_error) {
 	if (prm_.is_masked()) return masked_refuses("w_finish");
 	if (beta_dense_) return beta_refuses("w_finish");
 	if (prm_.divergence != 0) return kl_w_finish(exchange, compute_error);
-	if (alg_ == ALG_HALS) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
+	if (hals_family(alg_)) { last_error_ = "HALS: no three-phase (column-sharded) form"; return ST_INVALID; }
 	const T eps = std::numeric_limits<T>::epsilon();
 	const T* ex_hht = exchange + (long)RP_ * mpad_;
 	if (alg_ != ALG_MU && alg_ != ALG_NSNMF) {
@@ -2128,7 +2131,7 @@ Status Engine<T>::begin_next_iteration() {
 template <typename T>
 Status Engine<T>::set_hals_penalties(double l1W, double l1H, double l2W, double l2H) {
 	// (prm_, not beta_dense_: allocate() calls this before it has looked at the divergence)
-	if (const char* why = hals_penalties_fault(l1W, l1H, l2W, l2H, sizeof(T) == 4, prm_.takes_penalties(alg_ == ALG_HALS))) { last_error_ = why; return ST_INVALID; }
+	if (const char* why = hals_penalties_fault(l1W, l1H, l2W, l2H, sizeof(T) == 4, prm_.takes_penalties(hals_family(alg_)))) { last_error_ = why; return ST_INVALID; }
 	// kept rounded to T, as the sweeps take them: a value that rounds to 0 in the engine's precision is 0 for the normalisation switch too, and the
 	// (T) casts where the sweeps are launched change nothing any more
 	prm_.l1W = (double)(T)l1W; prm_.l1H = (double)(T)l1H; prm_.l2W = (double)(T)l2W; prm_.l2H = (double)(T)l2H;
@@ -2146,6 +2149,19 @@ template <typename T>
 Status Engine<T>::set_hals_sweep_tolerance(double delta) {
 	if (const char* why = hals_sweep_tolerance_fault(delta, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
 	prm_.sweep_tolerance = delta;
+	return ST_OK;
+}
+
+template <typename T>
+Status Engine<T>::set_nenmf_steps(int h, int w) {
+	if (const char* why = nenmf_steps_fault((double)h, (double)w, true, alg_ == ALG_NENMF)) { last_error_ = why; return ST_INVALID; }
+	prm_.steps_h = h; prm_.steps_w = w;
+	return ST_OK;
+}
+
+template <typename T>
+Status Engine<T>::apg_steps(bool w_step, T* P, const T* G, int S, int len_pad, int len_valid, T* ps, T* sumsq_part, T l1, T l2) {
+	HIPX(launch_panel_steps_apg<T>(P, slabs_, S, slab_stride_, G, RP_, r_, len_pad, len_valid, ps, sumsq_part, stream_, l1, l2, (int)(w_step ? prm_.steps_w : prm_.steps_h)));
 	return ST_OK;
 }
 
@@ -2241,7 +2257,7 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				if (tri_) wtw = reinterpret_cast<const T*>(Gw_raw_);
 				else if (fused_capable()) wtw = G_;             // (rank 64: the H step's passengers took it from the unsmoothed image, pending scale applied)
 				else { HIPX(launch_gram<T>(Wt_, RP_, m_, gram_parts_, gram_part_, G2_, stream_)); wtw = G2_; }
-			} else if (alg_ != ALG_MU && alg_ != ALG_HALS) wtw = G2_;      // LS algorithms: copy saved before the regulariser (MU, HALS: W^T W of this H step)
+			} else if (alg_ != ALG_MU && !hals_family(alg_)) wtw = G2_;      // LS algorithms: copy saved before the regulariser (MU, HALS: W^T W of this H step)
 			HIPX(launch_trace_small<T>(HHt_, wtw, RP_, r_, psR_, stream_, tri_trace_scale()));
 		}
 		if (!constant_w) {
@@ -2277,17 +2293,17 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				// (rank 256, H H^T rode in that launch: the error term's trace of H H^T against the unsmoothed W^T W of this iteration's H step, AlgorithmNonSmoothNMF.h:201-202)
 				if (compute_error && tri_ride.tri_frags != nullptr) HIPX(launch_trace_small<T>(HHt_, reinterpret_cast<const T*>(Gw_raw_), RP_, r_, psR_, stream_, tri_trace_scale()));
 			}
-			if (alg_ == ALG_HALS) {
+			if (hals_family(alg_)) {
 				// coordinate sweep over every row of W against H H^T and the summed slabs of V H^T, then the column normalisation that keeps W H:
 				// W(:, c) / d(c), H(c, :) d(c) -- applied to H at once, no pending scale.  With a penalty there is no normalisation: it keeps W H but not the
 				// penalty terms, and without it one iteration is one pass of scikit-learn's coordinate descent (docs/HALS.md).
 				wx3_valid_ = false;
 				gram_w_ready_ = false;
 				if (prm_.hals_penalised()) {
-					if (Status s = hals_sweeps(true, Wt_, HHt_, S, (int)mpad_, m_, nullptr, nullptr, (T)prm_.l1W, (T)prm_.l2W)) return s;
+					if (Status s = family_step(true, Wt_, HHt_, S, (int)mpad_, m_, nullptr, nullptr, (T)prm_.l1W, (T)prm_.l2W)) return s;
 				} else {
-					if (Status s = hals_sweeps(true, Wt_, HHt_, S, (int)mpad_, m_, nullptr, sumsq_part_, T(0), T(0))) return s;
-					HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, panel_sweep_hals_parts(RP_, sizeof(T), (int)mpad_), stream_));
+					if (Status s = family_step(true, Wt_, HHt_, S, (int)mpad_, m_, nullptr, sumsq_part_, T(0), T(0))) return s;
+					HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, sumsq_part_, family_parts((int)mpad_), stream_));
 				}
 			} else if (!ls_family) {
 				const bool gd_err = alg_ == ALG_GDCLS && compute_error;
@@ -2321,7 +2337,7 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				}
 				if (Status s = normalize_w(wpart != nullptr, norm_parts)) return s;
 			}
-		} else if (compute_error && alg_ != ALG_MU && alg_ != ALG_NSNMF && alg_ != ALG_HALS) {
+		} else if (compute_error && alg_ != ALG_MU && alg_ != ALG_NSNMF && !hals_family(alg_)) {
 			// constant basis vectors, LS algorithms: the reference's trace reads W against itself
 			// (ALS/ACLS/AHCLS :199-205 with W never overwritten) or a stale buffer (GDCLS); here:
 			// ALS family as the reference, GDCLS the product the formula names.

@@ -16,7 +16,10 @@
 namespace nmfamd {
 
 // ALG_HALS: coordinate descent (kernels_hals.hip, docs/HALS.md) -- the generic launch sequence only, single-engine runs only (no three-phase / sharded form)
-enum Algorithm { ALG_MU = 0, ALG_GDCLS = 1, ALG_ALS = 2, ALG_ACLS = 3, ALG_AHCLS = 4, ALG_NSNMF = 5, ALG_HALS = 6 };
+// ALG_NENMF: the HALS iteration with accelerated projected-gradient steps in place of the sweeps (kernels_nenmf.hip, docs/NENMF.md); HALS's limits
+enum Algorithm { ALG_MU = 0, ALG_GDCLS = 1, ALG_ALS = 2, ALG_ACLS = 3, ALG_AHCLS = 4, ALG_NSNMF = 5, ALG_HALS = 6, ALG_NENMF = 7 };
+// the two algorithms that share the HALS iteration (products, slabs, ps, trace, normalisation, penalties, constant W) and differ in the step of a factor
+inline bool hals_family(int alg) { return alg == ALG_HALS || alg == ALG_NENMF; }
 
 struct AlgorithmParams {
 	double lambda = 0, lambdaW = 0, lambdaH = 0, alphaW = 0, alphaH = 0, theta = 0;
@@ -35,6 +38,9 @@ struct AlgorithmParams {
 	// HALS: the tolerance delta of the per-column dynamic stopping rule (docs/HALS.md, "Dynamic stopping"), in [0, 1); 0: static counts.  With delta > 0 the
 	// counts above are maximum counts.  Engine::set_hals_sweep_tolerance changes it between iterations.
 	double sweep_tolerance = 0;
+	// NeNMF: projected-gradient steps per product in the H step and in the W step (docs/NENMF.md); integers in 1 ... 256.  Engine::set_nenmf_steps changes them
+	// between iterations.
+	double steps_h = APG_STEPS_DEFAULT, steps_w = APG_STEPS_DEFAULT;
 	double dense_compute = 0;  // 1 with divergence = 1: the KL update on a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) instead of over the stored entries
 	double beta_value = 0;      // divergence = 3: the beta of the divergence, any finite value (0 and 1 run the Itakura-Saito and dense KL engines as they are)
 	double weighted = 0;        // 1 on a dense divergence engine: per-entry weights uploaded beside V (upload_dense_weighted; kernels_beta_weighted.hip, docs/DIVERGENCE.md)
@@ -72,6 +78,16 @@ inline const char* hals_sweeps_fault(double sweeps_h, double sweeps_w, bool is_h
 		if (!(x >= HALS_SWEEPS_MIN && x <= HALS_SWEEPS_MAX) || x != (double)(int)x) return "HALS sweeps: sweepsH and sweepsW must be integers in 1 ... 64";
 	}
 	if ((sweeps_h != 1 || sweeps_w != 1) && !is_hals) return "HALS sweeps: only the HALS algorithm takes sweepsH / sweepsW other than 1";
+	return nullptr;
+}
+
+// What the step counts of NeNMF must satisfy, stated once for Engine::set_nenmf_steps and nmfgpu::compute (which reads them from Parameters, as doubles): nullptr,
+// or why not.  given: the caller named a count (a Parameter, the setter), which only a NeNMF engine takes.
+inline const char* nenmf_steps_fault(double steps_h, double steps_w, bool given, bool is_nenmf) {
+	if (given && !is_nenmf) return "NeNMF steps: only the NeNMF algorithm takes stepsH / stepsW";
+	for (double x : {steps_h, steps_w}) {
+		if (!(x >= APG_STEPS_MIN && x <= APG_STEPS_MAX) || x != (double)(int)x) return "NeNMF steps: stepsH and stepsW must be integers in 1 ... 256";
+	}
 	return nullptr;
 }
 
@@ -188,6 +204,9 @@ public:
 	// bit for bit.  Valid any time between iterations.  ST_INVALID with last_error() for a value outside [0, 1), NaN included, and for a non-zero one on an engine
 	// of another algorithm.
 	Status set_hals_sweep_tolerance(double delta);
+	// NeNMF: projected-gradient steps per product of the iterations that follow, h in the H step and w in the W step (1 ... 256).  Valid any time between
+	// iterations.  ST_INVALID with last_error() for a count out of range, and on an engine of another algorithm.
+	Status set_nenmf_steps(int h, int w);
 	// HALS: the sweeps applied per column of H (which = 0, n entries) or row of W (which = 1, m entries) in the most recent step of that factor.  Waits for the
 	// stream.  The number of entries copied; negative on another engine, for another `which`, for a capacity too small and before any such step.
 	long hals_sweep_counts(int which, int* out, long capacity);
@@ -280,7 +299,7 @@ public:
 	int rp() const { return RP_; }
 	// GDCLS and the ALS family evaluate tr(H^T W^T V) as r terms (one per factor row, from the reduced sums: identical on every rank of a
 	// column-sharded run); the multiplicative algorithms as one term per column of V
-	bool error_terms_per_factor_row() const { return alg_ != ALG_MU && alg_ != ALG_NSNMF && alg_ != ALG_HALS; }
+	bool error_terms_per_factor_row() const { return alg_ != ALG_MU && alg_ != ALG_NSNMF && !hals_family(alg_); }
 	int algorithm() const { return alg_; }
 	long mpad() const { return mpad_; }
 	long npad() const { return npad_; }
@@ -368,6 +387,13 @@ private:
 	int hals_static_h_ = 0, hals_static_w_ = 0;      // > 0: that step ran this fixed number of sweeps (tolerance 0, or a maximum of 1) and wrote no counts
 	// one panel sweep launch of an HALS step, static or dynamic by prm_.sweep_tolerance, and the counts of the step
 	Status hals_sweeps(bool w_step, T* P, const T* G, int S, int len_pad, int len_valid, T* ps, T* sumsq_part, T l1, T l2);
+	// NeNMF: the launch of prm_.steps_h / steps_w projected-gradient steps in the same place, on the same arrays
+	Status apg_steps(bool w_step, T* P, const T* G, int S, int len_pad, int len_valid, T* ps, T* sumsq_part, T l1, T l2);
+	// the step of a factor of whichever of the two algorithms the engine runs, and the number of partial sums of squares its W step leaves
+	Status family_step(bool w_step, T* P, const T* G, int S, int len_pad, int len_valid, T* ps, T* sumsq_part, T l1, T l2) {
+		return alg_ == ALG_NENMF ? apg_steps(w_step, P, G, S, len_pad, len_valid, ps, sumsq_part, l1, l2) : hals_sweeps(w_step, P, G, S, len_pad, len_valid, ps, sumsq_part, l1, l2);
+	}
+	int family_parts(int len_pad) const { return alg_ == ALG_NENMF ? panel_steps_apg_parts(RP_, sizeof(T), len_pad) : panel_sweep_hals_parts(RP_, sizeof(T), len_pad); }
 	// bf16-operand products (kernels_bf16.hip): fragment-ordered bf16 images of V, Vt and of the two factor panels
 	bool bf16_ = false;
 	void *Vb_ = nullptr, *Vtb_ = nullptr, *Wtb_ = nullptr, *Hb_ = nullptr;

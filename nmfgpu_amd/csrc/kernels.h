@@ -288,6 +288,18 @@ hipError_t launch_panel_sweeps_hals(T* P, const T* slabs, int S, long slab_strid
 template <typename T>
 hipError_t launch_panel_sweeps_hals_dyn(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part,
                                         hipStream_t stream, T l1, T l2, int sweeps, double tol, int* counts);
+// NeNMF (kernels_nenmf.hip; docs/NENMF.md): `steps` Nesterov-accelerated projected-gradient steps of the panel against G and the summed slabs in one launch, on the
+// arrays of launch_panel_sweeps_hals and with its outputs (ps and sumsq_part from the final projected iterate, panel_steps_apg_parts() partials).  The step length
+// is 1 / L, L = max row sum of G + l2, computed inside the launch; L <= 0 or not finite: the panel keeps its values.  Padded ranks 64 and 128 in both precisions;
+// steps outside APG_STEPS_MIN ... APG_STEPS_MAX, another rank, a negative or non-finite penalty: hipErrorInvalidValue.
+constexpr int APG_STEPS_MIN = 1, APG_STEPS_MAX = 256, APG_STEPS_DEFAULT = 8;
+bool panel_steps_apg_available(int RP, size_t elem);
+int panel_steps_apg_parts(int RP, size_t elem, int len_pad);
+// c[t] = (alpha_t - 1) / alpha_{t+1}, alpha_0 = 1, alpha_{t+1} = (1 + sqrt(4 alpha_t^2 + 1)) / 2, t < steps: the extrapolation behind step t, in double
+void apg_momentum(int steps, double* out);
+template <typename T>
+hipError_t launch_panel_steps_apg(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part,
+                                  hipStream_t stream, T l1, T l2, int steps);
 // W(:, c) <- W(:, c) / d(c), H(c, :) <- H(c, :) d(c) where d(c) = ||W(:, c)|| > 0, d from `parts` vectors of partial sums of squares (W H unchanged);
 // sumsq_part needs RP elements of scratch behind the partials
 template <typename T>

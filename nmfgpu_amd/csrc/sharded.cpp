@@ -27,7 +27,7 @@ ShardedRank<T>::~ShardedRank() {
 template <typename T>
 Status ShardedRank<T>::prepare() {
 	if (!eng_ || !comm_ || (mode_ != SHARD_ROW_BLOCKS && mode_ != SHARD_REPLICATED)) return ST_INVALID;
-	if (eng_->algorithm() == ALG_HALS) { last_error_ = "HALS: no sharded form"; return ST_INVALID; }
+	if (hals_family(eng_->algorithm())) { last_error_ = "HALS: no sharded form"; return ST_INVALID; }
 	if (eng_->is_masked()) { last_error_ = "missing values: no sharded form"; return ST_INVALID; }
 	if (eng_->is_beta_dense()) { last_error_ = "dense divergence update: no sharded form (single GPU)"; return ST_INVALID; }
 	if (eng_->is_kl() && mode_ != SHARD_REPLICATED) { last_error_ = "KL update: the sharded W step is the replicated form (shard mode 1)"; return ST_INVALID; }

@@ -8,7 +8,7 @@ import numpy as np
 
 from ._lib import library
 
-ALGORITHMS = {"mu": 0, "gdcls": 1, "als": 2, "acls": 3, "ahcls": 4, "nsnmf": 5, "hals": 6}
+ALGORITHMS = {"mu": 0, "gdcls": 1, "als": 2, "acls": 3, "ahcls": 4, "nsnmf": 5, "hals": 6, "nenmf": 7}
 _STATUS = {0: "ok", 1: "invalid argument", 2: "out of device memory", 3: "out of host memory", 4: "HIP error", 5: "no HIP device",
            6: "values outside the exact range of the split-operand product"}
 
@@ -87,7 +87,8 @@ class Engine:
                  lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence: str = "frobenius",
                  sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False,
                  l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None, weighted: bool = False, mixed_precision: bool = False,
-                 batch_size=None, forget_factor=0.7, sweeps_h: int = 1, sweeps_w: int = 1, sweep_tolerance: float = 0.0):
+                 batch_size=None, forget_factor=0.7, sweeps_h: int = 1, sweeps_w: int = 1, sweep_tolerance: float = 0.0,
+                 steps_h: Optional[int] = None, steps_w: Optional[int] = None):
         """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V),
         "is" (Itakura-Saito, always dense: every entry of V > 0) or "beta" (the beta-divergence at `beta`, any finite value, always dense: scikit-learn's
         solver="mu" with beta_loss=beta; beta=0.0 and beta=1.0 are the "is" and the dense "kl" engines; beta <= 0 needs every entry of V > 0) --
@@ -117,7 +118,10 @@ class Engine:
         sweeps"); see set_sweeps.
 
         sweep_tolerance ("hals" only; in [0, 1)): per-column dynamic stopping of the inner sweeps, with sweeps_h / sweeps_w as maximum counts (docs/HALS.md, "Dynamic
-        stopping"); 0 keeps the static counts; see set_sweep_tolerance."""
+        stopping"); 0 keeps the static counts; see set_sweep_tolerance.
+
+        steps_h, steps_w ("nenmf" only; 1 ... 256, None = the library's 8): NeNMF, that many accelerated projected-gradient steps per product in the H step and
+        in the W step (docs/NENMF.md); see set_steps.  "nenmf" takes the penalties and sparse_compute of "hals"; rank <= 128."""
         if not batch_size:
             batch_size, forget_factor = 0.0, 0.0
         self._bind(m, n, r, dtype)
@@ -130,7 +134,8 @@ class Engine:
                                   float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
                                   float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted), float(mixed_precision), float(batch_size), float(forget_factor)],
                           penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)], sweeps=[_count(sweeps_h), _count(sweeps_w)],
-                          sweep_tolerance=float(sweep_tolerance))
+                          sweep_tolerance=float(sweep_tolerance),
+                          steps=None if steps_h is None and steps_w is None else [_count(8 if steps_h is None else steps_h), _count(8 if steps_w is None else steps_w)])
         self._create()
 
     def _bind(self, m, n, r, dtype):
@@ -179,6 +184,8 @@ class Engine:
                 self.set_sweeps(*c["sweeps"])
             if c["sweep_tolerance"] != 0.0:      # (likewise)
                 self.set_sweep_tolerance(c["sweep_tolerance"])
+            if c.get("steps") is not None:      # (likewise; given counts go to the library whatever the algorithm, which refuses them on any but "nenmf")
+                self.set_steps(*c["steps"])
         except EngineError:
             self.close()
             raise
@@ -286,6 +293,15 @@ class Engine:
         self._check(self._lib.nmfamd_engine_set_hals_sweeps(self._h, *(C.c_int(v) for v in vals)), "set_hals_sweeps")
         if self._ctor is not None:
             self._ctor["sweeps"] = vals
+
+    def set_steps(self, h: int = 8, w: int = 8):
+        """NeNMF: the iterations that follow take h accelerated projected-gradient steps per H step and w per W step against one set of products each
+        (nmfamd_engine_set_nenmf_steps; docs/NENMF.md).  Integers in 1 ... 256.  Valid between iterations; with constant_w only h matters.  Raises EngineError
+        on an engine of another algorithm."""
+        vals = [_count(h), _count(w)]
+        self._check(self._lib.nmfamd_engine_set_nenmf_steps(self._h, *(C.c_int(v) for v in vals)), "set_nenmf_steps")
+        if self._ctor is not None:
+            self._ctor["steps"] = vals
 
     def set_sweep_tolerance(self, tol: float = 0.0):
         """HALS: per-column dynamic stopping of the inner sweeps in the iterations that follow (nmfamd_engine_set_hals_sweep_tolerance; docs/HALS.md, "Dynamic
@@ -701,7 +717,8 @@ def op_tri_update(P: np.ndarray, num: np.ndarray, Q: np.ndarray, *, old_colsq: O
 
 
 def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_valid: int, *, ps: Optional[np.ndarray] = None,
-                  sumsq_part: Optional[np.ndarray] = None, penalties: Optional[tuple] = None, _sweeps: Optional[int] = None, _tol: Optional[float] = None):
+                  sumsq_part: Optional[np.ndarray] = None, penalties: Optional[tuple] = None, _sweeps: Optional[int] = None, _tol: Optional[float] = None,
+                  _apg: bool = False):
     """One launch of the HALS sweep (nmfamd_op_hals_sweep_*; with penalties = (l1, l2) through nmfamd_op_hals_sweep_pen_*, zeros included) on padded arrays: P (len_pad, RP) panel columns, slabs (S, slab_stride) with
     slab_stride >= len_pad * RP (slab s is the first len_pad * RP values of row s; the rest of the row is a gap the kernel must not read), G (RP, RP).
     ps (len_pad values) and sumsq_part ((len_pad // 16) * RP values), when given, are copied in before the launch, so entries the kernel leaves
@@ -726,7 +743,9 @@ def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_v
     parts = C.c_int(0)
     lib, real = library(), (C.c_float if dt == np.float32 else C.c_double)
     counts = None
-    if _tol is not None:         # (op_hals_sweeps_dyn)
+    if _apg:                     # (op_apg_steps)
+        fn, extra = (lib.nmfamd_op_apg_steps_f32 if dt == np.float32 else lib.nmfamd_op_apg_steps_f64), (real(penalties[0]), real(penalties[1]), C.c_int(_sweeps))
+    elif _tol is not None:       # (op_hals_sweeps_dyn)
         counts = np.full(len_pad, -1, dtype=np.int32)
         fn = lib.nmfamd_op_hals_sweeps_dyn_f32 if dt == np.float32 else lib.nmfamd_op_hals_sweeps_dyn_f64
         extra = (real(penalties[0]), real(penalties[1]), C.c_int(_sweeps), C.c_double(_tol), C.c_void_p(counts.ctypes.data))
@@ -761,6 +780,14 @@ def op_hals_sweeps_dyn(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, 
     docs/HALS.md "Dynamic stopping"), on the arrays of op_hals_sweep.  Returns what op_hals_sweeps returns plus `counts` (len_pad np.int32 values: the sweeps applied
     to each column, 0 on padding).  Always the dynamic kernel, one sweep included; tol outside (0, 1) is refused."""
     return op_hals_sweep(P, slabs, G, r, len_valid, ps=ps, sumsq_part=sumsq_part, penalties=(l1, l2), _sweeps=int(sweeps), _tol=float(tol))
+
+
+def op_apg_steps(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_valid: int, steps: int, *, l1=0.0, l2=0.0, ps: Optional[np.ndarray] = None,
+                 sumsq_part: Optional[np.ndarray] = None):
+    """One launch of `steps` accelerated projected-gradient steps of NeNMF with the penalties (l1, l2) (nmfamd_op_apg_steps_*; kernels_nenmf.hip, docs/NENMF.md),
+    on the arrays of op_hals_sweep and with its result; ps and sumsq_part describe the final projected iterate, `parts` = len_pad / 32 (float32) or len_pad / 16
+    (float64).  Padded ranks 64 and 128; steps outside 1 ... 256 are refused."""
+    return op_hals_sweep(P, slabs, G, r, len_valid, ps=ps, sumsq_part=sumsq_part, penalties=(l1, l2), _sweeps=_count(steps), _apg=True)
 
 
 def op_beta_half_step(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: int, out_valid: int, red_valid: int, beta: int, form: int = 0, *,
