@@ -96,7 +96,7 @@ enum class NmfAlgorithm {
 	AHCLS,           // ACLS with Hoyer sparseness terms alphaW / alphaH
 	nsNMF,           // non-smooth NMF (theta)
 	HALS,            // hierarchical alternating least squares / coordinate descent (extension: optional penalties "l1W", "l1H", "l2W", "l2H", sweeps per product "sweepsH", "sweepsW", their per-column stopping tolerance "sweepsTolerance", "sparseCompute"; single GPU)
-	NeNMF,           // the HALS iteration with Nesterov-accelerated projected-gradient steps in place of the sweeps (extension, docs/NENMF.md: steps per product "stepsH", "stepsW" in 1 ... 256, absent = 8; the penalties and "sparseCompute" of HALS; at most 128 features; single GPU)
+	NeNMF,           // the HALS iteration with Nesterov-accelerated projected-gradient steps in place of the sweeps (extension, docs/NENMF.md: steps per product "stepsH", "stepsW" in 1 ... 256, absent = 8, maximum counts with a "stepsTolerance" in (0, 1), absent = 0; the penalties and "sparseCompute" of HALS; at most 128 features; single GPU)
 };
 
 // ref: include/nmfgpu.h:117-126.  Console output level (process wide).

@@ -222,6 +222,17 @@ NMFAMD_API long nmfamd_engine_hals_sweep_counts(nmfamd_engine* e, int which, int
  * the next nmfamd_engine_iterate.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error) for a count outside 1 ... 256, and on any other engine.  On a NeNMF
  * engine nmfamd_engine_set_hals_sweeps refuses a count other than 1 and nmfamd_engine_set_hals_sweep_tolerance a value other than 0. */
 NMFAMD_API int nmfamd_engine_set_nenmf_steps(nmfamd_engine* e, int steps_h, int steps_w);
+/* NeNMF engines: per-column dynamic stopping of the projected-gradient steps (docs/NENMF.md, "Dynamic stopping").  With delta in (0, 1) the counts of
+ * nmfamd_engine_set_nenmf_steps become maximum counts: within one step launch a column of the panel is frozen after its step t when |P_{t+1} - Y_t|^2 of that
+ * column is at most delta^2 times that of its first step, keeps P_{t+1} and is not stepped again.  0, the default, runs the static counts, bit for bit.  Valid any
+ * time between iterations; takes effect at the next nmfamd_engine_iterate.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error) for a negative or
+ * non-finite value, for a value of 1 or more, and for any value on an engine of another algorithm. */
+NMFAMD_API int nmfamd_engine_set_nenmf_step_tolerance(nmfamd_engine* e, double delta);
+/* NeNMF engines: the steps applied to each column of H (which = 0: n entries) or row of W (which = 1: m entries) by the most recent step launch of that factor,
+ * 1 ... the maximum count (the maximum itself for every entry while the tolerance is 0; 0 for every entry where L admitted no step).  Synchronises.  Returns the
+ * number of entries copied, or a negative value: on an engine of another algorithm, for another `which`, for capacity below n (m), and before any step of that
+ * factor -- with constant W no W step runs, so which = 1 keeps returning what it returned before. */
+NMFAMD_API long nmfamd_engine_nenmf_step_counts(nmfamd_engine* e, int which, int* out, long capacity);
 /* Frobenius norm / RMSD of the most recent error iteration (IAlgorithm::frobeniusNorm / rmsd). */
 NMFAMD_API double nmfamd_engine_frobenius(nmfamd_engine* e);
 NMFAMD_API double nmfamd_engine_rmsd(nmfamd_engine* e);
@@ -486,6 +497,13 @@ NMFAMD_API int nmfamd_op_apg_steps_f32(float* P, const float* slabs, int S, long
                                        float* ps, float* sumsq_part, int* parts, float l1, float l2, int steps);
 NMFAMD_API int nmfamd_op_apg_steps_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid,
                                        double* ps, double* sumsq_part, int* parts, double l1, double l2, int steps);
+/* At most `steps` steps with per-column dynamic stopping at the tolerance tol (kernels_nenmf_dyn.hip; docs/NENMF.md, "Dynamic stopping"), always through
+ * k_apg_steps_dyn, one step included.  counts (len_pad values, may be NULL): the steps applied to each column, 0 on padding.  NMFAMD_INVALID_ARGUMENT also for tol
+ * outside (0, 1), NaN included. */
+NMFAMD_API int nmfamd_op_apg_steps_dyn_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid,
+                                           float* ps, float* sumsq_part, int* parts, float l1, float l2, int steps, float tol, int* counts);
+NMFAMD_API int nmfamd_op_apg_steps_dyn_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid,
+                                           double* ps, double* sumsq_part, int* parts, double l1, double l2, int steps, double tol, int* counts);
 /* The HALS column normalisation on host panels Wt [mpad][RP] and H [npad][RP] (both updated in place) from parts x RP partial sums of squares:
  * d(c) = sqrt(sum of the parts); where d(c) > 0, Wt(:, c) / d(c) and H(:, c) * d(c). */
 NMFAMD_API int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad, const float* sumsq_part, int parts);

@@ -270,7 +270,8 @@ def compute(V, W: np.ndarray, H: np.ndarray, *, algorithm: NmfAlgorithm = NmfAlg
     makes the counts maximum counts: every column stops sweeping by itself (docs/HALS.md, "Dynamic stopping"; in [0, 1), absent = 0).
 
     ``parameters={"stepsH": 16, "stepsW": 16}`` with the NeNMF algorithm: that many Nesterov-accelerated projected-gradient steps per product in the H and in
-    the W step (integers in 1 ... 256, absent = 8; docs/NENMF.md), next to the penalties and "sparseCompute" of HALS; at most 128 features."""
+    the W step (integers in 1 ... 256, absent = 8; docs/NENMF.md), next to the penalties and "sparseCompute" of HALS; at most 128 features.  ``"stepsTolerance": 0.1``
+    makes the counts maximum counts: every column stops stepping by itself (docs/NENMF.md, "Dynamic stopping"; in [0, 1), absent = 0)."""
     if W.dtype != H.dtype:
         raise TypeError("W and H must share a dtype")
     d = NmfDescription()

@@ -319,6 +319,14 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 			log_error((std::string("[ERROR] ") + why).c_str());
 			return ResultType::ErrorInvalidArgument;
 		}
+		// "stepsTolerance": the tolerance of NeNMF's per-column dynamic stopping rule (docs/NENMF.md, "Dynamic stopping"); absent = 0 (static counts), in [0, 1),
+		// other than 0 only with NeNMF -- the counts above are then maximum counts
+		const int it = parameter_index(d.parameters, d.numParameters, "stepsTolerance");
+		if (it >= 0) prm.steps_tolerance = d.parameters[it].value;
+		if (const char* why = nmfamd::nenmf_step_tolerance_fault(prm.steps_tolerance, prm.steps_tolerance != 0, d.algorithm == NmfAlgorithm::NeNMF)) {
+			log_error((std::string("[ERROR] ") + why).c_str());
+			return ResultType::ErrorInvalidArgument;
+		}
 		if (d.algorithm == NmfAlgorithm::NeNMF && !nmfamd::panel_steps_apg_available(nmfamd::padded_rank((int)d.features, prm.sparse_compute != 0 ? 4 : sizeof(T)), sizeof(T))) {
 			log_error("[ERROR] The NeNMF algorithm supports 1 ... 128 features!");
 			return ResultType::ErrorInvalidArgument;

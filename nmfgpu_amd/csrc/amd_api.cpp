@@ -348,6 +348,16 @@ int nmfamd_engine_set_nenmf_steps(nmfamd_engine* e, int steps_h, int steps_w) {
 	return dispatch(e, set, set);
 }
 
+int nmfamd_engine_set_nenmf_step_tolerance(nmfamd_engine* e, double delta) {
+	auto set = [&](auto& g) { return g.set_nenmf_step_tolerance(delta); };
+	return dispatch(e, set, set);
+}
+
+long nmfamd_engine_nenmf_step_counts(nmfamd_engine* e, int which, int* out, long capacity) {
+	if (!e || !out) return -1;
+	return e->elem_bytes == 4 ? e->f->nenmf_step_counts(which, out, capacity) : e->d->nenmf_step_counts(which, out, capacity);
+}
+
 long nmfamd_engine_hals_sweep_counts(nmfamd_engine* e, int which, int* out, long capacity) {
 	if (!e || !out) return -1;
 	return e->elem_bytes == 4 ? e->f->hals_sweep_counts(which, out, capacity) : e->d->hals_sweep_counts(which, out, capacity);
@@ -874,7 +884,8 @@ template <typename T>
 int op_hals_sweep(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part, int* parts, T l1 = T(0), T l2 = T(0),
                   int sweeps = 0, bool dyn = false, double tol = 0, int* counts = nullptr, bool apg = false) {
 	// sweeps == 0: the single-sweep launcher itself (nmfamd_op_hals_sweep_*, _pen_*); otherwise launch_panel_sweeps_hals, which decides about the count;
-	// dyn: launch_panel_sweeps_hals_dyn with tol and (optionally) counts; apg: launch_panel_steps_apg with `sweeps` as its step count (nmfamd_op_apg_steps_*)
+	// dyn: launch_panel_sweeps_hals_dyn with tol and (optionally) counts; apg: launch_panel_steps_apg with `sweeps` as its step count (nmfamd_op_apg_steps_*);
+	// apg and dyn: launch_panel_steps_apg_dyn with tol and (optionally) counts (nmfamd_op_apg_steps_dyn_*)
 	if (!P || !slabs || !G || !parts || S < 1 || RP < 1 || RP > 4096 || len_pad < 1 || slab_stride < (long)len_pad * RP) return NMFAMD_INVALID_ARGUMENT;
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	const int np = apg ? panel_steps_apg_parts(RP, sizeof(T), len_pad) : panel_sweep_hals_parts(RP, sizeof(T), len_pad);
@@ -888,7 +899,10 @@ int op_hals_sweep(T* P, const T* slabs, int S, long slab_stride, const T* G, int
 	    hipMemcpy(dG.p, G, sizeof(T) * (size_t)RP * RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (ps && hipMemcpy(dPs.p, ps, sizeof(T) * (size_t)len_pad, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (sumsq_part && np > 0 && hipMemcpy(dSq.p, sumsq_part, sizeof(T) * (size_t)np * RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
-	const hipError_t err = apg         ? launch_panel_steps_apg<T>((T*)dP.p, (const T*)dS.p, S, slab_stride, (const T*)dG.p, RP, r, len_pad, len_valid,
+	const hipError_t err = apg && dyn  ? launch_panel_steps_apg_dyn<T>((T*)dP.p, (const T*)dS.p, S, slab_stride, (const T*)dG.p, RP, r, len_pad, len_valid,
+	                                                                   ps ? (T*)dPs.p : nullptr, sumsq_part ? (T*)dSq.p : nullptr, nullptr, l1, l2, sweeps, (T)tol,
+	                                                                   counts ? (int*)dCnt.p : nullptr)
+	                       : apg       ? launch_panel_steps_apg<T>((T*)dP.p, (const T*)dS.p, S, slab_stride, (const T*)dG.p, RP, r, len_pad, len_valid,
 	                                                               ps ? (T*)dPs.p : nullptr, sumsq_part ? (T*)dSq.p : nullptr, nullptr, l1, l2, sweeps)
 	                       : dyn       ? launch_panel_sweeps_hals_dyn<T>((T*)dP.p, (const T*)dS.p, S, slab_stride, (const T*)dG.p, RP, r, len_pad, len_valid,
 	                                                                     ps ? (T*)dPs.p : nullptr, sumsq_part ? (T*)dSq.p : nullptr, nullptr, l1, l2, sweeps, tol,
@@ -1124,6 +1138,16 @@ int nmfamd_op_apg_steps_f32(float* P, const float* slabs, int S, long slab_strid
 int nmfamd_op_apg_steps_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid, double* ps,
                             double* sumsq_part, int* parts, double l1, double l2, int steps) {
 	return op_hals_sweep<double>(P, slabs, S, slab_stride, G, RP, r, len_pad, len_valid, ps, sumsq_part, parts, l1, l2, steps, false, 0, nullptr, true);
+}
+
+int nmfamd_op_apg_steps_dyn_f32(float* P, const float* slabs, int S, long slab_stride, const float* G, int RP, int r, int len_pad, int len_valid, float* ps,
+                                float* sumsq_part, int* parts, float l1, float l2, int steps, float tol, int* counts) {
+	return op_hals_sweep<float>(P, slabs, S, slab_stride, G, RP, r, len_pad, len_valid, ps, sumsq_part, parts, l1, l2, steps, true, tol, counts, true);
+}
+
+int nmfamd_op_apg_steps_dyn_f64(double* P, const double* slabs, int S, long slab_stride, const double* G, int RP, int r, int len_pad, int len_valid, double* ps,
+                                double* sumsq_part, int* parts, double l1, double l2, int steps, double tol, int* counts) {
+	return op_hals_sweep<double>(P, slabs, S, slab_stride, G, RP, r, len_pad, len_valid, ps, sumsq_part, parts, l1, l2, steps, true, tol, counts, true);
 }
 
 int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad, const float* sumsq_part, int parts) {

@@ -184,6 +184,7 @@ Status Engine<T>::allocate() {
 	if (Status s = set_hals_penalties(prm_.l1W, prm_.l1H, prm_.l2W, prm_.l2H)) return s;      // (values that came with the parameters: the setter's checks, and its rounding of prm_ to T)
 	if (const char* why = hals_sweeps_fault(prm_.sweeps_h, prm_.sweeps_w, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = hals_sweep_tolerance_fault(prm_.sweep_tolerance, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
+	if (const char* why = nenmf_step_tolerance_fault(prm_.steps_tolerance, prm_.steps_tolerance != 0, alg_ == ALG_NENMF)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = beta_dense_fault(prm_, alg_ == ALG_MU, r_, row_blocks_)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = weighted_fault(prm_)) { last_error_ = why; return ST_INVALID; }
 	beta_dense_ = prm_.is_beta_dense();
@@ -432,8 +433,8 @@ Status Engine<T>::allocate() {
 	HIPX(dalloc(&gram_part_, rr * gram_parts_));
 	HIPX(dalloc(&sumsq_part_, ((long)std::max({panel_update_parts(RP_, sizeof(T), (int)mpad_), (int)(mpad_ / panel_update_rows(RP_, sizeof(T))),
 	                                           hals_family(alg_) ? family_parts((int)mpad_) : 0}) + 16) * RP_));
-	if (alg_ == ALG_HALS) {
-		// the sweep counts of the most recent H and W step (dynamic stopping, docs/HALS.md)
+	if (hals_family(alg_)) {
+		// the sweep (step) counts of the most recent H and W step (dynamic stopping, docs/HALS.md, docs/NENMF.md)
 		HIPX(hipMalloc((void**)&hals_counts_h_, sizeof(int) * (size_t)npad_));
 		HIPX(hipMemsetAsync(hals_counts_h_, 0, sizeof(int) * (size_t)npad_, stream_));
 		HIPX(hipMalloc((void**)&hals_counts_w_, sizeof(int) * (size_t)mpad_));
@@ -2160,8 +2161,29 @@ Status Engine<T>::set_nenmf_steps(int h, int w) {
 }
 
 template <typename T>
+Status Engine<T>::set_nenmf_step_tolerance(double delta) {
+	if (const char* why = nenmf_step_tolerance_fault(delta, true, alg_ == ALG_NENMF)) { last_error_ = why; return ST_INVALID; }
+	prm_.steps_tolerance = delta;
+	return ST_OK;
+}
+
+// The steps of one NeNMF step launch against slabs_ and G, routed as hals_sweeps routes the sweeps.  Tolerance 0: launch_panel_steps_apg, as before the tolerance
+// existed; the counts are the static count and are written when somebody asks.  Tolerance > 0 and a maximum of one step: the same launch and counts of 1.
+// Otherwise the dynamic kernel, which writes the counts itself.
+template <typename T>
 Status Engine<T>::apg_steps(bool w_step, T* P, const T* G, int S, int len_pad, int len_valid, T* ps, T* sumsq_part, T l1, T l2) {
-	HIPX(launch_panel_steps_apg<T>(P, slabs_, S, slab_stride_, G, RP_, r_, len_pad, len_valid, ps, sumsq_part, stream_, l1, l2, (int)(w_step ? prm_.steps_w : prm_.steps_h)));
+	const int steps = (int)(w_step ? prm_.steps_w : prm_.steps_h);
+	(w_step ? hals_counts_w_valid_ : hals_counts_h_valid_) = true;
+	if (prm_.steps_tolerance > 0 && steps > 1) {
+		// (a double in (0, 1) may round to 0 or to 1 in a float engine: kept inside the launcher's open interval)
+		const T tol = std::min(std::max((T)prm_.steps_tolerance, std::numeric_limits<T>::min()), std::nextafter(T(1), T(0)));
+		HIPX(launch_panel_steps_apg_dyn<T>(P, slabs_, S, slab_stride_, G, RP_, r_, len_pad, len_valid, ps, sumsq_part, stream_, l1, l2, steps, tol,
+		                                   w_step ? hals_counts_w_ : hals_counts_h_));
+		(w_step ? hals_static_w_ : hals_static_h_) = 0;
+		return ST_OK;
+	}
+	HIPX(launch_panel_steps_apg<T>(P, slabs_, S, slab_stride_, G, RP_, r_, len_pad, len_valid, ps, sumsq_part, stream_, l1, l2, steps));
+	(w_step ? hals_static_w_ : hals_static_h_) = steps;
 	return ST_OK;
 }
 
@@ -2186,18 +2208,37 @@ Status Engine<T>::hals_sweeps(bool w_step, T* P, const T* G, int S, int len_pad,
 template <typename T>
 long Engine<T>::hals_sweep_counts(int which, int* out, long capacity) {
 	if (alg_ != ALG_HALS) { last_error_ = "HALS sweep counts: only a HALS engine has them"; return -1; }
-	if (which != 0 && which != 1) { last_error_ = "HALS sweep counts: which has to be 0 (H) or 1 (W)"; return -1; }
+	return family_counts(which, out, capacity);
+}
+
+template <typename T>
+long Engine<T>::nenmf_step_counts(int which, int* out, long capacity) {
+	if (alg_ != ALG_NENMF) { last_error_ = "NeNMF step counts: only a NeNMF engine has them"; return -1; }
+	return family_counts(which, out, capacity);
+}
+
+// (the counts of either algorithm of the family; the messages name the engine's own)
+template <typename T>
+long Engine<T>::family_counts(int which, int* out, long capacity) {
+	const bool ne = alg_ == ALG_NENMF;
+	if (which != 0 && which != 1) { last_error_ = ne ? "NeNMF step counts: which has to be 0 (H) or 1 (W)" : "HALS sweep counts: which has to be 0 (H) or 1 (W)"; return -1; }
 	const long len = which == 0 ? n_ : m_;
-	if (!(which == 0 ? hals_counts_h_valid_ : hals_counts_w_valid_)) { last_error_ = "HALS sweep counts: no step of this factor has run yet"; return -1; }
-	if (out == nullptr || capacity < len) { last_error_ = "HALS sweep counts: the output holds fewer than n (m) entries"; return -1; }
+	if (!(which == 0 ? hals_counts_h_valid_ : hals_counts_w_valid_)) {
+		last_error_ = ne ? "NeNMF step counts: no step of this factor has run yet" : "HALS sweep counts: no step of this factor has run yet";
+		return -1;
+	}
+	if (out == nullptr || capacity < len) {
+		last_error_ = ne ? "NeNMF step counts: the output holds fewer than n (m) entries" : "HALS sweep counts: the output holds fewer than n (m) entries";
+		return -1;
+	}
 	const int fixed = which == 0 ? hals_static_h_ : hals_static_w_;
-	if (fixed > 0) {      // (the step ran a fixed number of sweeps: nothing was written on the device)
+	if (fixed > 0) {      // (the step ran a fixed number of sweeps (steps): nothing was written on the device)
 		if (hipStreamSynchronize(stream_) != hipSuccess) return -1;
 		for (long i = 0; i < len; ++i) out[i] = fixed;
 		return len;
 	}
 	if (hipMemcpyAsync(out, which == 0 ? hals_counts_h_ : hals_counts_w_, sizeof(int) * (size_t)len, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
-	    hipStreamSynchronize(stream_) != hipSuccess) { last_error_ = "HALS sweep counts: copy failed"; return -1; }
+	    hipStreamSynchronize(stream_) != hipSuccess) { last_error_ = ne ? "NeNMF step counts: copy failed" : "HALS sweep counts: copy failed"; return -1; }
 	return len;
 }
 

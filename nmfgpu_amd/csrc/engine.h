@@ -41,6 +41,9 @@ struct AlgorithmParams {
 	// NeNMF: projected-gradient steps per product in the H step and in the W step (docs/NENMF.md); integers in 1 ... 256.  Engine::set_nenmf_steps changes them
 	// between iterations.
 	double steps_h = APG_STEPS_DEFAULT, steps_w = APG_STEPS_DEFAULT;
+	// NeNMF: the tolerance delta of the per-column dynamic stopping rule (docs/NENMF.md, "Dynamic stopping"), in [0, 1); 0: static counts.  With delta > 0 the
+	// counts above are maximum counts.  Engine::set_nenmf_step_tolerance changes it between iterations.
+	double steps_tolerance = 0;
 	double dense_compute = 0;  // 1 with divergence = 1: the KL update on a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) instead of over the stored entries
 	double beta_value = 0;      // divergence = 3: the beta of the divergence, any finite value (0 and 1 run the Itakura-Saito and dense KL engines as they are)
 	double weighted = 0;        // 1 on a dense divergence engine: per-entry weights uploaded beside V (upload_dense_weighted; kernels_beta_weighted.hip, docs/DIVERGENCE.md)
@@ -95,6 +98,14 @@ inline const char* nenmf_steps_fault(double steps_h, double steps_w, bool given,
 inline const char* hals_sweep_tolerance_fault(double delta, bool is_hals) {
 	if (!(delta >= 0 && delta < 1)) return "HALS sweep tolerance: sweepsTolerance must be a finite value in [0, 1)";      // (NaN fails both comparisons)
 	if (delta != 0 && !is_hals) return "HALS sweep tolerance: only the HALS algorithm takes a sweepsTolerance other than 0";
+	return nullptr;
+}
+
+// ... and the tolerance of NeNMF's rule, for Engine::set_nenmf_step_tolerance and nmfgpu::compute.  given: the caller named a value that only a NeNMF engine takes
+// (the setter: any value; a Parameter: a non-zero one).
+inline const char* nenmf_step_tolerance_fault(double delta, bool given, bool is_nenmf) {
+	if (!(delta >= 0 && delta < 1)) return "NeNMF step tolerance: stepsTolerance must be a finite value in [0, 1)";      // (NaN fails both comparisons)
+	if (given && !is_nenmf) return "NeNMF step tolerance: only the NeNMF algorithm takes a stepsTolerance";
 	return nullptr;
 }
 
@@ -207,6 +218,13 @@ public:
 	// NeNMF: projected-gradient steps per product of the iterations that follow, h in the H step and w in the W step (1 ... 256).  Valid any time between
 	// iterations.  ST_INVALID with last_error() for a count out of range, and on an engine of another algorithm.
 	Status set_nenmf_steps(int h, int w);
+	// NeNMF: the tolerance delta of the per-column dynamic stopping rule for the iterations that follow (docs/NENMF.md, "Dynamic stopping"); 0: the static counts,
+	// bit for bit.  Valid any time between iterations.  ST_INVALID with last_error() for a value outside [0, 1), NaN included, and on an engine of another
+	// algorithm.
+	Status set_nenmf_step_tolerance(double delta);
+	// NeNMF: the steps applied per column of H (which = 0, n entries) or row of W (which = 1, m entries) in the most recent step launch of that factor, with the
+	// contract of hals_sweep_counts.
+	long nenmf_step_counts(int which, int* out, long capacity);
 	// HALS: the sweeps applied per column of H (which = 0, n entries) or row of W (which = 1, m entries) in the most recent step of that factor.  Waits for the
 	// stream.  The number of entries copied; negative on another engine, for another `which`, for a capacity too small and before any such step.
 	long hals_sweep_counts(int which, int* out, long capacity);
@@ -381,15 +399,16 @@ private:
 	T *G_ = nullptr, *G2_ = nullptr, *HHt_ = nullptr, *Qinv_ = nullptr, *gram_part_ = nullptr;
 	T *sumsq_part_ = nullptr;
 	// HALS: the sweeps applied per column of H (npad) and per row of W (mpad) in the most recent H and W step of the dynamic kernel (0 on padding); *_valid_: a
-	// step of that factor has run
+	// step of that factor has run.  A NeNMF engine keeps the counts of its steps in the same members.
 	int *hals_counts_h_ = nullptr, *hals_counts_w_ = nullptr;
 	bool hals_counts_h_valid_ = false, hals_counts_w_valid_ = false;
 	int hals_static_h_ = 0, hals_static_w_ = 0;      // > 0: that step ran this fixed number of sweeps (tolerance 0, or a maximum of 1) and wrote no counts
 	// one panel sweep launch of an HALS step, static or dynamic by prm_.sweep_tolerance, and the counts of the step
 	Status hals_sweeps(bool w_step, T* P, const T* G, int S, int len_pad, int len_valid, T* ps, T* sumsq_part, T l1, T l2);
-	// NeNMF: the launch of prm_.steps_h / steps_w projected-gradient steps in the same place, on the same arrays
+	// NeNMF: the launch of prm_.steps_h / steps_w projected-gradient steps in the same place, on the same arrays, static or dynamic by prm_.steps_tolerance
 	Status apg_steps(bool w_step, T* P, const T* G, int S, int len_pad, int len_valid, T* ps, T* sumsq_part, T l1, T l2);
 	// the step of a factor of whichever of the two algorithms the engine runs, and the number of partial sums of squares its W step leaves
+	long family_counts(int which, int* out, long capacity);
 	Status family_step(bool w_step, T* P, const T* G, int S, int len_pad, int len_valid, T* ps, T* sumsq_part, T l1, T l2) {
 		return alg_ == ALG_NENMF ? apg_steps(w_step, P, G, S, len_pad, len_valid, ps, sumsq_part, l1, l2) : hals_sweeps(w_step, P, G, S, len_pad, len_valid, ps, sumsq_part, l1, l2);
 	}

@@ -300,6 +300,13 @@ void apg_momentum(int steps, double* out);
 template <typename T>
 hipError_t launch_panel_steps_apg(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part,
                                   hipStream_t stream, T l1, T l2, int steps);
+// ... with per-column dynamic stopping (kernels_nenmf_dyn.hip; docs/NENMF.md, "Dynamic stopping"): `steps` is the maximum; a column is frozen after step t when
+// d_t <= tol^2 d_0, d_t = |P_{t+1} - Y_t|^2 of that column, keeps P_{t+1} and is never stepped again.  counts (optional, len_pad ints): steps applied per column,
+// 0 on padding and where L admits no step.  Always the dynamic kernel, one step included; tol outside (0, 1), NaN included: hipErrorInvalidValue, beside what
+// launch_panel_steps_apg refuses.
+template <typename T>
+hipError_t launch_panel_steps_apg_dyn(T* P, const T* slabs, int S, long slab_stride, const T* G, int RP, int r, int len_pad, int len_valid, T* ps, T* sumsq_part,
+                                      hipStream_t stream, T l1, T l2, int steps, T tol, int* counts);
 // W(:, c) <- W(:, c) / d(c), H(c, :) <- H(c, :) d(c) where d(c) = ||W(:, c)|| > 0, d from `parts` vectors of partial sums of squares (W H unchanged);
 // sumsq_part needs RP elements of scratch behind the partials
 template <typename T>

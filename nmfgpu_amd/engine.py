@@ -88,7 +88,7 @@ class Engine:
                  sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False,
                  l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None, weighted: bool = False, mixed_precision: bool = False,
                  batch_size=None, forget_factor=0.7, sweeps_h: int = 1, sweeps_w: int = 1, sweep_tolerance: float = 0.0,
-                 steps_h: Optional[int] = None, steps_w: Optional[int] = None):
+                 steps_h: Optional[int] = None, steps_w: Optional[int] = None, step_tolerance: Optional[float] = None):
         """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V),
         "is" (Itakura-Saito, always dense: every entry of V > 0) or "beta" (the beta-divergence at `beta`, any finite value, always dense: scikit-learn's
         solver="mu" with beta_loss=beta; beta=0.0 and beta=1.0 are the "is" and the dense "kl" engines; beta <= 0 needs every entry of V > 0) --
@@ -121,7 +121,10 @@ class Engine:
         stopping"); 0 keeps the static counts; see set_sweep_tolerance.
 
         steps_h, steps_w ("nenmf" only; 1 ... 256, None = the library's 8): NeNMF, that many accelerated projected-gradient steps per product in the H step and
-        in the W step (docs/NENMF.md); see set_steps.  "nenmf" takes the penalties and sparse_compute of "hals"; rank <= 128."""
+        in the W step (docs/NENMF.md); see set_steps.  "nenmf" takes the penalties and sparse_compute of "hals"; rank <= 128.
+
+        step_tolerance ("nenmf" only; in [0, 1), None = 0): per-column dynamic stopping of those steps, with steps_h / steps_w as maximum counts (docs/NENMF.md,
+        "Dynamic stopping"); 0 keeps the static counts; see set_step_tolerance."""
         if not batch_size:
             batch_size, forget_factor = 0.0, 0.0
         self._bind(m, n, r, dtype)
@@ -134,7 +137,7 @@ class Engine:
                                   float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
                                   float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted), float(mixed_precision), float(batch_size), float(forget_factor)],
                           penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)], sweeps=[_count(sweeps_h), _count(sweeps_w)],
-                          sweep_tolerance=float(sweep_tolerance),
+                          sweep_tolerance=float(sweep_tolerance), step_tolerance=None if step_tolerance is None else float(step_tolerance),
                           steps=None if steps_h is None and steps_w is None else [_count(8 if steps_h is None else steps_h), _count(8 if steps_w is None else steps_w)])
         self._create()
 
@@ -186,6 +189,8 @@ class Engine:
                 self.set_sweep_tolerance(c["sweep_tolerance"])
             if c.get("steps") is not None:      # (likewise; given counts go to the library whatever the algorithm, which refuses them on any but "nenmf")
                 self.set_steps(*c["steps"])
+            if c.get("step_tolerance") is not None:      # (likewise)
+                self.set_step_tolerance(c["step_tolerance"])
         except EngineError:
             self.close()
             raise
@@ -311,6 +316,27 @@ class Engine:
         self._check(self._lib.nmfamd_engine_set_hals_sweep_tolerance(self._h, C.c_double(tol)), "set_hals_sweep_tolerance")
         if self._ctor is not None:
             self._ctor["sweep_tolerance"] = tol
+
+    def set_step_tolerance(self, tol: float = 0.0):
+        """NeNMF: per-column dynamic stopping of the projected-gradient steps in the iterations that follow (nmfamd_engine_set_nenmf_step_tolerance; docs/NENMF.md,
+        "Dynamic stopping").  With tol in (0, 1) the counts of set_steps are maximum counts: within a step launch a column is frozen after its step t when
+        |P_{t+1} - Y_t|^2 of that step is at most tol^2 times that of its first step.  0 restores the static counts, bit for bit.  Valid between iterations.
+        Raises EngineError on an engine of another algorithm."""
+        tol = float(tol)
+        self._check(self._lib.nmfamd_engine_set_nenmf_step_tolerance(self._h, C.c_double(tol)), "set_nenmf_step_tolerance")
+        if self._ctor is not None:
+            self._ctor["step_tolerance"] = tol
+
+    def step_counts(self, which: int) -> np.ndarray:
+        """NeNMF: the steps applied to each column of H (which = 0, n values) or row of W (which = 1, m values) by the most recent step launch of that factor, as
+        np.int32 (nmfamd_engine_nenmf_step_counts; synchronises), with the contract of sweep_counts."""
+        out = np.zeros(self.n if which == 0 else self.m, dtype=np.int32)
+        fn = self._lib.nmfamd_engine_nenmf_step_counts
+        fn.restype = C.c_long
+        got = fn(self._h, int(which), C.c_void_p(out.ctypes.data), C.c_long(out.size))
+        if got < 0:
+            raise EngineError(1, "nenmf_step_counts", (self._lib.nmfamd_engine_last_error(self._h) or b"").decode())
+        return out[:got]
 
     def sweep_counts(self, which: int) -> np.ndarray:
         """HALS: the sweeps applied to each column of H (which = 0, n values) or row of W (which = 1, m values) by the most recent step of that factor, as np.int32
@@ -743,7 +769,11 @@ def op_hals_sweep(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_v
     parts = C.c_int(0)
     lib, real = library(), (C.c_float if dt == np.float32 else C.c_double)
     counts = None
-    if _apg:                     # (op_apg_steps)
+    if _apg and _tol is not None:      # (op_apg_steps_dyn)
+        counts = np.full(len_pad, -1, dtype=np.int32)
+        fn = lib.nmfamd_op_apg_steps_dyn_f32 if dt == np.float32 else lib.nmfamd_op_apg_steps_dyn_f64
+        extra = (real(penalties[0]), real(penalties[1]), C.c_int(_sweeps), real(_tol), C.c_void_p(counts.ctypes.data))
+    elif _apg:                   # (op_apg_steps)
         fn, extra = (lib.nmfamd_op_apg_steps_f32 if dt == np.float32 else lib.nmfamd_op_apg_steps_f64), (real(penalties[0]), real(penalties[1]), C.c_int(_sweeps))
     elif _tol is not None:       # (op_hals_sweeps_dyn)
         counts = np.full(len_pad, -1, dtype=np.int32)
@@ -788,6 +818,14 @@ def op_apg_steps(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_va
     on the arrays of op_hals_sweep and with its result; ps and sumsq_part describe the final projected iterate, `parts` = len_pad / 32 (float32) or len_pad / 16
     (float64).  Padded ranks 64 and 128; steps outside 1 ... 256 are refused."""
     return op_hals_sweep(P, slabs, G, r, len_valid, ps=ps, sumsq_part=sumsq_part, penalties=(l1, l2), _sweeps=_count(steps), _apg=True)
+
+
+def op_apg_steps_dyn(P: np.ndarray, slabs: np.ndarray, G: np.ndarray, r: int, len_valid: int, steps: int, tol: float, *, l1=0.0, l2=0.0,
+                     ps: Optional[np.ndarray] = None, sumsq_part: Optional[np.ndarray] = None):
+    """One launch of at most `steps` steps of NeNMF with per-column dynamic stopping at the tolerance tol (nmfamd_op_apg_steps_dyn_*; kernels_nenmf_dyn.hip,
+    docs/NENMF.md "Dynamic stopping"), on the arrays of op_apg_steps.  Returns what op_apg_steps returns plus `counts` (len_pad np.int32 values: the steps applied to
+    each column, 0 on padding).  Always the dynamic kernel, one step included; tol outside (0, 1) is refused."""
+    return op_hals_sweep(P, slabs, G, r, len_valid, ps=ps, sumsq_part=sumsq_part, penalties=(l1, l2), _sweeps=int(steps), _tol=float(tol), _apg=True)
 
 
 def op_beta_half_step(A: np.ndarray, B: np.ndarray, X: np.ndarray, r: int, out_valid: int, red_valid: int, beta: int, form: int = 0, *,

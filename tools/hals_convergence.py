@@ -1,4 +1,4 @@
-"""usage: python tools/hals_convergence.py [ITERS] [--sweeps-h 1,2,4 --sweeps-w 1,2,4] [--sweep-tolerance 0.3,0.1] [--nenmf-steps 8,16,32]      (on the GPU box)
+"""usage: python tools/hals_convergence.py [ITERS] [--sweeps-h 1,2,4 --sweeps-w 1,2,4] [--sweep-tolerance 0.3,0.1] [--nenmf-steps 8,16,32] [--nenmf-step-tolerance 0.3,0.1]      (on the GPU box)
 HALS against the multiplicative update from the same start: the relative error ||V - W H|| / ||V|| every 10th iteration up to ITERS (default 1000), the
 iterations each algorithm needs to reach the error MU has after ITERS, and the unprofiled wall time per iteration (200 iterations without error terms) -- so
 the time to that error.  Two problems: planted (V = W0 H0 + 0.01 noise, 2 000 x 1 500, r = 20) and config 2's random shape (10 000 x 5 000, r = 64).
@@ -10,7 +10,8 @@ rule gives, rounded to the nearest integer, unless they are among the given pair
 once more per delta as MAXIMUM counts, and the row shows the mean number of sweeps a column of H and a row of W took per step (sampled at every 10th iteration,
 up to the iteration that reaches the target) next to the timings.  docs/HALS.md records the output.
 --nenmf-steps: a comma list of step counts T; one NeNMF row (docs/NENMF.md) per value at (T, T), from the same start and to the same target, timed like the HALS
-rows.  docs/NENMF.md records that output."""
+rows.  --nenmf-step-tolerance: a comma list of tolerances delta of NeNMF's per-column stopping rule (docs/NENMF.md, "Dynamic stopping"); every T runs once more
+per delta as a MAXIMUM count, with the mean number of steps per column as for --sweep-tolerance.  docs/NENMF.md records that output."""
 import argparse
 import os
 import sys
@@ -46,22 +47,26 @@ def sweep_costs(V, W, H):
     return base, out[1] - base, out[2] - base, (out[3] - base) / 4, (out[4] - base) / 4
 
 
-def curve(alg, V, W, H, iters, sweeps=(1, 1), tol=0.0, target=None, steps=None):
+def curve(alg, V, W, H, iters, sweeps=(1, 1), tol=0.0, target=None, steps=None, step_tol=0.0):
     """([(iteration, relative error)], microseconds per iteration, [(mean H count, mean W count)] per error point or None without a tolerance, and with a target
     the wall time in ms of a run from the start to the first error point at or below it, without error terms: median of three -- with a tolerance the
     iterations of a run do not cost the same, so iterations x time per iteration is only an estimate there)"""
     m, n = V.shape
-    kw = dict(steps_h=steps[0], steps_w=steps[1]) if steps is not None else {}      # (steps: the counts of a "nenmf" engine)
+    kw = dict(steps_h=steps[0], steps_w=steps[1]) if steps is not None else {}      # (steps: the counts of a "nenmf" engine; step_tol: its tolerance)
+    if step_tol > 0:
+        kw["step_tolerance"] = step_tol
     eng = na.Engine(m, n, W.shape[1], alg, sweeps_h=sweeps[0], sweeps_w=sweeps[1], sweep_tolerance=tol, **kw)
     eng.upload(V)
     eng.set_factors(W, H)
     nv = float(np.linalg.norm(V.astype(np.float64)))
-    out, counts = [], [] if tol > 0 else None
+    out, counts = [], [] if tol > 0 or step_tol > 0 else None
     for it in range(10, iters + 1, 10):
         eng.iterate(10, first_iteration=it - 9, error_every=10)
         out.append((it, eng.frobenius / nv))
         if tol > 0:
             counts.append((float(eng.sweep_counts(0).mean()), float(eng.sweep_counts(1).mean())))
+        elif step_tol > 0:
+            counts.append((float(eng.step_counts(0).mean()), float(eng.step_counts(1).mean())))
     eng.set_factors(W, H)
     eng.iterate(20, error_every=0)
     eng.synchronize()
@@ -97,6 +102,7 @@ def main():
     ap.add_argument("--sweep-tolerance", default="", help="comma list of tolerances of the dynamic stopping rule; each pair of counts runs once more per value, as maximum counts")
     ap.add_argument("--alpha", type=float, default=0.5, help="the alpha of Gillis & Glineur's rule s = 1 + alpha rho; one more HALS row runs at the counts it gives")
     ap.add_argument("--nenmf-steps", default="", help="comma list of step counts T: one NeNMF row per value at (T, T)")
+    ap.add_argument("--nenmf-step-tolerance", default="", help="comma list of tolerances of NeNMF's stopping rule; each T runs once more per value, as a maximum count")
     a = ap.parse_args()
     iters = a.iters
     pairs = list(zip((int(x) for x in a.sweeps_h.split(",")), (int(x) for x in a.sweeps_w.split(","))))
@@ -139,6 +145,9 @@ def main():
         for T in (int(x) for x in a.nenmf_steps.split(",") if x):
             cn, us_n, _, direct = curve("nenmf", V, W, H, iters, target=target, steps=(T, T))
             rows.append((f"NeNMF {T},{T}", cn, us_n, None, direct))
+            for delta in (float(x) for x in a.nenmf_step_tolerance.split(",") if x):
+                cn, us_n, counts, direct = curve("nenmf", V, W, H, iters, target=target, steps=(T, T), step_tol=delta)
+                rows.append((f"NeNMF <={T},<={T} delta {delta:g}", cn, us_n, counts, direct))
         for alg, c, us, counts, direct in rows:
             it = first_below(c, target)
             at = {k: e for k, e in c}
@@ -148,7 +157,7 @@ def main():
                 upto = counts[:it // 10] if it else counts
                 mean = f" mean sweeps per step H {np.mean([h for h, _ in upto]):.2f} W {np.mean([w for _, w in upto]):.2f} (last sample {counts[-1][0]:.2f} / {counts[-1][1]:.2f});"
             timed = f" (timed from the start: {direct:.1f} ms)" if direct is not None else ""
-            print(f"  {alg:12s} {us:8.1f} us/iteration;{mean} reaches it after {it} iterations = {it * us / 1e3 if it else float('nan'):.1f} ms{timed}; {pts}")
+            print(f"  {alg:28s} {us:8.1f} us/iteration;{mean} reaches it after {it} iterations = {it * us / 1e3 if it else float('nan'):.1f} ms{timed}; {pts}")
     na.finalize()
 
 
