@@ -294,6 +294,14 @@ NMFAMD_API int nmfamd_engine_geometry(const nmfamd_engine* e, nmfamd_geometry* o
 /* The same for a caller compiled against an older (shorter) or newer (longer) nmfamd_geometry: writes min(struct_size, sizeof(nmfamd_geometry)) bytes, never
  * past the caller's struct (the struct only ever grows at its end; round 3 added `one_pass`, round 5 the four counts behind it, round 6 three more).  Returns NMFAMD_INVALID_ARGUMENT for struct_size < 8. */
 NMFAMD_API int nmfamd_engine_geometry_sized(const nmfamd_engine* e, void* out, unsigned long struct_size);
+/* The geometry an engine created with these arguments would report on a device with num_cus compute units, a memory-side cache (AMD Infinity Cache) of
+ * memory_side_cache_bytes (0: none known) and free_bytes of free memory, WITHOUT a device: it runs the parameter checks and the planning step of engine creation --
+ * the step that fixes the kernel path and the order of every partial sum, from the shape, the parameters, these three numbers and the environment switches -- and
+ * allocates nothing (no HIP call; works in a process on a machine without a GPU).  params_sized / params_size, elem_bytes and row_blocks as for
+ * nmfamd_engine_create_v2; geometry_out / struct_size as for nmfamd_engine_geometry_sized.  kl_blocks_* and sparse_setup depend on an upload: they are those of a
+ * freshly created engine.  Where creation would refuse the arguments this returns the same status, with the reason in nmfamd_engine_last_error(NULL). */
+NMFAMD_API int nmfamd_plan_geometry(int m, int n, int r, int algorithm, const void* params_sized, unsigned long params_size, int elem_bytes, int row_blocks,
+                                    int num_cus, unsigned long long memory_side_cache_bytes, unsigned long long free_bytes, void* geometry_out, unsigned long struct_size);
 
 /* ---- column-sharded multi-GPU form of the multiplicative update ------------------------------
  * Rank g holds V(:, J_g), H(:, J_g) and a full replica of W.  Per iteration:

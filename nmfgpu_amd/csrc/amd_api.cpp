@@ -42,6 +42,46 @@ namespace {
 // why the last nmfamd_engine_create on this thread failed (the engine that knew is gone): nmfamd_engine_last_error(NULL)
 thread_local std::string g_create_error;
 
+// nmfamd_params or one of its sized successors (NULL: the defaults) -> the engine's parameters; false for a struct shorter than nmfamd_params
+bool sized_params(const void* params_sized, unsigned long params_size, AlgorithmParams* out) {
+	if (params_sized == nullptr) return true;
+	if (params_size < sizeof(nmfamd_params)) return false;
+	nmfamd_params_v6 v6;
+	std::memset(&v6, 0, sizeof(v6));
+	std::memcpy(&v6, params_sized, params_size < sizeof(v6) ? (size_t)params_size : sizeof(v6));
+	const nmfamd_params_v5& v5 = v6.v5;
+	const nmfamd_params_v4& v4 = v5.v4;
+	const nmfamd_params_v3& v3 = v4.v3;
+	const nmfamd_params_v2& v2 = v3.v2;
+	const nmfamd_params& b = v2.base;
+	AlgorithmParams& p = *out;
+	p.lambda = b.lambda; p.lambdaW = b.lambdaW; p.lambdaH = b.lambdaH; p.alphaW = b.alphaW; p.alphaH = b.alphaH; p.theta = b.theta; p.divergence = b.divergence; p.sparse_compute = b.sparse_compute; p.precision = b.precision; p.missing_values = b.missing_values; p.dense_compute = v2.dense_compute; p.beta_value = v3.beta; p.weighted = v4.weighted; p.mixed_precision = v5.mixed_precision; p.batch_size = v6.batch_size; p.forget_factor = v6.forget_factor;
+	return true;
+}
+
+// what nmfamd_engine_geometry reports of an engine, created or only planned
+template <typename T>
+void fill_geometry(const Engine<T>& g, nmfamd_geometry* out) {
+	out->m = g.m(); out->n = g.n(); out->r = g.r(); out->padded_rank = g.rp();
+	out->padded_m = g.mpad(); out->padded_n = g.npad();
+	out->slabs_h = g.slabs_h(); out->slabs_w = g.slabs_w(); out->exchange_count = g.exchange_count();
+	out->product_kernel = g.product_kernel(); out->resident_images = g.resident_images(); out->one_pass = g.one_pass_state();
+	out->kl_blocks_w = g.kl_blocks(true); out->kl_blocks_h = g.kl_blocks(false); out->gram_k_slices = g.gram_k_slices(); out->w_col_split = g.w_col_split() ? 1 : 0;
+	out->sparse_setup = g.sparse_mode() ? (g.sparse_setup_on_device() ? 1 : 0) : -1;
+	out->fused_launches = g.fused_launches(); out->gram_ride_slices_h = g.gram_ride_slices(false); out->gram_ride_slices_w = g.gram_ride_slices(true);
+}
+
+// check_parameters() + plan() of an engine that allocates nothing: no HIP call
+template <typename T>
+Status plan_geometry(int m, int n, int r, int algorithm, const AlgorithmParams& p, int row_blocks, const DeviceFacts& device, nmfamd_geometry* out) {
+	Engine<T> e(m, n, r, algorithm, p);
+	e.set_row_blocks(row_blocks);
+	Status st = e.check_parameters();
+	if (st == ST_OK) st = e.plan(device);
+	if (st == ST_OK) fill_geometry(e, out); else g_create_error = e.last_error();
+	return st;
+}
+
 template <typename Fn32, typename Fn64>
 int dispatch(nmfamd_engine* e, Fn32 f32, Fn64 f64) {
 	if (!e) return NMFAMD_INVALID_ARGUMENT;
@@ -168,21 +208,12 @@ int nmfamd_engine_create_blocks(int m, int n, int r, int algorithm, const nmfamd
 }
 
 int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* params_sized, unsigned long params_size, int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out) {
-	if (params_sized != nullptr && params_size < sizeof(nmfamd_params)) return NMFAMD_INVALID_ARGUMENT;
-	nmfamd_params_v6 v6;
-	std::memset(&v6, 0, sizeof(v6));
-	if (params_sized != nullptr) std::memcpy(&v6, params_sized, params_size < sizeof(v6) ? (size_t)params_size : sizeof(v6));
-	const nmfamd_params_v5& v5 = v6.v5;
-	const nmfamd_params_v4& v4 = v5.v4;
-	const nmfamd_params_v3& v3 = v4.v3;
-	const nmfamd_params_v2& v2 = v3.v2;
-	const nmfamd_params* params = params_sized != nullptr ? &v2.base : nullptr;
+	AlgorithmParams p;
+	if (!sized_params(params_sized, params_size, &p)) return NMFAMD_INVALID_ARGUMENT;
 	if (!out || (elem_bytes != 4 && elem_bytes != 8) || row_blocks < 1 || row_blocks > 64) return NMFAMD_INVALID_ARGUMENT;
 	*out = nullptr;
 	g_create_error.clear();
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
-	AlgorithmParams p;
-	if (params) { p.lambda = params->lambda; p.lambdaW = params->lambdaW; p.lambdaH = params->lambdaH; p.alphaW = params->alphaW; p.alphaH = params->alphaH; p.theta = params->theta; p.divergence = params->divergence; p.sparse_compute = params->sparse_compute; p.precision = params->precision; p.missing_values = params->missing_values; p.dense_compute = v2.dense_compute; p.beta_value = v3.beta; p.weighted = v4.weighted; p.mixed_precision = v5.mixed_precision; p.batch_size = v6.batch_size; p.forget_factor = v6.forget_factor; }
 	nmfamd_engine* e = new (std::nothrow) nmfamd_engine();
 	if (!e) return NMFAMD_NO_HOST_MEMORY;
 	e->elem_bytes = elem_bytes;
@@ -400,17 +431,26 @@ int nmfamd_engine_kernel_timing_read3(nmfamd_engine* e, double* total_ms, long* 
 
 int nmfamd_engine_geometry(const nmfamd_engine* e, nmfamd_geometry* out) {
 	if (!e || !out) return NMFAMD_INVALID_ARGUMENT;
-	auto fill = [&](const auto& g) {
-		out->m = g.m(); out->n = g.n(); out->r = g.r(); out->padded_rank = g.rp();
-		out->padded_m = g.mpad(); out->padded_n = g.npad();
-		out->slabs_h = g.slabs_h(); out->slabs_w = g.slabs_w(); out->exchange_count = g.exchange_count();
-		out->product_kernel = g.product_kernel(); out->resident_images = g.resident_images(); out->one_pass = g.one_pass_state();
-		out->kl_blocks_w = g.kl_blocks(true); out->kl_blocks_h = g.kl_blocks(false); out->gram_k_slices = g.gram_k_slices(); out->w_col_split = g.w_col_split() ? 1 : 0;
-		out->sparse_setup = g.sparse_mode() ? (g.sparse_setup_on_device() ? 1 : 0) : -1;
-		out->fused_launches = g.fused_launches(); out->gram_ride_slices_h = g.gram_ride_slices(false); out->gram_ride_slices_w = g.gram_ride_slices(true);
-	};
-	if (e->elem_bytes == 4) fill(*e->f); else fill(*e->d);
+	if (e->elem_bytes == 4) fill_geometry(*e->f, out); else fill_geometry(*e->d, out);
 	return NMFAMD_OK;
+}
+
+int nmfamd_plan_geometry(int m, int n, int r, int algorithm, const void* params_sized, unsigned long params_size, int elem_bytes, int row_blocks,
+                         int num_cus, unsigned long long memory_side_cache_bytes, unsigned long long free_bytes, void* geometry_out, unsigned long struct_size) {
+	AlgorithmParams p;
+	if (!sized_params(params_sized, params_size, &p)) return NMFAMD_INVALID_ARGUMENT;
+	if (!geometry_out || struct_size < 8 || (elem_bytes != 4 && elem_bytes != 8) || row_blocks < 1 || row_blocks > 64 || num_cus < 1) return NMFAMD_INVALID_ARGUMENT;
+	g_create_error.clear();
+	DeviceFacts device;
+	device.num_cus = num_cus; device.memory_side_cache_bytes = (size_t)memory_side_cache_bytes; device.free_bytes = (size_t)free_bytes;
+	nmfamd_geometry g;
+	std::memset(&g, 0, sizeof(g));
+	Status st;
+	try {
+		st = elem_bytes == 4 ? plan_geometry<float>(m, n, r, algorithm, p, row_blocks, device, &g) : plan_geometry<double>(m, n, r, algorithm, p, row_blocks, device, &g);
+	} catch (const std::bad_alloc&) { return NMFAMD_NO_HOST_MEMORY; }
+	if (st == ST_OK) std::memcpy(geometry_out, &g, struct_size < sizeof(g) ? (size_t)struct_size : sizeof(g));
+	return (int)st;
 }
 
 int nmfamd_engine_geometry_sized(const nmfamd_engine* e, void* out, unsigned long struct_size) {

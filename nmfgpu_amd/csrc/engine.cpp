@@ -89,10 +89,20 @@ template double resolve_frobenius_squared<double>(const std::vector<double>&, st
 // Size of the device's memory-side cache (AMD Infinity Cache): not in hipDeviceProp_t, so a table by architecture -- 256 MiB
 // on gfx942 / gfx950 in SPX mode (/opt/skills/guides/MI355X_MICROARCH.md, "Infinity Cache (L3) 256 MiB") -- which
 // NMFAMD_MALL_MB overrides (other parts, partitioned modes, several engines sharing the cache).  0 = unknown: no window.
-static size_t memory_side_cache_bytes(const hipDeviceProp_t& prop) {
-	if (const char* e = std::getenv("NMFAMD_MALL_MB")) { const long mb = std::atol(e); return mb > 0 ? (size_t)mb << 20 : 0; }
-	if (std::strncmp(prop.gcnArchName, "gfx942", 6) == 0 || std::strncmp(prop.gcnArchName, "gfx950", 6) == 0) return (size_t)256 << 20;
-	return 0;
+// The free memory is asked for here, once, whatever the plan: plan() looks at it on the split-operand path only, where the question used to be put -- before the
+// engine's first allocation there as well, so the answer is the same.  A device that does not answer counts as one with room.
+hipError_t device_facts(DeviceFacts* out) {
+	int dev = 0;
+	hipDeviceProp_t prop;
+	hipError_t e = hipGetDevice(&dev);
+	if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
+	if (e != hipSuccess) return e;
+	out->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+	out->memory_side_cache_bytes = (std::strncmp(prop.gcnArchName, "gfx942", 6) == 0 || std::strncmp(prop.gcnArchName, "gfx950", 6) == 0) ? (size_t)256 << 20 : 0;
+	if (const char* env = std::getenv("NMFAMD_MALL_MB")) { const long mb = std::atol(env); out->memory_side_cache_bytes = mb > 0 ? (size_t)mb << 20 : 0; }
+	size_t total_b = 0;
+	if (hipMemGetInfo(&out->free_bytes, &total_b) != hipSuccess) { (void)hipGetLastError(); out->free_bytes = std::numeric_limits<size_t>::max(); }
+	return hipSuccess;
 }
 
 template <typename T>
@@ -135,49 +145,31 @@ Engine<T>::~Engine() {
 #ifdef NMFAMD_DIAG_BUILD
 	if (bf16_) bf_stamps_dump();
 #endif
-	T* bufs[] = {V_, Vt_, Om_, Omt_, Wt_, H_, Ws_, Hs_, slabs_, numW_, Wold_, G_, G2_, HHt_, Qinv_, gram_part_, sumsq_part_, psN_, stage_};   // (psR_ lives behind psN_)
-	for (T* b : bufs) if (b) (void)hipFree(b);
-	if (inv_work_) (void)hipFree(inv_work_);
-	if (hals_counts_h_) (void)hipFree(hals_counts_h_);
-	if (hals_counts_w_) (void)hipFree(hals_counts_w_);
-	if (range_flag_) (void)hipFree(range_flag_);
-	{
-		void* sp[] = {csr_ptr_, csr_idx_, csc_ptr_, csc_idx_, csc_from_csr_, csr_val_, csc_val_, q_, q2_, t_vwh_, t_kl_, rowsum_part_, sW_, sH_, kl_scale_, csr_bptr_, csc_bptr_, kl_part_, kl_tpart_, msq_part_, beta_den_, beta_tpart_, online_A_, online_B_};
-		for (void* b : sp) if (b) (void)hipFree(b);
-	}
-	{ void* bb[] = {Vb_, Vtb_, Wtb_, Hb_, Wx3_, Hx3_, qx3_, gram_tri_part_, Gw_raw_, Gh_raw_, colsq_}; for (void* b : bb) if (b) (void)hipFree(b); }
 	if (f64_stamps_ != nullptr) {
 		std::vector<unsigned long long> h((size_t)4 * 4096 * 8);
 		if (hipMemcpy(h.data(), f64_stamps_, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost) == hipSuccess) {
 			if (FILE* f = std::fopen(tuning_env("NMFAMD_F64_STAMPS"), "wb")) { std::fwrite(h.data(), sizeof(unsigned long long), h.size(), f); std::fclose(f); }
 		}
-		(void)hipFree(f64_stamps_);
 	}
-	if (f32w_scale_) (void)hipFree(f32w_scale_);
-	{ void* fb[] = {f64_scale_, f64_partial_, f64_counters_, f64_items_h_, f64_items_w_}; for (void* b : fb) if (b) (void)hipFree(b); }
-	if (gramW_part_) (void)hipFree(gramW_part_);
-	if (wsq_part_) (void)hipFree(wsq_part_);
-	if (rowdot_part_) (void)hipFree(rowdot_part_);
-	if (tri_ride_counters_) (void)hipFree(tri_ride_counters_);
-	if (Gpart_) (void)hipFree(Gpart_);
-	if (gram_spread_counter_) (void)hipFree(gram_spread_counter_);
-	if (Graw64_) (void)hipFree(Graw64_);
-	if (gramH_part_) (void)hipFree(gramH_part_);
-	if (scale_) (void)hipFree(scale_);
-	{ void* ob[] = {op_part_, op_hfrag_, op_ctl_, op_slabs_, op_hh_part_, op_ps4_, op_H2_, op_stamps_}; for (void* b : ob) if (b) (void)hipFree(b); }
-	if (pin_abort_) (void)hipHostFree(pin_abort_);
 	if (err_event_) (void)hipEventDestroy(err_event_);
 	if (ev_fork_) (void)hipEventDestroy(ev_fork_);
 	if (ev_join_) (void)hipEventDestroy(ev_join_);
 	if (aux_) (void)hipStreamDestroy(aux_);
-	if (pin_psN_) (void)hipHostFree(pin_psN_);   // (pin_psR_ lives behind it)
-	if (pin_kl_) (void)hipHostFree(pin_kl_);
 	for (hipEvent_t e : ev_) (void)hipEventDestroy(e);
-}
+}      // (buffers_ frees the memory)
 
 template <typename T>
 Status Engine<T>::allocate() {
-	if (m_ <= 0 || n_ <= 0 || r_ <= 0 || alg_ < 0 || alg_ > ALG_NENMF) return ST_INVALID;
+	if (Status s = check_parameters()) return s;
+	DeviceFacts device;
+	HIPX(device_facts(&device));
+	if (Status s = plan(device)) return s;
+	return allocate_buffers();
+}
+
+template <typename T>
+Status Engine<T>::check_parameters() {
+	if (m_ <= 0|| n_ <= 0 || r_ <= 0 || alg_ < 0 || alg_ > ALG_NENMF) return ST_INVALID;
 	if (alg_ == ALG_HALS && !panel_sweep_hals_available(RP_, sizeof(T))) { last_error_ = "HALS: no sweep kernel for this padded rank (fp32: 64 ... 512, fp64: multiples of 64 up to 512)"; return ST_INVALID; }
 	if (alg_ == ALG_NENMF && !panel_steps_apg_available(RP_, sizeof(T))) { last_error_ = "NeNMF: no step kernel for this padded rank (supported ranks: 1 ... 128, in either precision)"; return ST_INVALID; }
 	if (const char* why = nenmf_steps_fault(prm_.steps_h, prm_.steps_w, false, alg_ == ALG_NENMF)) { last_error_ = why; return ST_INVALID; }
@@ -198,11 +190,14 @@ Status Engine<T>::allocate() {
 		beta_ = (double)(T)prm_.beta();
 		if (!std::isfinite(beta_)) { last_error_ = "dense divergence update: 'beta' out of the range of the engine's precision"; return ST_INVALID; }
 	}
-	int dev = 0;
-	HIPX(hipGetDevice(&dev));
-	hipDeviceProp_t prop;
-	HIPX(hipGetDeviceProperties(&prop, dev));
-	num_cus_ = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+	return ST_OK;
+}
+
+// Everything that decides which kernels run and in which order partial sums are added, from the shape, the parameters, the three device facts and the environment
+// switches: no HIP call, so nmfamd_plan_geometry (and the CPU suite through it) sees exactly what an engine on such a device would run.
+template <typename T>
+Status Engine<T>::plan(const DeviceFacts& device) {
+	num_cus_ = device.num_cus;
 
 	// both products run on the MFMA pipe: fp32 (kernels.hip) or fp64 (kernels_f64.hip), each with its own cut
 	const bool f64 = std::is_same<T, double>::value;
@@ -283,9 +278,9 @@ Status Engine<T>::allocate() {
 	// (ranks <= 32 stay on the fp32 MFMA kernel: with half its MFMA work it is HBM-bound already and needs no split image)
 	// ... except where one image in the memory-side cache pays more than the halved MFMA work (§3: 107 -> 100 us at config 2's shape)
 	// One resident image pays when it fits the memory-side (Infinity) cache and two do not: a window around the cache size,
-	// computed once (cache_window_) from the device (memory_side_cache_bytes)
+	// computed once from the device (DeviceFacts::memory_side_cache_bytes)
 	const size_t image_bytes = sizeof(T) * (size_t)pad128(m_) * (size_t)pad128(n_);
-	const size_t mall = memory_side_cache_bytes(prop);
+	const size_t mall = device.memory_side_cache_bytes;
 	const bool cache_window = mall > 0 && (double)image_bytes > 0.6 * (double)mall && (double)image_bytes < 1.12 * (double)mall && std::getenv("NMFAMD_ONE_IMAGE") == nullptr;
 	// (the opt-in one-pass iteration runs on the split-operand products whatever the rank)
 #ifdef NMFAMD_DIAG_BUILD
@@ -325,8 +320,6 @@ Status Engine<T>::allocate() {
 		// (10 000 x 5 000 scaled, r = 64): 148 MB two images 97 us / one 102; 185 MB 109 / 100; 207 MB 126 / 108; 246 MB
 		// 145 / 129; 266 MB 152 / 143; 328 MB 173 / 174; 1.6 GB 792 / 988.  Also one image when two (plus the staging
 		// image of the upload) do not fit in HBM.  NMFAMD_ONE_IMAGE = 1 / 0 forces the choice.
-		size_t free_b = 0, total_b = 0;
-		const size_t image_b = sizeof(T) * (size_t)pad128(m_) * (size_t)pad128(n_);
 		const char* force = std::getenv("NMFAMD_ONE_IMAGE");
 		// the one-pass iteration needs ONE image (16-row tiles) and nothing else
 		// (measurement build, NMFAMD_ONE_PASS=1: measured slower than the two-pass iteration, docs/HISTORY.md)
@@ -334,7 +327,7 @@ Status Engine<T>::allocate() {
 		if (one_pass_) one_image_ = true;
 		else if (force != nullptr) one_image_ = std::atoi(force) != 0;
 		else if (cache_window) one_image_ = true;
-		else if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && 3 * image_b + (image_b >> 3) > free_b) one_image_ = true;
+		else if (3 * image_bytes + (image_bytes >> 3) > device.free_bytes) one_image_ = true;
 		// V H^T of a narrow column shard (short reduction range: at most 20 K-steps per wave without K slices): ONE slab from 128 x 32 workgroups, two per x-tile and two to a
 		// CU (kernels_x3.hip, NBW = 1), instead of up to three K slices of 128 x 64 ones.  Per wave the 128 x 64 form is bound by its own MFMA issue (35 cycles each) while
 		// a third of the chip's SIMDs work; the narrow form puts a second wave on every SIMD (the operand split is done twice, so it pays only while the range is short).
@@ -361,162 +354,21 @@ Status Engine<T>::allocate() {
 	elemsV_ = mpad_ * npad_;     // tiled or not: every tile spans all columns
 	elemsVt_ = tiled_ ? (long)planH_.xtiles * strideVt_ : mpad_ * npad_;
 	slab_stride_ = (long)RP_ * std::max(mpad_, npad_);
-	const long slab_elems = slab_stride_ * std::max(std::max(planH_.splits, planW_.splits), std::max(std::max(betaHb_.slabs, betaWb_.slabs), std::max(betaHr_.slabs, betaWr_.slabs)));
-	const long panelW = (long)RP_ * mpad_, panelH = (long)RP_ * npad_, rr = (long)RP_ * RP_;
-
-	auto dalloc = [&](T** p, long elems) -> hipError_t {
-		hipError_t e = hipMalloc((void**)p, (size_t)elems * sizeof(T));
-		if (e != hipSuccess) return e;
-		return hipMemsetAsync(*p, 0, (size_t)elems * sizeof(T), stream_);
-	};
-	if (bf16_) {
-		HIPX(hipMalloc(&Vb_, 16 * (size_t)planW_.xtiles * ksW_ * 256));
-		HIPX(hipMalloc(&Vtb_, 16 * (size_t)planH_.xtiles * ksH_ * 256));
-		{
-			// (row-block sharded runs all-gather the fragments in place, world x blk_rows / 16 K-steps = mpad_ / 16 of them -- more than ksH_ whenever m is not a
-			//  multiple of 128 x world (ADVICE r5: config 4's 50 000 rows on 8 ranks are padded to 50 176); the K-steps behind ksH_ are never read by a product and stay zero)
-			const size_t ks_alloc = (size_t)std::max<long>(ksH_, mpad_ / 16);
-			HIPX(hipMalloc(&Wtb_, 16 * ks_alloc * (RP_ / 32) * 64));
-			if (ks_alloc > (size_t)ksH_) HIPX(hipMemsetAsync((char*)Wtb_ + 16 * (size_t)ksH_ * (RP_ / 32) * 64, 0, 16 * (ks_alloc - (size_t)ksH_) * (RP_ / 32) * 64, stream_));
-		}
-		HIPX(hipMalloc(&Hb_, 16 * (size_t)ksW_ * (RP_ / 32) * 64));
-	} else if (!sparse_) {
-		if (x3_) {
-			// + 1: the all-zero K-step that closes the image (written here once; the update kernels never touch it)
-			const size_t bw = 3 * 16 * (size_t)(ksH_ + 1) * (RP_ / 32) * 64, bh = 3 * 16 * (size_t)(ksW_ + 1) * (RP_ / 32) * 64;
-			HIPX(hipMalloc(&Wx3_, bw));
-			HIPX(hipMalloc(&Hx3_, bh));
-			HIPX(hipMemsetAsync(Wx3_, 0, bw, stream_));
-			HIPX(hipMemsetAsync(Hx3_, 0, bh, stream_));
-		}
-		HIPX(dalloc(&V_, elemsV_));
-		if (!one_image_) HIPX(dalloc(&Vt_, elemsVt_));
-	} else {
-		HIPX(dalloc(&t_vwh_, mpad_));
-		HIPX(dalloc(&t_kl_, mpad_));
-		HIPX(dalloc(&rowsum_part_, (std::max(mpad_, npad_) / 128) * RP_));
-		HIPX(dalloc(&sW_, RP_));
-		HIPX(dalloc(&sH_, RP_));
-		HIPX(dalloc(&kl_scale_, RP_));
-		HIPX(hipHostMalloc((void**)&pin_kl_, sizeof(T) * (2 * (size_t)m_ + 3 * (size_t)RP_)));
-		if (prm_.is_masked()) HIPX(dalloc(&msq_part_, (long)(MASKED_NORM_PARTS + 16) * RP_));      // (+ 16: launch_normalize_panel's compaction scratch)
-	}
-	if (beta_dense_) {
-		HIPX(dalloc(&t_vwh_, mpad_));
-		HIPX(dalloc(&t_kl_, mpad_));
-		// (minibatch: k_beta_update_rows leaves one vector of sums per BETA_ROWS_PER_WG rows, not per 128)
-		HIPX(dalloc(&rowsum_part_, (std::max(mpad_, npad_) / (minibatch_ ? BETA_ROWS_PER_WG : 128)) * RP_));
-		HIPX(dalloc(&sW_, RP_));
-		HIPX(dalloc(&sH_, RP_));
-		if (minibatch_) { HIPX(dalloc(&online_A_, (long)RP_ * mpad_)); HIPX(dalloc(&online_B_, (long)RP_ * mpad_)); }
-		HIPX(dalloc(&beta_tpart_, 2l * BETA_MAX_SLABS * mpad_));
-		if (beta_ != 1 || weighted_) HIPX(dalloc(&beta_den_, slab_elems));
-		if (weighted_) { HIPX(dalloc(&Om_, elemsV_)); HIPX(dalloc(&Omt_, elemsVt_)); }
-		HIPX(hipHostMalloc((void**)&pin_kl_, sizeof(T) * (2 * (size_t)m_ + 3 * (size_t)RP_)));
-	}
-	HIPX(dalloc(&Wt_, panelW));
-	HIPX(dalloc(&H_, panelH));
-	// wide fp32 panels: scratch for the split image of the r x r matrix the update kernel multiplies with (kernels_wide.hip)
-	if (std::is_same<T, float>::value && panel_update_wide_available(RP_) && std::getenv("NMFAMD_FORCE_VALU") == nullptr &&
-	    tuning_env("NMFAMD_WIDE_FP32_MFMA") == nullptr)
-	{
-		const size_t qb = 3 * 16 * (size_t)(RP_ / 16 + 1) * (RP_ / 32) * 64;
-		HIPX(hipMalloc(&qx3_, qb));
-		HIPX(hipMemsetAsync(qx3_, 0, qb, stream_));      // (the closing all-zero K-step: k_smooth_gram writes the others only)
-	}
-	HIPX(dalloc(&slabs_, slab_elems));
-	HIPX(dalloc(&numW_, panelW));
-	HIPX(dalloc(&G_, rr));
-	HIPX(dalloc(&G2_, rr));
-	HIPX(dalloc(&HHt_, rr));
-	HIPX(dalloc(&Qinv_, rr));
-	HIPX(dalloc(&gram_part_, rr * gram_parts_));
-	HIPX(dalloc(&sumsq_part_, ((long)std::max({panel_update_parts(RP_, sizeof(T), (int)mpad_), (int)(mpad_ / panel_update_rows(RP_, sizeof(T))),
-	                                           hals_family(alg_) ? family_parts((int)mpad_) : 0}) + 16) * RP_));
-	if (hals_family(alg_)) {
-		// the sweep (step) counts of the most recent H and W step (dynamic stopping, docs/HALS.md, docs/NENMF.md)
-		HIPX(hipMalloc((void**)&hals_counts_h_, sizeof(int) * (size_t)npad_));
-		HIPX(hipMemsetAsync(hals_counts_h_, 0, sizeof(int) * (size_t)npad_, stream_));
-		HIPX(hipMalloc((void**)&hals_counts_w_, sizeof(int) * (size_t)mpad_));
-		HIPX(hipMemsetAsync(hals_counts_w_, 0, sizeof(int) * (size_t)mpad_, stream_));
-	}
-	// the two error-term vectors share one allocation (and one pinned landing buffer): ONE device-to-host copy per error iteration
 	ps_stride_ = std::max<long>(npad_, RP_);
-	HIPX(dalloc(&psN_, ps_stride_ + RP_));
-	psR_ = psN_ + ps_stride_;
-	HIPX(dalloc(&stage_, std::max(mpad_, npad_) * RP_));
-	HIPX(hipMalloc((void**)&range_flag_, sizeof(int)));
-	if constexpr (std::is_same<T, float>::value) {
-		tri_ = bf16_ && tri_kernels_available(RP_) && (alg_ == ALG_MU || alg_ == ALG_NSNMF);
-		if (tri_) {
-			HIPX(hipMalloc((void**)&gram_tri_part_, sizeof(float) * (size_t)std::max<long>(gram_tri_partial_elems(num_cus_), (long)(TRI_PASSENGERS / 2) * 36 * 1024)));
-			HIPX(hipMalloc((void**)&tri_ride_counters_, 64));
-			HIPX(hipMemsetAsync(tri_ride_counters_, 0, 64, stream_));
-			HIPX(dalloc(&Gw_raw_, rr));
-			HIPX(dalloc(&Gh_raw_, rr));
-			HIPX(dalloc(&colsq_, (long)RP_ * colsq_stage_parts()));
-			tri_w_den_bf16_ = tuning_env("NMFAMD_TRI_FP32_DEN") == nullptr;
-		}
-	}
-	if (alg_ == ALG_NSNMF) {
-		HIPX(dalloc(&Ws_, panelW));                       // (tri_: only get_factors() materialises W S)
-		if (!tri_) HIPX(dalloc(&Hs_, panelH));
-	}
-	if (alg_ >= ALG_GDCLS && alg_ <= ALG_AHCLS) {
-		HIPX(dalloc(&Wold_, panelW));
-		HIPX(dalloc(&rowdot_part_, (long)ROW_DOT_GROUPS * RP_));
-		HIPX(hipMalloc((void**)&inv_work_, sizeof(double) * 2 * (size_t)r_ * r_));
-		if (tuning_env("NMFAMD_NO_OVERLAP") == nullptr) {
-			HIPX(hipStreamCreateWithFlags(&aux_, hipStreamNonBlocking));
-			HIPX(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-			HIPX(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-			overlap_inverse_ = true;
-		}
-	}
+	// wide fp32 panels: the update kernel multiplies with the split image of an r x r matrix (kernels_wide.hip)
+	wide_q_image_ = std::is_same<T, float>::value && panel_update_wide_available(RP_) && std::getenv("NMFAMD_FORCE_VALU") == nullptr && tuning_env("NMFAMD_WIDE_FP32_MFMA") == nullptr;
+	tri_ = bf16_ && tri_kernels_available(RP_) && (alg_ == ALG_MU || alg_ == ALG_NSNMF);
+	if (tri_) tri_w_den_bf16_ = tuning_env("NMFAMD_TRI_FP32_DEN") == nullptr;
+	overlap_inverse_ = alg_ >= ALG_GDCLS && alg_ <= ALG_AHCLS && tuning_env("NMFAMD_NO_OVERLAP") == nullptr;      // (the r x r inverse on a side stream)
 	gram_image_ = x3_ && fused_capable() && RP_ == 64 && std::getenv("NMFAMD_GRAM_PARTIALS") == nullptr;
 	one_pass_ = one_pass_ && x3_ && gram_image_ && one_image_ && img_th_ == 16;
-#ifdef NMFAMD_DIAG_BUILD
-	if (one_pass_) {
-		HIPX(hipMalloc(&op_part_, onepass_part_bytes()));
-		HIPX(hipMalloc(&op_hfrag_, onepass_hfrag_bytes()));
-		HIPX(hipMalloc((void**)&op_ctl_, 64));
-		HIPX(hipMalloc((void**)&op_slabs_, sizeof(float) * (size_t)ONEPASS_XCDS * RP_ * mpad_));
-		HIPX(hipMalloc((void**)&op_hh_part_, sizeof(float) * 4096 * (size_t)(ONEPASS_XCDS * ONEPASS_GROUP)));
-		HIPX(hipMalloc((void**)&op_ps4_, sizeof(float) * 4 * (size_t)npad_));
-		HIPX(dalloc(&op_H2_, panelH));
-		HIPX(hipMemsetAsync(op_ps4_, 0, sizeof(float) * 4 * (size_t)npad_, stream_));
-		HIPX(hipMemsetAsync(op_part_, 0, onepass_part_bytes(), stream_));
-		HIPX(hipMemsetAsync(op_hfrag_, 0, onepass_hfrag_bytes(), stream_));
-		HIPX(hipMemsetAsync(op_ctl_, 0, 64, stream_));
-		HIPX(hipMemsetAsync(op_slabs_, 0, sizeof(float) * (size_t)ONEPASS_XCDS * RP_ * mpad_, stream_));
-		HIPX(hipHostMalloc((void**)&pin_abort_, sizeof(unsigned)));
-		*pin_abort_ = 0;
-		op_seq_ = 0;
-		if (tuning_env("NMFAMD_ONEPASS_STAMPS") != nullptr) {
-			HIPX(hipMalloc((void**)&op_stamps_, sizeof(unsigned long long) * 16 * 8 * ONEPASS_XCDS * ONEPASS_GROUP));
-			HIPX(hipMemsetAsync(op_stamps_, 0, sizeof(unsigned long long) * 16 * 8 * ONEPASS_XCDS * ONEPASS_GROUP, stream_));
-		}
-	}
-#endif
-	if (fused_capable() || gram_from_update()) {
-		HIPX(hipMalloc((void**)&gramW_part_, sizeof(float) * 4096 * (size_t)(mpad_ / 64)));
-		HIPX(hipMalloc((void**)&Graw64_, sizeof(float) * 4096));      // the reduced, unscaled W^T W of normalize_w's one-launch form
-		HIPX(hipMalloc((void**)&gramH_part_, sizeof(float) * 4096 * (size_t)(npad_ / 64)));
-		HIPX(hipMalloc((void**)&scale_, sizeof(float) * 64));
-		HIPX(hipMalloc((void**)&Gpart_, sizeof(float) * 4096 * GRAM_KSPLIT_MAX));
-		HIPX(hipMemsetAsync(Gpart_, 0, sizeof(float) * 4096 * GRAM_KSPLIT_MAX, stream_));      // (spread form: a tile's absent pieces are never written)
-		// W^T W of a whole problem (one K slice): the ten tiles' K ranges dealt to all sixteen passengers (gram_image.h) -- with a tile each, ten of them were the
-		// last workgroups of config 2's W^T V launch (37 - 40 us against 33 - 36.5 for the product blocks, profiles/r05_update_tail.md).  NMFAMD_GRAM_SPREAD=0
-		// (measurement builds) restores that form.
-		gram_spread_ = gram_ksplit_ == 1 && !(tuning_env("NMFAMD_GRAM_SPREAD") != nullptr && std::atoi(tuning_env("NMFAMD_GRAM_SPREAD")) == 0);
-		HIPX(hipMalloc((void**)&gram_spread_counter_, 64));
-		HIPX(hipMemsetAsync(gram_spread_counter_, 0, 64, stream_));
-		HIPX(hipMalloc((void**)&wsq_part_, sizeof(float) * 64 * (size_t)(mpad_ / 32)));
-		HIPX(hipMemsetAsync(wsq_part_, 0, sizeof(float) * 64 * (size_t)(mpad_ / 32), stream_));
-	}
-	if (fused32w_capable()) {
-		HIPX(hipMalloc((void**)&f32w_scale_, sizeof(float) * (size_t)RP_));
-		HIPX(hipMemsetAsync(f32w_scale_, 0, sizeof(float) * (size_t)RP_, stream_));
+	op_stamps_wanted_ = one_pass_ && tuning_env("NMFAMD_ONEPASS_STAMPS") != nullptr;
+	// W^T W of a whole problem (one K slice): the ten tiles' K ranges dealt to all sixteen passengers (gram_image.h) -- with a tile each, ten of them were the
+	// last workgroups of config 2's W^T V launch (37 - 40 us against 33 - 36.5 for the product blocks, profiles/r05_update_tail.md).  NMFAMD_GRAM_SPREAD=0
+	// (measurement builds) restores that form.
+	if (fused_capable() || gram_from_update()) gram_spread_ = gram_ksplit_ == 1 && !(tuning_env("NMFAMD_GRAM_SPREAD") != nullptr && std::atoi(tuning_env("NMFAMD_GRAM_SPREAD")) == 0);
+	fused32w_planned_ = fused32w_capable();
+	if (fused32w_planned_) {
 		// The Gram slices as passengers of the product launch (gram_wide.h) where the product's first round of workgroups leaves CUs free for them and their chain --
 		// a slice's K-steps at ~0.75 us each under the product's memory stream (measured: 625 steps in one slice made a 330 us launch 460) -- stays inside the launch,
 		// or is shorter than the launch of their own it replaces (~10 us); otherwise k_gram_wide_x3.  Measured (profiles/r06_f32w_ride_ab.txt), 10 000 x 5 000:
@@ -537,7 +389,8 @@ Status Engine<T>::allocate() {
 		f32w_ride_h_ = ride(planHx_, m_);
 		f32w_ride_w_ = ride(planWx_, n_);
 	}
-	if (fused64_capable()) {
+	fused64_planned_ = fused64_capable();
+	if (fused64_planned_) {
 		// Gram passengers of the two product launches (kernels_f64.hip, gram_ride_f64): as many K slices per 64 x 64 super-block as the product's grid leaves CUs for,
 		// at most 16 (the level-1 finisher adds them one after the other), at least 4 (a grid that fills the chip: the passengers queue behind the product blocks)
 		const int nbk = RP_ / 64, nsuper = nbk * (nbk + 1) / 2;
@@ -548,25 +401,154 @@ Status Engine<T>::allocate() {
 		};
 		f64_slices_h_ = slices(planH_, m_);      // W^T W beside W^T V
 		f64_slices_w_ = slices(planW_, n_);      // H H^T beside V H^T
-		HIPX(hipMalloc((void**)&f64_scale_, sizeof(double) * (size_t)RP_));
-		HIPX(hipMalloc((void**)&f64_partial_, sizeof(double) * 4096 * (size_t)nsuper * (size_t)std::max(f64_slices_h_, f64_slices_w_)));
-		HIPX(hipMalloc((void**)&f64_counters_, sizeof(unsigned) * (size_t)(nsuper + 1)));
-		HIPX(hipMemsetAsync(f64_counters_, 0, sizeof(unsigned) * (size_t)(nsuper + 1), stream_));
-		if (tuning_env("NMFAMD_RIDE64_PID_ORDER") == nullptr) {
-			std::vector<int> items;
-			gram_ride_f64_items(planH_, RP_, f64_slices_h_, items);
-			HIPX(hipMalloc((void**)&f64_items_h_, sizeof(int) * items.size()));
-			HIPX(hipMemcpy(f64_items_h_, items.data(), sizeof(int) * items.size(), hipMemcpyHostToDevice));
-			gram_ride_f64_items(planW_, RP_, f64_slices_w_, items);
-			HIPX(hipMalloc((void**)&f64_items_w_, sizeof(int) * items.size()));
-			HIPX(hipMemcpy(f64_items_w_, items.data(), sizeof(int) * items.size(), hipMemcpyHostToDevice));
+		if (tuning_env("NMFAMD_RIDE64_PID_ORDER") == nullptr) {      // (the passengers' XCD-aware work tables: built here, uploaded by allocate_buffers)
+			gram_ride_f64_items(planH_, RP_, f64_slices_h_, f64_items_h_host_);
+			gram_ride_f64_items(planW_, RP_, f64_slices_w_, f64_items_w_host_);
 		}
-		if (tuning_env("NMFAMD_F64_STAMPS") != nullptr) {
-			HIPX(hipMalloc((void**)&f64_stamps_, sizeof(unsigned long long) * 4 * 4096 * 8));
-			HIPX(hipMemsetAsync(f64_stamps_, 0, sizeof(unsigned long long) * 4 * 4096 * 8, stream_));
+		f64_stamps_wanted_ = tuning_env("NMFAMD_F64_STAMPS") != nullptr;
+	}
+	return ST_OK;
+}
+
+// Memory, zero fills (on stream_, in this order), the side stream and the events for what plan() decided.
+template <typename T>
+Status Engine<T>::allocate_buffers() {
+	const long slab_elems = slab_stride_ * std::max(std::max(planH_.splits, planW_.splits), std::max(std::max(betaHb_.slabs, betaWb_.slabs), std::max(betaHr_.slabs, betaWr_.slabs)));
+	const long panelW = (long)RP_ * mpad_, panelH = (long)RP_ * npad_, rr = (long)RP_ * RP_;
+	auto dalloc = [&](T** p, long elems) { return buffers_.device(p, (size_t)elems * sizeof(T), true, stream_); };      // (zero-filled)
+	auto bytes = [&](auto** p, size_t count, bool zero = false) { return buffers_.device(p, count, zero, stream_); };
+	if (bf16_) {
+		HIPX(bytes(&Vb_, 16 * (size_t)planW_.xtiles * ksW_ * 256));
+		HIPX(bytes(&Vtb_, 16 * (size_t)planH_.xtiles * ksH_ * 256));
+		{
+			// (row-block sharded runs all-gather the fragments in place, world x blk_rows / 16 K-steps = mpad_ / 16 of them -- more than ksH_ whenever m is not a
+			//  multiple of 128 x world (ADVICE r5: config 4's 50 000 rows on 8 ranks are padded to 50 176); the K-steps behind ksH_ are never read by a product and stay zero)
+			const size_t ks_alloc = (size_t)std::max<long>(ksH_, mpad_ / 16);
+			HIPX(bytes(&Wtb_, 16 * ks_alloc * (RP_ / 32) * 64));
+			if (ks_alloc > (size_t)ksH_) HIPX(hipMemsetAsync((char*)Wtb_ + 16 * (size_t)ksH_ * (RP_ / 32) * 64, 0, 16 * (ks_alloc - (size_t)ksH_) * (RP_ / 32) * 64, stream_));
+		}
+		HIPX(bytes(&Hb_, 16 * (size_t)ksW_ * (RP_ / 32) * 64));
+	} else if (!sparse_) {
+		if (x3_) {
+			// + 1: the all-zero K-step that closes the image (written here once; the update kernels never touch it)
+			HIPX(bytes(&Wx3_, 3 * 16 * (size_t)(ksH_ + 1) * (RP_ / 32) * 64, true));
+			HIPX(bytes(&Hx3_, 3 * 16 * (size_t)(ksW_ + 1) * (RP_ / 32) * 64, true));
+		}
+		HIPX(dalloc(&V_, elemsV_));
+		if (!one_image_) HIPX(dalloc(&Vt_, elemsVt_));
+	} else {
+		HIPX(dalloc(&t_vwh_, mpad_));
+		HIPX(dalloc(&t_kl_, mpad_));
+		HIPX(dalloc(&rowsum_part_, (std::max(mpad_, npad_) / 128) * RP_));
+		HIPX(dalloc(&sW_, RP_));
+		HIPX(dalloc(&sH_, RP_));
+		HIPX(dalloc(&kl_scale_, RP_));
+		HIPX(buffers_.pinned(&pin_kl_, sizeof(T) * (2 * (size_t)m_ + 3 * (size_t)RP_)));
+		if (prm_.is_masked()) HIPX(dalloc(&msq_part_, (long)(MASKED_NORM_PARTS + 16) * RP_));      // (+ 16: launch_normalize_panel's compaction scratch)
+	}
+	if (beta_dense_) {
+		HIPX(dalloc(&t_vwh_, mpad_));
+		HIPX(dalloc(&t_kl_, mpad_));
+		// (minibatch: k_beta_update_rows leaves one vector of sums per BETA_ROWS_PER_WG rows, not per 128)
+		HIPX(dalloc(&rowsum_part_, (std::max(mpad_, npad_) / (minibatch_ ? BETA_ROWS_PER_WG : 128)) * RP_));
+		HIPX(dalloc(&sW_, RP_));
+		HIPX(dalloc(&sH_, RP_));
+		if (minibatch_) { HIPX(dalloc(&online_A_, (long)RP_ * mpad_)); HIPX(dalloc(&online_B_, (long)RP_ * mpad_)); }
+		HIPX(dalloc(&beta_tpart_, 2l * BETA_MAX_SLABS * mpad_));
+		if (beta_ != 1 || weighted_) HIPX(dalloc(&beta_den_, slab_elems));
+		if (weighted_) { HIPX(dalloc(&Om_, elemsV_)); HIPX(dalloc(&Omt_, elemsVt_)); }
+		HIPX(buffers_.pinned(&pin_kl_, sizeof(T) * (2 * (size_t)m_ + 3 * (size_t)RP_)));
+	}
+	HIPX(dalloc(&Wt_, panelW));
+	HIPX(dalloc(&H_, panelH));
+	// wide fp32 panels: scratch for the split image of the r x r matrix (zero: the closing all-zero K-step -- k_smooth_gram writes the others only)
+	if (wide_q_image_) HIPX(bytes(&qx3_, 3 * 16 * (size_t)(RP_ / 16 + 1) * (RP_ / 32) * 64, true));
+	HIPX(dalloc(&slabs_, slab_elems));
+	HIPX(dalloc(&numW_, panelW));
+	HIPX(dalloc(&G_, rr));
+	HIPX(dalloc(&G2_, rr));
+	HIPX(dalloc(&HHt_, rr));
+	HIPX(dalloc(&Qinv_, rr));
+	HIPX(dalloc(&gram_part_, rr * gram_parts_));
+	HIPX(dalloc(&sumsq_part_, ((long)std::max({panel_update_parts(RP_, sizeof(T), (int)mpad_), (int)(mpad_ / panel_update_rows(RP_, sizeof(T))),
+	                                           hals_family(alg_) ? family_parts((int)mpad_) : 0}) + 16) * RP_));
+	if (hals_family(alg_)) {
+		// the sweep (step) counts of the most recent H and W step (dynamic stopping, docs/HALS.md, docs/NENMF.md)
+		HIPX(bytes(&hals_counts_h_, sizeof(int) * (size_t)npad_, true));
+		HIPX(bytes(&hals_counts_w_, sizeof(int) * (size_t)mpad_, true));
+	}
+	// the two error-term vectors share one allocation (and one pinned landing buffer): ONE device-to-host copy per error iteration
+	HIPX(dalloc(&psN_, ps_stride_ + RP_));
+	psR_ = psN_ + ps_stride_;
+	HIPX(dalloc(&stage_, std::max(mpad_, npad_) * RP_));
+	HIPX(bytes(&range_flag_, sizeof(int)));
+	if (tri_) {
+		HIPX(bytes(&gram_tri_part_, sizeof(float) * (size_t)std::max<long>(gram_tri_partial_elems(num_cus_), (long)(TRI_PASSENGERS / 2) * 36 * 1024)));
+		HIPX(bytes(&tri_ride_counters_, 64, true));
+		HIPX(bytes(&Gw_raw_, sizeof(float) * (size_t)rr, true));
+		HIPX(bytes(&Gh_raw_, sizeof(float) * (size_t)rr, true));
+		HIPX(bytes(&colsq_, sizeof(float) * (size_t)RP_ * colsq_stage_parts(), true));
+	}
+	if (alg_ == ALG_NSNMF) {
+		HIPX(dalloc(&Ws_, panelW));                       // (tri_: only get_factors() materialises W S)
+		if (!tri_) HIPX(dalloc(&Hs_, panelH));
+	}
+	if (alg_ >= ALG_GDCLS && alg_ <= ALG_AHCLS) {
+		HIPX(dalloc(&Wold_, panelW));
+		HIPX(dalloc(&rowdot_part_, (long)ROW_DOT_GROUPS * RP_));
+		HIPX(bytes(&inv_work_, sizeof(double) * 2 * (size_t)r_ * r_));
+		if (overlap_inverse_) {
+			HIPX(hipStreamCreateWithFlags(&aux_, hipStreamNonBlocking));
+			HIPX(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
+			HIPX(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
 		}
 	}
-	HIPX(hipHostMalloc((void**)&pin_psN_, sizeof(T) * (size_t)(ps_stride_ + RP_)));
+#ifdef NMFAMD_DIAG_BUILD
+	if (one_pass_) {
+		HIPX(bytes(&op_part_, onepass_part_bytes()));
+		HIPX(bytes(&op_hfrag_, onepass_hfrag_bytes()));
+		HIPX(bytes(&op_ctl_, 64));
+		HIPX(bytes(&op_slabs_, sizeof(float) * (size_t)ONEPASS_XCDS * RP_ * mpad_));
+		HIPX(bytes(&op_hh_part_, sizeof(float) * 4096 * (size_t)(ONEPASS_XCDS * ONEPASS_GROUP)));
+		HIPX(bytes(&op_ps4_, sizeof(float) * 4 * (size_t)npad_));
+		HIPX(dalloc(&op_H2_, panelH));
+		HIPX(hipMemsetAsync(op_ps4_, 0, sizeof(float) * 4 * (size_t)npad_, stream_));
+		HIPX(hipMemsetAsync(op_part_, 0, onepass_part_bytes(), stream_));
+		HIPX(hipMemsetAsync(op_hfrag_, 0, onepass_hfrag_bytes(), stream_));
+		HIPX(hipMemsetAsync(op_ctl_, 0, 64, stream_));
+		HIPX(hipMemsetAsync(op_slabs_, 0, sizeof(float) * (size_t)ONEPASS_XCDS * RP_ * mpad_, stream_));
+		HIPX(buffers_.pinned(&pin_abort_, sizeof(unsigned)));
+		*pin_abort_ = 0;
+		op_seq_ = 0;
+		if (op_stamps_wanted_) HIPX(bytes(&op_stamps_, sizeof(unsigned long long) * 16 * 8 * ONEPASS_XCDS * ONEPASS_GROUP, true));
+	}
+#endif
+	if (fused_capable() || gram_from_update()) {
+		HIPX(bytes(&gramW_part_, sizeof(float) * 4096 * (size_t)(mpad_ / 64)));
+		HIPX(bytes(&Graw64_, sizeof(float) * 4096));      // the reduced, unscaled W^T W of normalize_w's one-launch form
+		HIPX(bytes(&gramH_part_, sizeof(float) * 4096 * (size_t)(npad_ / 64)));
+		HIPX(bytes(&scale_, sizeof(float) * 64));
+		HIPX(bytes(&Gpart_, sizeof(float) * 4096 * GRAM_KSPLIT_MAX, true));      // (spread form: a tile's absent pieces are never written)
+		HIPX(bytes(&gram_spread_counter_, 64, true));
+		HIPX(bytes(&wsq_part_, sizeof(float) * 64 * (size_t)(mpad_ / 32), true));
+	}
+	if (fused32w_planned_) HIPX(bytes(&f32w_scale_, sizeof(float) * (size_t)RP_, true));
+	if (fused64_planned_) {
+		const int nbk = RP_ / 64, nsuper = nbk * (nbk + 1) / 2;
+		HIPX(bytes(&f64_scale_, sizeof(double) * (size_t)RP_));
+		HIPX(bytes(&f64_partial_, sizeof(double) * 4096 * (size_t)nsuper * (size_t)std::max(f64_slices_h_, f64_slices_w_)));
+		HIPX(bytes(&f64_counters_, sizeof(unsigned) * (size_t)(nsuper + 1), true));
+		auto table = [&](int** dev, std::vector<int>& host) {      // (empty: NMFAMD_RIDE64_PID_ORDER, no work tables)
+			hipError_t e = host.empty() ? hipSuccess : bytes(dev, sizeof(int) * host.size());
+			if (e == hipSuccess && !host.empty()) e = hipMemcpy(*dev, host.data(), sizeof(int) * host.size(), hipMemcpyHostToDevice);
+			std::vector<int>().swap(host);
+			return e;
+		};
+		HIPX(table(&f64_items_h_, f64_items_h_host_));
+		HIPX(table(&f64_items_w_, f64_items_w_host_));
+		if (f64_stamps_wanted_) HIPX(bytes(&f64_stamps_, sizeof(unsigned long long) * 4 * 4096 * 8, true));
+	}
+	HIPX(buffers_.pinned(&pin_psN_, sizeof(T) * (size_t)(ps_stride_ + RP_)));
 	pin_psR_ = pin_psN_ + ps_stride_;
 	{
 		void* dp = nullptr;       // the device's view of the pinned buffer (fetch_error_terms writes it from a kernel)
@@ -649,13 +631,13 @@ Status Engine<T>::upload_dense(const T* V, long ld) {
 	T* Vcol = V_;
 	const bool staged = tiled_ || bf16_;
 	if (staged) {
-		HIPX(hipMalloc((void**)&Vcol, sizeof(T) * (size_t)(mpad_ * npad_)));
-		hipError_t e = hipMemsetAsync(Vcol, 0, sizeof(T) * (size_t)(mpad_ * npad_), stream_);
-		if (e != hipSuccess) { (void)hipFree(Vcol); return hip_fail(e, "hipMemsetAsync(staging)"); }
+		Vcol = nullptr;
+		hipError_t e = buffers_.device(&Vcol, sizeof(T) * (size_t)(mpad_ * npad_), true, stream_);
+		if (e != hipSuccess) { buffers_.release(Vcol); return hip_fail(e, "hipMalloc / hipMemsetAsync(staging)"); }
 	}
 	hipError_t e = hipMemcpy2DAsync(Vcol, mpad_ * sizeof(T), V, ld * sizeof(T), m_ * sizeof(T), n_, hipMemcpyHostToDevice, stream_);
 	Status st = e == hipSuccess ? finish_upload(Vcol) : hip_fail(e, "hipMemcpy2DAsync(V)");
-	if (staged) (void)hipFree(Vcol);
+	if (staged) buffers_.release(Vcol);
 	if (beta_dense_ && st == ST_OK) beta_uploaded_ = true;
 	return st;
 }
@@ -767,15 +749,15 @@ Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const
 	Status st = ST_OK;
 	do {
 		hipError_t e;
-		if ((e = hipMalloc((void**)&d_val, sizeof(T) * (size_t)std::max<long>(nnz, 1))) != hipSuccess ||
-		    (e = hipMalloc((void**)&d_a, sizeof(int) * (size_t)std::max<long>(na, 1))) != hipSuccess ||
-		    (e = hipMalloc((void**)&d_b, sizeof(int) * (size_t)std::max<long>(nnz, 1))) != hipSuccess) { st = hip_fail(e, "hipMalloc(sparse staging)"); break; }
+		if ((e = buffers_.device(&d_val, sizeof(T) * (size_t)std::max<long>(nnz, 1), false, stream_)) != hipSuccess ||
+		    (e = buffers_.device(&d_a, sizeof(int) * (size_t)std::max<long>(na, 1), false, stream_)) != hipSuccess ||
+		    (e = buffers_.device(&d_b, sizeof(int) * (size_t)std::max<long>(nnz, 1), false, stream_)) != hipSuccess) { st = hip_fail(e, "hipMalloc(sparse staging)"); break; }
 		if (nnz > 0) {
 			if ((e = hipMemcpyAsync(d_val, values, sizeof(T) * nnz, hipMemcpyHostToDevice, stream_)) != hipSuccess ||
 			    (e = hipMemcpyAsync(d_b, b, sizeof(int) * nnz, hipMemcpyHostToDevice, stream_)) != hipSuccess) { st = hip_fail(e, "hipMemcpyAsync(sparse)"); break; }
 		}
 		if (na > 0 && (e = hipMemcpyAsync(d_a, a, sizeof(int) * na, hipMemcpyHostToDevice, stream_)) != hipSuccess) { st = hip_fail(e, "hipMemcpyAsync(sparse ptr)"); break; }
-		if ((tiled_ || bf16_) && (e = hipMalloc((void**)&Vcol, sizeof(T) * (size_t)(mpad_ * npad_))) != hipSuccess) { Vcol = nullptr; st = hip_fail(e, "hipMalloc(staging)"); break; }
+		if ((tiled_ || bf16_) && (e = buffers_.device(&Vcol, sizeof(T) * (size_t)(mpad_ * npad_), false, stream_)) != hipSuccess) { st = hip_fail(e, "hipMalloc(staging)"); break; }
 		if (!(tiled_ || bf16_)) Vcol = V_;
 		if ((e = hipMemsetAsync(Vcol, 0, sizeof(T) * (size_t)(mpad_ * npad_), stream_)) != hipSuccess) { st = hip_fail(e, "hipMemsetAsync(V)"); break; }
 		// CSR: ptr = a (rowPtr), idx = b (columns); CSC: ptr = a (columnPtr), idx = b (rows); COO: idx = a (rows), idx2 = b (columns)
@@ -785,10 +767,8 @@ Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const
 		st = finish_upload(Vcol);
 		if (beta_dense_ && st == ST_OK) beta_uploaded_ = true;
 	} while (0);
-	if ((tiled_ || bf16_) && Vcol) (void)hipFree(Vcol);
-	if (d_val) (void)hipFree(d_val);
-	if (d_a) (void)hipFree(d_a);
-	if (d_b) (void)hipFree(d_b);
+	if (tiled_ || bf16_) buffers_.release(Vcol);
+	buffers_.release(d_val, d_a, d_b);
 	return st;
 }
 
@@ -806,48 +786,45 @@ Status Engine<T>::upload_sparse_device(int format, const T* values, const int* a
 	int *d_a = nullptr, *d_b = nullptr, *row = nullptr, *col = nullptr, *items = nullptr, *rowq = nullptr, *counts = nullptr, *small = nullptr;
 	T* d_vtv = nullptr;
 	double* d_colsum = nullptr;
-	std::vector<void*> owned;
-	auto alloc = [&](void** p, size_t bytes) -> hipError_t { hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16)); if (e == hipSuccess) owned.push_back(*p); else *p = nullptr; return e; };
-	auto disown = [&](void* p) { for (auto& q : owned) if (q == p) q = nullptr; };
-	struct Cleanup { std::vector<void*>& v; ~Cleanup() { for (void* p : v) if (p) (void)hipFree(p); } } cleanup{owned};
+	DeviceBuffers scratch;
+	auto alloc = [&](auto** p, size_t bytes) { return scratch.device(p, std::max<size_t>(bytes, 16), false, stream_); };
+	auto image = [&](auto** p, size_t bytes) { return buffers_.device(p, bytes, false, stream_); };      // (a part of the engine's CSR / CSC images)
 	auto need_host = [&]() { *fallback = true; return ST_OK; };
 
-	void** old[] = {(void**)&csr_ptr_, (void**)&csr_idx_, (void**)&csc_ptr_, (void**)&csc_idx_, (void**)&csc_from_csr_, (void**)&csr_val_, (void**)&csc_val_, (void**)&q_, (void**)&q2_};
-	for (void** o : old) { if (*o) (void)hipFree(*o); *o = nullptr; }
+	buffers_.release(csr_ptr_, csr_idx_, csc_ptr_, csc_idx_, csc_from_csr_, csr_val_, csc_val_, q_, q2_);
 	nnz_ = 0;
 
 	const size_t ni = sizeof(int) * (size_t)nnz, nv = sizeof(T) * (size_t)nnz;
-	HIPX(alloc((void**)&d_val, nv)); HIPX(alloc((void**)&d_a, sizeof(int) * (size_t)na)); HIPX(alloc((void**)&d_b, ni));
-	HIPX(alloc((void**)&row, ni)); HIPX(alloc((void**)&col, ni));
-	HIPX(alloc((void**)&counts, sizeof(int) * (size_t)segs)); HIPX(alloc((void**)&small, sizeof(int) * 4));
+	HIPX(alloc(&d_val, nv)); HIPX(alloc(&d_a, sizeof(int) * (size_t)na)); HIPX(alloc(&d_b, ni));
+	HIPX(alloc(&row, ni)); HIPX(alloc(&col, ni));
+	HIPX(alloc(&counts, sizeof(int) * (size_t)segs)); HIPX(alloc(&small, sizeof(int) * 4));
 	HIPX(hipMemcpyAsync(d_val, values, nv, hipMemcpyHostToDevice, stream_));
 	HIPX(hipMemcpyAsync(d_a, a, sizeof(int) * (size_t)na, hipMemcpyHostToDevice, stream_));
 	HIPX(hipMemcpyAsync(d_b, b, ni, hipMemcpyHostToDevice, stream_));
 	HIPX(hipMemsetAsync(small, 0, sizeof(int) * 4, stream_));
 	int* flags = small;                       // [0] flags, [1] longest row, [2] longest column
 	HIPX(launch_sp_expand(format, d_a, d_b, nnz, outer, base, m_, n_, row, col, flags, stream_));
-	HIPX(hipMalloc((void**)&csr_ptr_, sizeof(int) * (size_t)(m_ + 1)));
-	HIPX(hipMalloc((void**)&csc_ptr_, sizeof(int) * (size_t)(n_ + 1)));
+	HIPX(image(&csr_ptr_, sizeof(int) * (size_t)(m_ + 1)));
+	HIPX(image(&csc_ptr_, sizeof(int) * (size_t)(n_ + 1)));
 	HIPX(launch_sp_histogram_scan(row, nnz, m_, counts, csr_ptr_, small + 1, stream_));
 	int h_small[4] = {0, 0, 0, 0};
 	HIPX(hipMemcpyAsync(h_small, small, sizeof(int) * 4, hipMemcpyDeviceToHost, stream_));
 	HIPX(hipStreamSynchronize(stream_));
 	if ((h_small[0] & 3) != 0) return need_host();
-	(void)hipFree(d_a); disown(d_a); d_a = nullptr;
-	(void)hipFree(d_b); disown(d_b); d_b = nullptr;
+	scratch.release(d_a, d_b);
 
-	HIPX(alloc((void**)&items, ni));
+	HIPX(alloc(&items, ni));
 	if ((h_small[0] & 4) != 0) {
 		// not in (row, column) order (COO, CSC, an unsorted CSR): the entries' positions by row, every row by (column, position)
 		if (h_small[1] > sp_segment_sort_capacity()) return need_host();
-		HIPX(alloc((void**)&rowq, ni));
-		HIPX(hipMalloc((void**)&csr_idx_, ni)); HIPX(hipMalloc((void**)&csr_val_, nv));
+		HIPX(alloc(&rowq, ni));
+		HIPX(image(&csr_idx_, ni)); HIPX(image(&csr_val_, nv));
 		HIPX(launch_sp_scatter_sort(row, nnz, m_, csr_ptr_, counts, items, col, h_small[1], stream_));
 		HIPX(launch_sp_gather_csr<T>(items, row, col, d_val, nnz, csr_idx_, csr_val_, rowq, stream_));
 	} else {
 		// the input IS the CSR image (0-based by now): its buffers are adopted as they are
-		csr_idx_ = col; disown(col);
-		csr_val_ = d_val; disown(d_val); d_val = nullptr;
+		csr_idx_ = col; buffers_.adopt(scratch, col);
+		csr_val_ = d_val; buffers_.adopt(scratch, d_val); d_val = nullptr;
 		rowq = row;
 	}
 	HIPX(launch_sp_histogram_scan(csr_idx_, nnz, n_, counts, csc_ptr_, small + 2, stream_));
@@ -856,12 +833,12 @@ Status Engine<T>::upload_sparse_device(int format, const T* values, const int* a
 	if (h_small[2] > sp_segment_sort_capacity()) return need_host();
 	// the CSR positions by column, every column's list ascending = ascending row, duplicates in CSR order
 	HIPX(launch_sp_scatter_sort(csr_idx_, nnz, n_, csc_ptr_, counts, items, nullptr, h_small[2], stream_));
-	HIPX(hipMalloc((void**)&csc_idx_, ni)); HIPX(hipMalloc((void**)&csc_val_, nv));
+	HIPX(image(&csc_idx_, ni)); HIPX(image(&csc_val_, nv));
 	HIPX(launch_sp_gather_csc<T>(items, rowq, csr_val_, nnz, csc_idx_, csc_val_, stream_));
 	const bool two_pass = tuning_env("NMFAMD_KL_TWO_PASS") != nullptr;      // (round 1's two-pass KL step, a measurement switch: quotient buffers + the CSR -> CSC permutation)
-	if (two_pass) { csc_from_csr_ = items; disown(items); HIPX(hipMalloc((void**)&q_, nv)); HIPX(hipMalloc((void**)&q2_, nv)); }
+	if (two_pass) { csc_from_csr_ = items; buffers_.adopt(scratch, items); HIPX(image(&q_, nv)); HIPX(image(&q2_, nv)); }
 	// tr(V^T V) terms per column (accumulated in T like the trace kernel, in the image's order) and sum(V) for the KL divergence
-	HIPX(alloc((void**)&d_vtv, sizeof(T) * (size_t)n_)); HIPX(alloc((void**)&d_colsum, sizeof(double) * (size_t)n_));
+	HIPX(alloc(&d_vtv, sizeof(T) * (size_t)n_)); HIPX(alloc(&d_colsum, sizeof(double) * (size_t)n_));
 	HIPX(launch_sp_col_sumsq<T>(csc_ptr_, csc_val_, n_, d_vtv, d_colsum, stream_));
 	h_vtv_.assign(n_, T(0));
 	std::vector<double> colsum((size_t)n_);
@@ -1749,7 +1726,7 @@ bool Engine<T>::fused_capable() const {
 template <typename T>
 bool Engine<T>::fused32w_capable() const {
 	return std::is_same<T, float>::value && x3_ && tiled_ && !bf16_ && !sparse_ && (alg_ == ALG_MU || alg_ == ALG_NSNMF) && RP_ >= 128 && panel_update_wide_available(RP_) &&
-	       gram_wide_available(RP_) && qx3_ != nullptr &&
+	       gram_wide_available(RP_) && wide_q_image_ &&
 	       std::getenv("NMFAMD_FORCE_VALU") == nullptr && std::getenv("NMFAMD_NO_FUSED_MU") == nullptr;
 }
 
@@ -2131,7 +2108,7 @@ Status Engine<T>::begin_next_iteration() {
 
 template <typename T>
 Status Engine<T>::set_hals_penalties(double l1W, double l1H, double l2W, double l2H) {
-	// (prm_, not beta_dense_: allocate() calls this before it has looked at the divergence)
+	// (prm_, not beta_dense_: check_parameters() calls this before it has looked at the divergence)
 	if (const char* why = hals_penalties_fault(l1W, l1H, l2W, l2H, sizeof(T) == 4, prm_.takes_penalties(hals_family(alg_)))) { last_error_ = why; return ST_INVALID; }
 	// kept rounded to T, as the sweeps take them: a value that rounds to 0 in the engine's precision is 0 for the normalisation switch too, and the
 	// (T) casts where the sweeps are launched change nothing any more
@@ -2445,16 +2422,16 @@ Status Engine<T>::upload_triplets(std::vector<int>& rows, std::vector<int>& cols
 	}
 	std::sort(h_vtv_.begin(), h_vtv_.end());
 
-	void** old[] = {(void**)&csr_ptr_, (void**)&csr_idx_, (void**)&csc_ptr_, (void**)&csc_idx_, (void**)&csc_from_csr_, (void**)&csr_val_, (void**)&csc_val_, (void**)&q_, (void**)&q2_};
-	for (void** b : old) { if (*b) (void)hipFree(*b); *b = nullptr; }
+	buffers_.release(csr_ptr_, csr_idx_, csc_ptr_, csc_idx_, csc_from_csr_, csr_val_, csc_val_, q_, q2_);
+	auto image = [&](auto** p, size_t bytes) { return buffers_.device(p, bytes, false, stream_); };
 	const size_t ni = sizeof(int) * (size_t)std::max<long>(nnz, 1), nv = sizeof(T) * (size_t)std::max<long>(nnz, 1);
-	HIPX(hipMalloc((void**)&csr_ptr_, sizeof(int) * (m_ + 1)));
-	HIPX(hipMalloc((void**)&csc_ptr_, sizeof(int) * (n_ + 1)));
+	HIPX(image(&csr_ptr_, sizeof(int) * (m_ + 1)));
+	HIPX(image(&csc_ptr_, sizeof(int) * (n_ + 1)));
 	// (the quotient buffers and the CSR -> CSC permutation only serve round 1's two-pass KL step, a measurement switch)
 	const bool two_pass = tuning_env("NMFAMD_KL_TWO_PASS") != nullptr;
-	HIPX(hipMalloc((void**)&csr_idx_, ni)); HIPX(hipMalloc((void**)&csc_idx_, ni));
-	HIPX(hipMalloc((void**)&csr_val_, nv)); HIPX(hipMalloc((void**)&csc_val_, nv));
-	if (two_pass) { HIPX(hipMalloc((void**)&csc_from_csr_, ni)); HIPX(hipMalloc((void**)&q_, nv)); HIPX(hipMalloc((void**)&q2_, nv)); }
+	HIPX(image(&csr_idx_, ni)); HIPX(image(&csc_idx_, ni));
+	HIPX(image(&csr_val_, nv)); HIPX(image(&csc_val_, nv));
+	if (two_pass) { HIPX(image(&csc_from_csr_, ni)); HIPX(image(&q_, nv)); HIPX(image(&q2_, nv)); }
 	HIPX(hipMemcpyAsync(csr_ptr_, csr_ptr.data(), sizeof(int) * (m_ + 1), hipMemcpyHostToDevice, stream_));
 	HIPX(hipMemcpyAsync(csc_ptr_, csc_ptr.data(), sizeof(int) * (n_ + 1), hipMemcpyHostToDevice, stream_));
 	if (nnz > 0) {
@@ -2478,8 +2455,7 @@ Status Engine<T>::setup_kl_blocks() {
 	// 0 = no blocking) when the whole factor does not: W step gathers rows of H by column index (range n), H step rows of Wt by row index
 	// (range m).  A row's entries are sorted by that index, so its entries of block b are one range: only boundaries are needed.
 	{
-		void** oldb[] = {(void**)&csr_bptr_, (void**)&csc_bptr_, (void**)&kl_part_, (void**)&kl_tpart_};
-		for (void** b : oldb) { if (*b) (void)hipFree(*b); *b = nullptr; }
+		buffers_.release(csr_bptr_, csc_bptr_, kl_part_, kl_tpart_);
 		kl_blocks_w_ = kl_blocks_h_ = 1;
 		const char* be = std::getenv("NMFAMD_KL_BLOCK_KB");
 		const long block_bytes = be ? std::atol(be) * 1024 : 3584 * 1024;     // (measured at config 3: 2 MiB 1.73 ms / iteration, 3 MiB 1.62, 3.5 MiB 1.58, 4 MiB 1.57, 8 MiB 1.64; unblocked 2.14)
@@ -2500,7 +2476,7 @@ Status Engine<T>::setup_kl_blocks() {
 			kl_blocks_w_ = fit(kl_blocks_w_, mpad_); kl_blocks_h_ = fit(kl_blocks_h_, npad_);
 			auto boundaries = [&](const int* ptr, const int* idx, int rows, long range, int blocks, int** dev) -> hipError_t {
 				if (blocks <= 1) return hipSuccess;
-				hipError_t e = hipMalloc((void**)dev, sizeof(int) * (size_t)rows * (blocks + 1));
+				hipError_t e = buffers_.device(dev, sizeof(int) * (size_t)rows * (blocks + 1), false, stream_);
 				if (e != hipSuccess) return e;
 				return launch_sp_boundaries(ptr, idx, rows, range, blocks, *dev, stream_);      // (a row's indices ascend: block b of the row is one range)
 			};
@@ -2508,11 +2484,11 @@ Status Engine<T>::setup_kl_blocks() {
 			HIPX(boundaries(csc_ptr_, csc_idx_, n_, m_, kl_blocks_h_, &csc_bptr_));
 			const long pe = std::max<long>(kl_blocks_w_ > 1 ? (long)kl_blocks_w_ * RP_ * mpad_ : 0, kl_blocks_h_ > 1 ? (long)kl_blocks_h_ * RP_ * npad_ : 0);
 			// (no room for the partial panels after all: the unblocked gather needs none)
-			bool ok = pe == 0 || hipMalloc((void**)&kl_part_, sizeof(T) * (size_t)pe) == hipSuccess;
-			if (ok && kl_blocks_w_ > 1) ok = hipMalloc((void**)&kl_tpart_, sizeof(T) * 2 * (size_t)kl_blocks_w_ * mpad_) == hipSuccess;
+			bool ok = pe == 0 || buffers_.device(&kl_part_, sizeof(T) * (size_t)pe, false, stream_) == hipSuccess;
+			if (ok && kl_blocks_w_ > 1) ok = buffers_.device(&kl_tpart_, sizeof(T) * 2 * (size_t)kl_blocks_w_ * mpad_, false, stream_) == hipSuccess;
 			if (!ok) {
 				(void)hipGetLastError();
-				for (void** b : oldb) { if (*b) (void)hipFree(*b); *b = nullptr; }
+				buffers_.release(csr_bptr_, csc_bptr_, kl_part_, kl_tpart_);
 				kl_blocks_w_ = kl_blocks_h_ = 1;
 			}
 		}
@@ -2927,12 +2903,11 @@ Status Engine<T>::debug_read(int which, T* out, long count) {
 		if (count > avail) return ST_INVALID;
 		if (!tiled_) { src = img; break; }
 		T* tmp = nullptr;
-		HIPX(hipMalloc((void**)&tmp, sizeof(T) * (size_t)avail));
-		hipError_t e = hipMemsetAsync(tmp, 0, sizeof(T) * (size_t)avail, stream_);
+		hipError_t e = buffers_.device(&tmp, sizeof(T) * (size_t)avail, true, stream_);
 		if (e == hipSuccess) e = vt ? launch_tile<T>(img, npad_, n_, m_, tmp, strideVt_, planH_.th, true, stream_) : launch_tile<T>(img, mpad_, m_, n_, tmp, strideV_, img_th_, true, stream_);
 		if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, sizeof(T) * count, hipMemcpyDeviceToHost, stream_);
 		if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-		(void)hipFree(tmp);
+		buffers_.release(tmp);
 		return e == hipSuccess ? ST_OK : hip_fail(e, "debug_read(V)");
 	}
 	default: return ST_INVALID;

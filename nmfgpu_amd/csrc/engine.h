@@ -11,9 +11,19 @@
 #include <functional>
 #include <vector>
 
+#include "device_buffers.h"
 #include "kernels.h"
 
 namespace nmfamd {
+
+// What Engine::plan reads of the device -- and all it reads: the plan, and with it the kernel path and the order of every partial sum, is a function of the shape,
+// the parameters, these three numbers and the environment switches.  device_facts() gathers them from the current HIP device; nmfamd_plan_geometry takes them from its caller.
+struct DeviceFacts {
+	int num_cus = 256;
+	size_t memory_side_cache_bytes = 0;   // AMD Infinity Cache; 0 = unknown: no cache window
+	size_t free_bytes = 0;                // free device memory before the engine allocates anything
+};
+hipError_t device_facts(DeviceFacts* out);
 
 // ALG_HALS: coordinate descent (kernels_hals.hip, docs/HALS.md) -- the generic launch sequence only, single-engine runs only (no three-phase / sharded form)
 // ALG_NENMF: the HALS iteration with accelerated projected-gradient steps in place of the sweeps (kernels_nenmf.hip, docs/NENMF.md); HALS's limits
@@ -170,7 +180,12 @@ public:
 	Engine(int m, int n, int r, int algorithm, const AlgorithmParams& params);
 	~Engine();
 
+	// Creation in three steps: check_parameters() (the *_fault checks, prm_ rounded to T), plan() (every decision that fixes which kernels run and in which order
+	// partial sums are added; no HIP call) and allocate_buffers() (memory, zero fills, streams and events for what plan() decided).  allocate() runs all three with
+	// the facts of the current device; check_parameters() + plan() alone serve nmfamd_plan_geometry on a machine without one.
 	Status allocate();
+	Status check_parameters();
+	Status plan(const DeviceFacts& device);
 	// Row-block form of the sharded W step (sharded.cpp): the padded row count becomes a multiple of 128 * blocks, so that
 	// the Wt panel splits into `blocks` equal row blocks.  Call before allocate().
 	void set_row_blocks(int blocks) { row_blocks_ = blocks > 1 ? blocks : 1; }
@@ -263,10 +278,10 @@ public:
 	int gram_k_slices() const { return gram_spread_ ? GRAM_REDUCE_BLOCKS : gram_ksplit_; }      // (16: the spread form)
 	bool w_col_split() const { return w_col_split_; }
 	int fused_launches() const {
-		if ((fused_capable() && !one_pass_ && gram_image_) || (f64_partial_ != nullptr && fused64_capable())) return 4;
-		return f32w_scale_ != nullptr && fused32w_capable() ? 8 - (f32w_ride_h_ > 0 ? 1 : 0) - (f32w_ride_w_ > 0 ? 1 : 0) : 0;
+		if ((fused_capable() && !one_pass_ && gram_image_) || (fused64_planned_ && fused64_capable())) return 4;
+		return fused32w_planned_ && fused32w_capable() ? 8 - (f32w_ride_h_ > 0 ? 1 : 0) - (f32w_ride_w_ > 0 ? 1 : 0) : 0;
 	}
-	int gram_ride_slices(bool w_side) const { return f64_partial_ != nullptr ? (w_side ? f64_slices_w_ : f64_slices_h_) : (f32w_scale_ != nullptr ? (w_side ? f32w_ride_w_ : f32w_ride_h_) : 0); }
+	int gram_ride_slices(bool w_side) const { return fused64_planned_ ? (w_side ? f64_slices_w_ : f64_slices_h_) : (fused32w_planned_ ? (w_side ? f32w_ride_w_ : f32w_ride_h_) : 0); }
 	// Row-block form at padded rank 256 with bf16 operands (config 4): between two W updates the OTHER ranks read only the bf16 fragments of a rank's rows (the next
 	// W^T V's operand and the Gram matrix are made from them) -- so the all-gather carries the fragments w_normalize_rows() left for this rank's rows (RP / 2 four-byte
 	// words per row: 25.6 MB at config 4 instead of 51.2 MB of fp32 rows) and the fp32 rows of the other ranks stay STALE in w_panel() until somebody needs them
@@ -334,6 +349,12 @@ public:
 
 private:
 	Status hip_fail(hipError_t e, const char* what);
+	Status allocate_buffers();                       // third step of allocate(): a buffer exists if plan() set its flag; no decision of its own
+	DeviceBuffers buffers_;                          // every device and pinned allocation of the engine, creation and uploads alike: the typed members below are views
+	// set by plan(), read by allocate_buffers(): the fused fp64 / wide fp32 iteration is in use (f64_* / f32w_scale_ exist), qx3_ exists, the stamp buffers of the
+	// measurement builds exist; the passengers' work tables until they are uploaded
+	bool fused64_planned_ = false, fused32w_planned_ = false, wide_q_image_ = false, f64_stamps_wanted_ = false, op_stamps_wanted_ = false;
+	std::vector<int> f64_items_h_host_, f64_items_w_host_;
 	Status h_step_impl(bool compute_error);
 	// prepacked: the split (x3) image of F is already in Wx3_ / Hx3_ (emitted by the update kernel that wrote F)
 	Status product_h(const T* F, const GramReduceArgs* rg = nullptr, bool prepacked = false);   // slabs_ <- partials of F V   (r x n)
@@ -474,7 +495,7 @@ private:
 	double sum_w_ = 0;
 	// rank-64 MU fast path: W is kept unnormalised with a pending column scale (kernels_mu64.hip)
 	float *gramW_part_ = nullptr, *gramH_part_ = nullptr, *scale_ = nullptr, *Graw64_ = nullptr;
-	bool w_col_split_ = false;       // V H^T from 128 x 32 workgroups and one slab (narrow column shards, Engine::init)
+	bool w_col_split_ = false;       // V H^T from 128 x 32 workgroups and one slab (narrow column shards, Engine::plan)
 	bool gram_spread_ = false;       // ... or, one slice: the sixteen passengers share the ten tiles' K ranges (gram_image.h, spread form) and the last one finishes G_
 	unsigned* gram_spread_counter_ = nullptr;
 	int gram_ksplit_ = 1;            // K slices of the W^T W passengers (gram_image.h): > 1 for column shards narrower than config 2
@@ -493,7 +514,7 @@ private:
 	// it (normalise + smooth + bf16 fragments), Gram matrices of the smoothed panels from the unsmoothed ones (S G S)
 	bool tri_ = false;
 	unsigned* tri_ride_counters_ = nullptr;          // arrival counters of the Gram passengers (tri_gram_tile.h): zero between launches
-	bool tri_ride_w_ = false, tri_ride_h_ = false;   // the Gram matrix of W / of S H rides in the W^T V / V (S H)^T launch (Engine::init leaves TRI_PASSENGERS CUs free)
+	bool tri_ride_w_ = false, tri_ride_h_ = false;   // the Gram matrix of W / of S H rides in the W^T V / V (S H)^T launch (Engine::plan leaves TRI_PASSENGERS CUs free)
 	bool wtb_valid_ = false;         // Wtb_ holds the bf16 fragments of the current W as it lies in Wt_ (unsmoothed; without the pending column scale)
 	bool tri_scale_pending_ = false; // W = Wt_ diag(d), d(c) = 1 / sqrt(staged sums in colsq_): the column normalisation of the last W update has not been folded into the panel
 	bool tri_scale_from_gram_ = false; // ... and its sums of squares are still to come out of the next Gram reduction (tri_prepare_w), into colsq_

@@ -80,6 +80,40 @@ def _count(v) -> int:
     return int(v)
 
 
+def _param_values(lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence="frobenius", sparse_compute=False, precision="native",
+                  missing_values=False, dense_compute=False, beta=None, weighted=False, mixed_precision=False, batch_size=None, forget_factor=0.7) -> list:
+    """The sixteen doubles of nmfamd_params_v6, in its order, from the keyword arguments of Engine (and of plan_geometry)."""
+    if not batch_size:
+        batch_size, forget_factor = 0.0, 0.0
+    if beta is not None and divergence != "beta":
+        raise ValueError('beta needs divergence="beta"')
+    if divergence == "beta" and beta is None:
+        raise ValueError('divergence="beta" needs a beta')
+    return [lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0, "is": 2.0, "beta": 3.0}[divergence],
+            float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
+            float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted), float(mixed_precision), float(batch_size), float(forget_factor)]
+
+
+def _params_struct(v: list) -> _ParamsV6:
+    return _ParamsV6(_ParamsV5(_ParamsV4(_ParamsV3(_ParamsV2(_Params(*v[:10]), v[10]), v[11]), v[12]), v[13]), v[14], v[15])
+
+
+def plan_geometry(m: int, n: int, r: int, algorithm: str = "mu", dtype=np.float32, *, num_cus: int, memory_side_cache_bytes: int, free_bytes: int,
+                  row_blocks: int = 1, **params) -> dict:
+    """Engine(m, n, r, algorithm, dtype, row_blocks=row_blocks, **params).geometry() as it would be on a device with num_cus compute units, a memory-side cache of
+    memory_side_cache_bytes and free_bytes of free memory -- without a device (nmfamd_plan_geometry: the parameter checks and the planning step of engine creation,
+    no allocation).  params: the keyword arguments of Engine that travel in nmfamd_params (lam ... forget_factor).  Raises EngineError where creation would refuse."""
+    lib = library()
+    p = _params_struct(_param_values(**params))
+    g = _Geometry()
+    st = lib.nmfamd_plan_geometry(int(m), int(n), int(r), ALGORITHMS[algorithm], C.byref(p), C.c_ulong(C.sizeof(p)), np.dtype(dtype).itemsize, int(row_blocks),
+                                  int(num_cus), C.c_ulonglong(memory_side_cache_bytes), C.c_ulonglong(free_bytes), C.byref(g), C.c_ulong(C.sizeof(g)))
+    if st != 0:
+        lib.nmfamd_engine_last_error.restype = C.c_char_p
+        raise EngineError(st, "nmfamd_plan_geometry", (lib.nmfamd_engine_last_error(None) or b"").decode())
+    return {k: getattr(g, k) for k, _ in _Geometry._fields_}
+
+
 class Engine:
     """One factorisation resident on the current HIP device (see include/nmfgpu_amd.h)."""
 
@@ -125,17 +159,10 @@ class Engine:
 
         step_tolerance ("nenmf" only; in [0, 1), None = 0): per-column dynamic stopping of those steps, with steps_h / steps_w as maximum counts (docs/NENMF.md,
         "Dynamic stopping"); 0 keeps the static counts; see set_step_tolerance."""
-        if not batch_size:
-            batch_size, forget_factor = 0.0, 0.0
         self._bind(m, n, r, dtype)
-        if beta is not None and divergence != "beta":
-            raise ValueError('beta needs divergence="beta"')
-        if divergence == "beta" and beta is None:
-            raise ValueError('divergence="beta" needs a beta')
         self._ctor = dict(algorithm=algorithm, stream=stream, row_blocks=row_blocks,
-                          params=[lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0, "is": 2.0, "beta": 3.0}[divergence],
-                                  float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
-                                  float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted), float(mixed_precision), float(batch_size), float(forget_factor)],
+                          params=_param_values(lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, divergence, sparse_compute, precision, missing_values, dense_compute, beta,
+                                               weighted, mixed_precision, batch_size, forget_factor),
                           penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)], sweeps=[_count(sweeps_h), _count(sweeps_w)],
                           sweep_tolerance=float(sweep_tolerance), step_tolerance=None if step_tolerance is None else float(step_tolerance),
                           steps=None if steps_h is None and steps_w is None else [_count(8 if steps_h is None else steps_h), _count(8 if steps_w is None else steps_w)])
@@ -166,8 +193,7 @@ class Engine:
 
     def _create(self):
         c = self._ctor
-        p = _ParamsV6(_ParamsV5(_ParamsV4(_ParamsV3(_ParamsV2(_Params(*c["params"][:10]), c["params"][10]), c["params"][11]), c["params"][12]), c["params"][13]),
-                      c["params"][14], c["params"][15])
+        p = _params_struct(c["params"])
         h = C.c_void_p()
         # row_blocks > 1: the padded row count is a multiple of 128 * row_blocks (row-block form of the sharded W step)
         if not hasattr(self._lib, "nmfamd_engine_create_v2"):
