@@ -562,6 +562,45 @@ NMFAMD_API int nmfamd_op_beta_update_rows_f32(float* P, float* Aacc, float* Bacc
                                               int r, int out_pad, int out_valid, double beta, double l1, double l2, int online, double rho, int flush, float* sum_part);
 NMFAMD_API int nmfamd_op_beta_update_rows_f64(double* P, double* Aacc, double* Bacc, const double* num_part, const double* den_part, int slabs, const double* dsum, int RP,
                                               int r, int out_pad, int out_valid, double beta, double l1, double l2, int online, double rho, int flush, double* sum_part);
+/* The launches of the sparse path (kernels_sparse.hip), one each, on caller-built host arrays, for tests.  Panels are row-major [rows][RP]; a sparse image is
+ * ptr / idx / val with 0-based int32 indices ascending within a row, nnz stored entries, the indices referring to rows of the gathered panel (b_rows / p_rows of
+ * them).  eps is the epsilon of the type, as in the engine's KL iteration.  Output arrays are uploaded as the caller filled them and are not cleared before the
+ * launch: what a launch does not write comes back unchanged.  NMFAMD_INVALID_ARGUMENT for sizes that do not fit, ranges of ptr outside [0, nnz], an index
+ * outside the gathered panel, and wherever the launcher refuses (the gathers and the KL update run at RP 64, 128 and 256 only).
+ *
+ * kl_fused: out(row, :) = sum_p val[p] / (s .* A(row, :) . B(idx[p], :) + eps) * B(idx[p], :) over the row's entries (s = a_scale, NULL: ones); rows in
+ * [rows, rows_pad) of out are zeroed.  t_vwh / t_kl (both or neither): per row sum val * wh and sum val * log(val / (wh + eps)) over the entries with val > 0.
+ * blocks > 1: ptr is the [rows][blocks + 1] boundary array (entry b of a row: the first position whose index is >= b * ceil(b_rows / blocks)), out is
+ * [blocks][rows_pad][RP] and t_vwh / t_kl are [blocks][rows_pad]: one partial result per block. */
+NMFAMD_API int nmfamd_op_kl_fused_f32(const int* ptr, const int* idx, const float* val, long nnz, const float* A, const float* B, long b_rows, int RP, int rows,
+                                      int rows_pad, int blocks, const float* a_scale, float* out, float* t_vwh, float* t_kl);
+NMFAMD_API int nmfamd_op_kl_fused_f64(const int* ptr, const int* idx, const double* val, long nnz, const double* A, const double* B, long b_rows, int RP, int rows,
+                                      int rows_pad, int blocks, const double* a_scale, double* out, double* t_vwh, double* t_kl);
+/* kl_update: P(y, c) <- (P(y, c) * scale(c)) * (sum over the parts of num) / (den(c) + eps) on P [len_pad][RP] (scale NULL: ones); num holds `parts` panels
+ * part_stride values apart (a multiple of 4, >= len_pad * RP when parts > 1; what lies between two panels is not read).  sumsq_part / sum_part (each optional,
+ * [len_pad / 128][RP]): per 128 rows the sums of squares / the sums of the new values.  len_pad a multiple of 128. */
+NMFAMD_API int nmfamd_op_kl_update_f32(float* P, const float* num, int parts, long part_stride, const float* den, const float* scale, int RP, int len_pad,
+                                       float* sumsq_part, float* sum_part);
+NMFAMD_API int nmfamd_op_kl_update_f64(double* P, const double* num, int parts, long part_stride, const double* den, const double* scale, int RP, int len_pad,
+                                       double* sumsq_part, double* sum_part);
+/* kl_sums: sums(c) = sum over the parts of sum_part(., c), divided by sqrt(sum over the parts of sumsq_part(., c)) where sumsq_part is given and that sum is > 0;
+ * scale (optional): 1 / sqrt of that sum, 1 where it is 0.  sum_part, sumsq_part: [parts][RP]. */
+NMFAMD_API int nmfamd_op_kl_sums_f32(const float* sum_part, const float* sumsq_part, int parts, int RP, float* sums, float* scale);
+NMFAMD_API int nmfamd_op_kl_sums_f64(const double* sum_part, const double* sumsq_part, int parts, int RP, double* sums, double* scale);
+/* panel_rowsum: sums(c) = sum over y of P(y, c), P [len_pad][RP], len_pad a multiple of 128. */
+NMFAMD_API int nmfamd_op_panel_rowsum_f32(const float* P, int RP, int len_pad, float* sums);
+NMFAMD_API int nmfamd_op_panel_rowsum_f64(const double* P, int RP, int len_pad, double* sums);
+/* spmm_rows: out(row, :) = sum_p val[p] * P(idx[p], :) over the row's entries; rows in [rows, rows_pad) of out are zeroed. */
+NMFAMD_API int nmfamd_op_spmm_rows_f32(const int* ptr, const int* idx, const float* val, long nnz, const float* P, long p_rows, int RP, int rows, int rows_pad,
+                                       float* out);
+NMFAMD_API int nmfamd_op_spmm_rows_f64(const int* ptr, const int* idx, const double* val, long nnz, const double* P, long p_rows, int RP, int rows, int rows_pad,
+                                       double* out);
+/* sddmm_quotient: q[p] = val[p] / (A(row, :) . B(idx[p], :) + eps) for every stored entry (nnz values; A [rows][RP]); t_vwh / t_kl (both or neither, `rows`
+ * values): the per-row terms of kl_fused, the logarithm taken in double. */
+NMFAMD_API int nmfamd_op_sddmm_quotient_f32(const int* ptr, const int* idx, const float* val, long nnz, const float* A, const float* B, long b_rows, int RP, int rows,
+                                            float* q, float* t_vwh, float* t_kl);
+NMFAMD_API int nmfamd_op_sddmm_quotient_f64(const int* ptr, const int* idx, const double* val, long nnz, const double* A, const double* B, long b_rows, int RP, int rows,
+                                            double* q, double* t_vwh, double* t_kl);
 /* Test access to an engine's device intermediates in panel layout: which = 0 Wt, 1 H, 2 W^T W,
  * 3 H H^T, 4 slabs, 5 inverse, 6 V, 7 Vt; rank-256 fp32 engines also 8 W^T W as last reduced, 9 staged column sums of squares,
  * 10 / 11 the bf16 fragments of W / H as 4-byte words. */

@@ -1069,6 +1069,141 @@ int op_beta_update_rows(T* P, T* Aacc, T* Bacc, const T* num_part, const T* den_
 	if (sum_part && hipMemcpy(sum_part, dSum.p, sums, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
 	return NMFAMD_OK;
 }
+
+// Test entries of kernels_sparse.hip: one launch each on caller-built arrays, eps = epsilon of T as in Engine::iterate_kl.  The arguments are checked as far as the
+// buffer sizes and the indices go (a stored index outside the gathered panel would be read on the device); which padded ranks run is the launchers' decision.
+// Output arrays are uploaded as the caller filled them and are not cleared, so a test sees what a launch wrote and what it left alone.
+bool sparse_image_ok(const int* ptr, const int* idx, long nnz, int rows, int blocks, long range) {
+	// blocks == 1: ptr[rows + 1]; otherwise the (rows, blocks + 1) boundary array of k_sp_boundaries.  Every range inside [0, nnz], every index inside [0, range)
+	const int per_row = blocks > 1 ? blocks + 1 : 1;
+	const long count = blocks > 1 ? (long)rows * per_row : (long)rows + 1;
+	for (long i = 0; i < count; ++i)
+		if (ptr[i] < 0 || ptr[i] > nnz) return false;
+	for (int row = 0; row < rows; ++row)
+		for (int b = 0; b < (blocks > 1 ? blocks : 1); ++b)
+			if (ptr[(long)row * per_row + b] > ptr[(long)row * per_row + b + 1]) return false;
+	for (long p = 0; p < nnz; ++p)
+		if (idx[p] < 0 || idx[p] >= range) return false;
+	return true;
+}
+
+template <typename T>
+hipError_t upload(DevBuf& d, const T* src, size_t count) {
+	if (hipError_t e = d.alloc(sizeof(T) * count); e != hipSuccess) return e;
+	return count ? hipMemcpy(d.p, src, sizeof(T) * count, hipMemcpyHostToDevice) : hipSuccess;
+}
+
+inline int op_status(hipError_t launch) {
+	if (launch == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
+	return launch == hipSuccess && hipDeviceSynchronize() == hipSuccess ? NMFAMD_OK : NMFAMD_HIP_ERROR;
+}
+
+template <typename T>
+int op_kl_fused(const int* ptr, const int* idx, const T* val, long nnz, const T* A, const T* B, long b_rows, int RP, int rows, int rows_pad, int blocks, const T* a_scale,
+                T* out, T* t_vwh, T* t_kl) {
+	if (!ptr || !idx || !val || !A || !B || !out || (t_vwh == nullptr) != (t_kl == nullptr) || nnz < 0 || nnz > 0x7fffffffl || b_rows < 1 || RP < 64 || RP > 4096 ||
+	    RP % 64 != 0 || rows < 1 || rows > rows_pad || blocks < 1 || blocks > 64 || !sparse_image_ok(ptr, idx, nnz, rows, blocks, b_rows))
+		return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const size_t panel = (size_t)rows_pad * RP, np = blocks > 1 ? (size_t)rows * (blocks + 1) : (size_t)rows + 1, nt = (size_t)blocks * rows_pad;
+	DevBuf dPtr, dIdx, dVal, dA, dB, dS, dOut, dTv, dTk;
+	if (upload(dPtr, ptr, np) != hipSuccess || upload(dIdx, idx, (size_t)nnz) != hipSuccess || upload(dVal, val, (size_t)nnz) != hipSuccess || upload(dA, A, panel) != hipSuccess ||
+	    upload(dB, B, (size_t)b_rows * RP) != hipSuccess || upload(dOut, out, panel * blocks) != hipSuccess || (a_scale && upload(dS, a_scale, (size_t)RP) != hipSuccess) ||
+	    (t_vwh && (upload(dTv, t_vwh, nt) != hipSuccess || upload(dTk, t_kl, nt) != hipSuccess)))
+		return NMFAMD_NO_DEVICE_MEMORY;
+	const int st = op_status(launch_kl_fused<T>((const int*)dPtr.p, (const int*)dIdx.p, (const T*)dVal.p, (const T*)dA.p, (const T*)dB.p, RP, std::numeric_limits<T>::epsilon(),
+	                                            (T*)dOut.p, (T*)dTv.p, (T*)dTk.p, rows, rows_pad, nullptr, blocks, blocks > 1 ? (long)panel : 0, (const T*)dS.p));
+	if (st != NMFAMD_OK) return st;
+	if (hipMemcpy(out, dOut.p, sizeof(T) * panel * blocks, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (t_vwh && (hipMemcpy(t_vwh, dTv.p, sizeof(T) * nt, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(t_kl, dTk.p, sizeof(T) * nt, hipMemcpyDeviceToHost) != hipSuccess))
+		return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
+
+template <typename T>
+int op_kl_update(T* P, const T* num, int parts, long part_stride, const T* den, const T* scale, int RP, int len_pad, T* sumsq_part, T* sum_part) {
+	// num: `parts` panels of len_pad * RP values, part_stride values apart (what lies between them is uploaded too, and must not be read)
+	if (!P || !num || !den || RP < 4 || RP > 4096 || RP % 4 != 0 || len_pad < 128 || len_pad % 128 != 0 || parts < 1 || parts > 4096 || part_stride % 4 != 0 ||
+	    (parts > 1 && part_stride < (long)len_pad * RP) || part_stride < 0)
+		return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const size_t panel = (size_t)len_pad * RP, all_num = (size_t)(parts - 1) * (size_t)part_stride + panel, ns = (size_t)(len_pad / 128) * RP;
+	DevBuf dP, dNum, dDen, dSc, dSq, dSm;
+	if (upload(dP, P, panel) != hipSuccess || upload(dNum, num, all_num) != hipSuccess || upload(dDen, den, (size_t)RP) != hipSuccess ||
+	    (scale && upload(dSc, scale, (size_t)RP) != hipSuccess) || (sumsq_part && upload(dSq, sumsq_part, ns) != hipSuccess) || (sum_part && upload(dSm, sum_part, ns) != hipSuccess))
+		return NMFAMD_NO_DEVICE_MEMORY;
+	const int st = op_status(launch_kl_update<T>((T*)dP.p, (const T*)dNum.p, (const T*)dDen.p, RP, len_pad, std::numeric_limits<T>::epsilon(), (T*)dSq.p, nullptr, parts, part_stride,
+	                                             (T*)dSm.p, (const T*)dSc.p));
+	if (st != NMFAMD_OK) return st;
+	if (hipMemcpy(P, dP.p, sizeof(T) * panel, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (sumsq_part && hipMemcpy(sumsq_part, dSq.p, sizeof(T) * ns, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (sum_part && hipMemcpy(sum_part, dSm.p, sizeof(T) * ns, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
+
+template <typename T>
+int op_kl_sums(const T* sum_part, const T* sumsq_part, int parts, int RP, T* sums, T* scale) {
+	if (!sum_part || !sums || parts < 1 || RP < 16 || RP > 4096 || RP % 16 != 0) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const size_t np = (size_t)parts * RP;
+	DevBuf dA, dB, dS, dSc;
+	if (upload(dA, sum_part, np) != hipSuccess || (sumsq_part && upload(dB, sumsq_part, np) != hipSuccess) || upload(dS, sums, (size_t)RP) != hipSuccess ||
+	    (scale && upload(dSc, scale, (size_t)RP) != hipSuccess))
+		return NMFAMD_NO_DEVICE_MEMORY;
+	const int st = op_status(launch_kl_sums<T>((const T*)dA.p, (const T*)dB.p, parts, RP, (T*)dS.p, nullptr, (T*)dSc.p));
+	if (st != NMFAMD_OK) return st;
+	if (hipMemcpy(sums, dS.p, sizeof(T) * RP, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (scale && hipMemcpy(scale, dSc.p, sizeof(T) * RP, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
+
+template <typename T>
+int op_panel_rowsum(const T* P, int RP, int len_pad, T* sums) {
+	if (!P || !sums || RP < 1 || RP > 4096 || len_pad < 128 || len_pad % 128 != 0) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	DevBuf dP, dPart, dS;
+	if (upload(dP, P, (size_t)len_pad * RP) != hipSuccess || dPart.alloc(sizeof(T) * (size_t)(len_pad / 128) * RP) != hipSuccess || upload(dS, sums, (size_t)RP) != hipSuccess)
+		return NMFAMD_NO_DEVICE_MEMORY;
+	const int st = op_status(launch_panel_rowsum<T>((const T*)dP.p, RP, len_pad, (T*)dPart.p, (T*)dS.p, nullptr));
+	if (st != NMFAMD_OK) return st;
+	return hipMemcpy(sums, dS.p, sizeof(T) * RP, hipMemcpyDeviceToHost) == hipSuccess ? NMFAMD_OK : NMFAMD_HIP_ERROR;
+}
+
+template <typename T>
+int op_spmm_rows(const int* ptr, const int* idx, const T* val, long nnz, const T* P, long p_rows, int RP, int rows, int rows_pad, T* out) {
+	if (!ptr || !idx || !val || !P || !out || nnz < 0 || nnz > 0x7fffffffl || p_rows < 1 || RP < 64 || RP > 4096 || RP % 64 != 0 || rows < 1 || rows > rows_pad ||
+	    !sparse_image_ok(ptr, idx, nnz, rows, 1, p_rows))
+		return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const size_t panel = (size_t)rows_pad * RP;
+	DevBuf dPtr, dIdx, dVal, dP, dOut;
+	if (upload(dPtr, ptr, (size_t)rows + 1) != hipSuccess || upload(dIdx, idx, (size_t)nnz) != hipSuccess || upload(dVal, val, (size_t)nnz) != hipSuccess ||
+	    upload(dP, P, (size_t)p_rows * RP) != hipSuccess || upload(dOut, out, panel) != hipSuccess)
+		return NMFAMD_NO_DEVICE_MEMORY;
+	const int st = op_status(launch_spmm_rows<T>((const int*)dPtr.p, (const int*)dIdx.p, (const T*)dVal.p, (const T*)dP.p, RP, (T*)dOut.p, rows, rows_pad, nullptr));
+	if (st != NMFAMD_OK) return st;
+	return hipMemcpy(out, dOut.p, sizeof(T) * panel, hipMemcpyDeviceToHost) == hipSuccess ? NMFAMD_OK : NMFAMD_HIP_ERROR;
+}
+
+template <typename T>
+int op_sddmm_quotient(const int* ptr, const int* idx, const T* val, long nnz, const T* A, const T* B, long b_rows, int RP, int rows, T* q, T* t_vwh, T* t_kl) {
+	if (!ptr || !idx || !val || !A || !B || !q || (t_vwh == nullptr) != (t_kl == nullptr) || nnz < 0 || nnz > 0x7fffffffl || b_rows < 1 || RP < 64 || RP > 4096 ||
+	    RP % 64 != 0 || rows < 1 || !sparse_image_ok(ptr, idx, nnz, rows, 1, b_rows))
+		return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	DevBuf dPtr, dIdx, dVal, dA, dB, dQ, dTv, dTk;
+	if (upload(dPtr, ptr, (size_t)rows + 1) != hipSuccess || upload(dIdx, idx, (size_t)nnz) != hipSuccess || upload(dVal, val, (size_t)nnz) != hipSuccess ||
+	    upload(dA, A, (size_t)rows * RP) != hipSuccess || upload(dB, B, (size_t)b_rows * RP) != hipSuccess || upload(dQ, q, (size_t)nnz) != hipSuccess ||
+	    (t_vwh && (upload(dTv, t_vwh, (size_t)rows) != hipSuccess || upload(dTk, t_kl, (size_t)rows) != hipSuccess)))
+		return NMFAMD_NO_DEVICE_MEMORY;
+	const int st = op_status(launch_sddmm_quotient<T>((const int*)dPtr.p, (const int*)dIdx.p, (const T*)dVal.p, (const T*)dA.p, (const T*)dB.p, RP, std::numeric_limits<T>::epsilon(),
+	                                                  (T*)dQ.p, (T*)dTv.p, (T*)dTk.p, rows, nullptr));
+	if (st != NMFAMD_OK) return st;
+	if (nnz > 0 && hipMemcpy(q, dQ.p, sizeof(T) * (size_t)nnz, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (t_vwh && (hipMemcpy(t_vwh, dTv.p, sizeof(T) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess ||
+	              hipMemcpy(t_kl, dTk.p, sizeof(T) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess)) return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
 }
 
 extern "C" {
@@ -1196,6 +1331,56 @@ int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad
 
 int nmfamd_op_hals_normalize_f64(double* Wt, int RP, int mpad, double* H, int npad, const double* sumsq_part, int parts) {
 	return op_hals_normalize<double>(Wt, RP, mpad, H, npad, sumsq_part, parts);
+}
+
+int nmfamd_op_kl_fused_f32(const int* ptr, const int* idx, const float* val, long nnz, const float* A, const float* B, long b_rows, int RP, int rows, int rows_pad, int blocks,
+                           const float* a_scale, float* out, float* t_vwh, float* t_kl) {
+	return op_kl_fused<float>(ptr, idx, val, nnz, A, B, b_rows, RP, rows, rows_pad, blocks, a_scale, out, t_vwh, t_kl);
+}
+
+int nmfamd_op_kl_fused_f64(const int* ptr, const int* idx, const double* val, long nnz, const double* A, const double* B, long b_rows, int RP, int rows, int rows_pad, int blocks,
+                           const double* a_scale, double* out, double* t_vwh, double* t_kl) {
+	return op_kl_fused<double>(ptr, idx, val, nnz, A, B, b_rows, RP, rows, rows_pad, blocks, a_scale, out, t_vwh, t_kl);
+}
+
+int nmfamd_op_kl_update_f32(float* P, const float* num, int parts, long part_stride, const float* den, const float* scale, int RP, int len_pad, float* sumsq_part,
+                            float* sum_part) {
+	return op_kl_update<float>(P, num, parts, part_stride, den, scale, RP, len_pad, sumsq_part, sum_part);
+}
+
+int nmfamd_op_kl_update_f64(double* P, const double* num, int parts, long part_stride, const double* den, const double* scale, int RP, int len_pad, double* sumsq_part,
+                            double* sum_part) {
+	return op_kl_update<double>(P, num, parts, part_stride, den, scale, RP, len_pad, sumsq_part, sum_part);
+}
+
+int nmfamd_op_kl_sums_f32(const float* sum_part, const float* sumsq_part, int parts, int RP, float* sums, float* scale) {
+	return op_kl_sums<float>(sum_part, sumsq_part, parts, RP, sums, scale);
+}
+
+int nmfamd_op_kl_sums_f64(const double* sum_part, const double* sumsq_part, int parts, int RP, double* sums, double* scale) {
+	return op_kl_sums<double>(sum_part, sumsq_part, parts, RP, sums, scale);
+}
+
+int nmfamd_op_panel_rowsum_f32(const float* P, int RP, int len_pad, float* sums) { return op_panel_rowsum<float>(P, RP, len_pad, sums); }
+
+int nmfamd_op_panel_rowsum_f64(const double* P, int RP, int len_pad, double* sums) { return op_panel_rowsum<double>(P, RP, len_pad, sums); }
+
+int nmfamd_op_spmm_rows_f32(const int* ptr, const int* idx, const float* val, long nnz, const float* P, long p_rows, int RP, int rows, int rows_pad, float* out) {
+	return op_spmm_rows<float>(ptr, idx, val, nnz, P, p_rows, RP, rows, rows_pad, out);
+}
+
+int nmfamd_op_spmm_rows_f64(const int* ptr, const int* idx, const double* val, long nnz, const double* P, long p_rows, int RP, int rows, int rows_pad, double* out) {
+	return op_spmm_rows<double>(ptr, idx, val, nnz, P, p_rows, RP, rows, rows_pad, out);
+}
+
+int nmfamd_op_sddmm_quotient_f32(const int* ptr, const int* idx, const float* val, long nnz, const float* A, const float* B, long b_rows, int RP, int rows, float* q,
+                                 float* t_vwh, float* t_kl) {
+	return op_sddmm_quotient<float>(ptr, idx, val, nnz, A, B, b_rows, RP, rows, q, t_vwh, t_kl);
+}
+
+int nmfamd_op_sddmm_quotient_f64(const int* ptr, const int* idx, const double* val, long nnz, const double* A, const double* B, long b_rows, int RP, int rows, double* q,
+                                 double* t_vwh, double* t_kl) {
+	return op_sddmm_quotient<double>(ptr, idx, val, nnz, A, B, b_rows, RP, rows, q, t_vwh, t_kl);
 }
 
 } // extern "C"

@@ -11,6 +11,10 @@
 // One wave owns one output row ("wavefront-segmented" reduction: the 64 lanes hold the RP factor
 // rows of the running sum, the stored entries of the row are walked in index order), so every
 // sum has a fixed order and the result is deterministic.
+//
+// Every launcher of this file but launch_permute has a test entry that runs it once on caller-built arrays (nmfamd_op_kl_fused_*, _kl_update_*, _kl_sums_*,
+// _panel_rowsum_*, _spmm_rows_*, _sddmm_quotient_*: amd_api.cpp); tests/test_gpu_sparse_kl_ops.py compares each launch with the restatements of
+// tests/sparse_kl_reference.py, which are written from the formulas in the comments below.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -452,7 +456,9 @@ template hipError_t launch_kl_sums<double>(const double*, const double*, int, in
 
 template <typename T>
 hipError_t launch_kl_update(T* P, const T* num, const T* den, int RP, int len_pad, T eps, T* sumsq_part, hipStream_t stream, int parts, long part_stride, T* sum_part, const T* scale) {
-	if (RP % 64 != 0 || RP > 256 || parts < 1) return hipErrorInvalidValue;
+	// padded ranks 64, 128, 256, as in the gather launchers: k_kl_update's thread mapping needs RP / 4 to divide 256 (at 192 the last of its six thread groups
+	// would repeat the rows of the first, and the exchange would read five groups of six)
+	if ((RP != 64 && RP != 128 && RP != 256) || parts < 1) return hipErrorInvalidValue;
 	hipLaunchKernelGGL((k_kl_update<T>), dim3(len_pad / 128), dim3(256), 0, stream, P, num, den, RP, eps, sumsq_part, parts, part_stride, sum_part, scale);
 	return hipGetLastError();
 }

@@ -984,6 +984,154 @@ def op_hals_normalize(Wt: np.ndarray, H: np.ndarray, sumsq_part: np.ndarray):
     return {"Wt": Wt, "H": H}
 
 
+# The launches of the sparse path (kernels_sparse.hip), one each (nmfamd_op_kl_fused_* ... nmfamd_op_sddmm_quotient_*).  Every output array starts filled with `fill`
+# (NaN by default) and is NOT cleared on the device: what the launch did not write is still `fill` in the result.
+def _sparse_dtype(a: np.ndarray) -> np.dtype:
+    dt = np.dtype(a.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("float32 or float64")
+    return dt
+
+
+def _p(a):
+    return C.c_void_p(a.ctypes.data) if a is not None else None
+
+
+def _sparse_fn(name: str, dt: np.dtype):
+    return getattr(library(), f"nmfamd_op_{name}_{'f32' if dt == np.float32 else 'f64'}")
+
+
+def _sparse_image(ptr, idx, val, dt):
+    ptr = np.ascontiguousarray(ptr, dtype=np.int32); idx = np.ascontiguousarray(idx, dtype=np.int32); val = np.ascontiguousarray(val, dtype=dt)
+    if idx.ndim != 1 or idx.shape != val.shape:
+        raise ValueError("idx and val: one value per stored entry")
+    return ptr, idx, val
+
+
+def op_kl_fused(ptr: np.ndarray, idx: np.ndarray, val: np.ndarray, A: np.ndarray, B: np.ndarray, rows: int, rows_pad: int, blocks: int = 1,
+                a_scale: Optional[np.ndarray] = None, terms: bool = False, *, fill=np.nan):
+    """One launch of the fused KL gather (launch_kl_fused): A (>= rows_pad, RP) holds the output rows' own factor rows, B (b_rows, RP) the gathered panel, ptr / idx /
+    val the image (ptr: rows + 1 offsets; with blocks > 1 the (rows, blocks + 1) boundary array).  Returns a dict: `out` (blocks, rows_pad, RP) and, with terms,
+    `t_vwh`, `t_kl` (blocks, rows_pad) -- else None."""
+    dt = _sparse_dtype(val)
+    ptr, idx, val = _sparse_image(ptr, idx, val, dt)
+    A = np.ascontiguousarray(A, dtype=dt); B = np.ascontiguousarray(B, dtype=dt)
+    rows, rows_pad, blocks = int(rows), int(rows_pad), int(blocks)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1] or A.shape[0] < rows_pad:
+        raise ValueError("shapes: A (rows_pad, RP); B (b_rows, RP)")
+    if ptr.shape != ((rows, blocks + 1) if blocks > 1 else (rows + 1,)):
+        raise ValueError("ptr: rows + 1 offsets, or the (rows, blocks + 1) boundary array")
+    RP = A.shape[1]
+    if a_scale is not None:
+        a_scale = np.ascontiguousarray(a_scale, dtype=dt)
+        if a_scale.shape != (RP,):
+            raise ValueError("a_scale: RP values")
+    out = np.full((max(blocks, 1), rows_pad, RP), fill, dt)
+    tv = np.full((max(blocks, 1), rows_pad), fill, dt) if terms else None
+    tk = np.full((max(blocks, 1), rows_pad), fill, dt) if terms else None
+    st = _sparse_fn("kl_fused", dt)(_p(ptr), _p(idx), _p(val), C.c_long(len(val)), _p(A), _p(B), C.c_long(B.shape[0]), RP, rows, rows_pad, blocks, _p(a_scale), _p(out),
+                                    _p(tv), _p(tk))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_kl_fused")
+    return {"out": out, "t_vwh": tv, "t_kl": tk}
+
+
+def op_kl_update(P: np.ndarray, num_parts: np.ndarray, den: np.ndarray, scale: Optional[np.ndarray] = None, want_sumsq: bool = False, want_sum: bool = True,
+                 part_stride: Optional[int] = None, *, parts: Optional[int] = None, fill=np.nan):
+    """One launch of the KL update (launch_kl_update): P (len_pad, RP); num_parts either (parts, len_pad, RP) or, with part_stride, a flat array that holds `parts`
+    panels part_stride values apart (the gaps are uploaded with it); den, scale: RP values.  Returns a dict: `P` (a new array), `sumsq_part`, `sum_part`
+    ((len_pad // 128, RP), or None where not asked for)."""
+    dt = _sparse_dtype(P)
+    P = np.array(P, dtype=dt, order="C")
+    num = np.ascontiguousarray(num_parts, dtype=dt)
+    den = np.ascontiguousarray(den, dtype=dt)
+    if P.ndim != 2 or den.shape != (P.shape[1],):
+        raise ValueError("shapes: P (len_pad, RP); den RP values")
+    len_pad, RP = P.shape
+    if part_stride is None:
+        if num.ndim != 3 or num.shape[1:] != (len_pad, RP):
+            raise ValueError("num_parts: (parts, len_pad, RP), or a flat array with part_stride")
+        parts, part_stride = num.shape[0], len_pad * RP
+    else:
+        part_stride = int(part_stride)
+        if parts is None:
+            parts = 1 if part_stride == 0 else (num.size - len_pad * RP) // part_stride + 1
+        if num.ndim != 1 or parts < 1 or num.size < (parts - 1) * part_stride + len_pad * RP:
+            raise ValueError("num_parts: a flat array of (parts - 1) * part_stride + len_pad * RP values")
+    if scale is not None:
+        scale = np.ascontiguousarray(scale, dtype=dt)
+        if scale.shape != (RP,):
+            raise ValueError("scale: RP values")
+    sq = np.full((len_pad // 128, RP), fill, dt) if want_sumsq else None
+    sm = np.full((len_pad // 128, RP), fill, dt) if want_sum else None
+    st = _sparse_fn("kl_update", dt)(_p(P), _p(num), int(parts), C.c_long(part_stride), _p(den), _p(scale), RP, len_pad, _p(sq), _p(sm))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_kl_update")
+    return {"P": P, "sumsq_part": sq, "sum_part": sm}
+
+
+def op_kl_sums(sum_part: np.ndarray, sumsq_part: Optional[np.ndarray] = None, want_scale: bool = False, *, fill=np.nan):
+    """One launch of launch_kl_sums on (parts, RP) partial sums (and partial sums of squares).  Returns a dict: `sums` (RP) and `scale` (RP, or None)."""
+    dt = _sparse_dtype(sum_part)
+    sa = np.ascontiguousarray(sum_part, dtype=dt)
+    sb = np.ascontiguousarray(sumsq_part, dtype=dt) if sumsq_part is not None else None
+    if sa.ndim != 2 or (sb is not None and sb.shape != sa.shape):
+        raise ValueError("shapes: sum_part, sumsq_part (parts, RP)")
+    parts, RP = sa.shape
+    sums = np.full(RP, fill, dt)
+    scale = np.full(RP, fill, dt) if want_scale else None
+    st = _sparse_fn("kl_sums", dt)(_p(sa), _p(sb), parts, RP, _p(sums), _p(scale))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_kl_sums")
+    return {"sums": sums, "scale": scale}
+
+
+def op_panel_rowsum(P: np.ndarray, *, fill=np.nan) -> np.ndarray:
+    """One launch_panel_rowsum on P (len_pad, RP): the RP sums over the panel's rows."""
+    dt = _sparse_dtype(P)
+    P = np.ascontiguousarray(P, dtype=dt)
+    if P.ndim != 2:
+        raise ValueError("P: (len_pad, RP)")
+    sums = np.full(P.shape[1], fill, dt)
+    st = _sparse_fn("panel_rowsum", dt)(_p(P), P.shape[1], P.shape[0], _p(sums))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_panel_rowsum")
+    return sums
+
+
+def op_spmm_rows(ptr: np.ndarray, idx: np.ndarray, val: np.ndarray, P: np.ndarray, rows: int, rows_pad: int, *, fill=np.nan) -> np.ndarray:
+    """One launch_spmm_rows: out (rows_pad, RP) with out(row, :) = sum_p val[p] P(idx[p], :), P (p_rows, RP)."""
+    dt = _sparse_dtype(val)
+    ptr, idx, val = _sparse_image(ptr, idx, val, dt)
+    P = np.ascontiguousarray(P, dtype=dt)
+    rows, rows_pad = int(rows), int(rows_pad)
+    if P.ndim != 2 or ptr.shape != (rows + 1,):
+        raise ValueError("shapes: P (p_rows, RP); ptr rows + 1 offsets")
+    out = np.full((rows_pad, P.shape[1]), fill, dt)
+    st = _sparse_fn("spmm_rows", dt)(_p(ptr), _p(idx), _p(val), C.c_long(len(val)), _p(P), C.c_long(P.shape[0]), P.shape[1], rows, rows_pad, _p(out))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_spmm_rows")
+    return out
+
+
+def op_sddmm_quotient(ptr: np.ndarray, idx: np.ndarray, val: np.ndarray, A: np.ndarray, B: np.ndarray, rows: int, terms: bool = False, *, fill=np.nan):
+    """One launch_sddmm_quotient: q[p] = val[p] / (A(row, :) . B(idx[p], :) + eps) per stored entry.  Returns a dict: `q` (nnz) and, with terms, `t_vwh`, `t_kl`
+    (rows) -- else None."""
+    dt = _sparse_dtype(val)
+    ptr, idx, val = _sparse_image(ptr, idx, val, dt)
+    A = np.ascontiguousarray(A, dtype=dt); B = np.ascontiguousarray(B, dtype=dt)
+    rows = int(rows)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1] or A.shape[0] < rows or ptr.shape != (rows + 1,):
+        raise ValueError("shapes: A (>= rows, RP); B (b_rows, RP); ptr rows + 1 offsets")
+    q = np.full(len(val), fill, dt)
+    tv = np.full(rows, fill, dt) if terms else None
+    tk = np.full(rows, fill, dt) if terms else None
+    st = _sparse_fn("sddmm_quotient", dt)(_p(ptr), _p(idx), _p(val), C.c_long(len(val)), _p(A), _p(B), C.c_long(B.shape[0]), A.shape[1], rows, _p(q), _p(tv), _p(tk))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_sddmm_quotient")
+    return {"q": q, "t_vwh": tv, "t_kl": tk}
+
+
 def host_kmeans(data: np.ndarray, k: int, *, seed: int = 0, iterations: int = 100, threshold: float = 0.005):
     """The host-side Lloyd k-means behind computeKMeans and the KMeans*/EInNMF initialisers, without a
     device or context (nmfamd_host_kmeans_*).  Returns (clusters m x k, membership, passes)."""
