@@ -178,6 +178,38 @@ NMFAMD_API int nmfamd_engine_upload_sparse(nmfamd_engine* e, int format, const v
  * Replaces CopyStrategy (source/init/CopyStrategy.h:41-46) and storeFactorization. */
 NMFAMD_API int nmfamd_engine_set_factors(nmfamd_engine* e, const void* W, long ldw, const void* H, long ldh);
 NMFAMD_API int nmfamd_engine_get_factors(nmfamd_engine* e, void* W, long ldw, void* H, long ldh);
+
+/* ---- device-resident input and output (docs/DEVICE_IO.md) ------------------------------------
+ * The four entries above with DEVICE pointers: a matrix that already lies in HBM (computed by another library on the same GPU) goes into the engine, and the
+ * factors come out of it, without crossing to the host.  layout: NMFAMD_COLUMN_MAJOR (ld >= rows) or NMFAMD_ROW_MAJOR (ld >= columns); ld in elements.
+ * Pointer check, before any device work: the memory has to be device memory of the engine's device (hipPointerGetAttributes), aligned to the element, and the
+ * extent the call touches -- (outer - 1) * ld + inner elements -- has to lie inside its allocation (hipMemGetAddressRange).  A null pointer where one is needed,
+ * host or pinned host memory, managed memory, another device's memory, ld below the inner extent and a layout other than 0 / 1 return
+ * NMFAMD_INVALID_ARGUMENT with nmfamd_engine_last_error naming the argument and what is wrong; no kernel reads such a pointer.
+ * Ordering: each entry calls hipDeviceSynchronize() before its first access -- a matrix produced on ANY stream of the device is complete, and nobody still reads
+ * a destination -- and returns after the engine's stream is idle, so any stream may use the result.  Sources are never written. */
+enum { NMFAMD_COLUMN_MAJOR = 0, NMFAMD_ROW_MAJOR = 1 };
+/* Replaces nmfamd_engine_upload_dense for V (m x n) in device memory: a copy / transpose kernel writes the column-major staging image of the host upload and
+ * evaluates the value rule of a dense divergence engine in the same pass; everything behind that image is the host upload's code, so the resident images, the
+ * tr(V^T V) terms and every later result equal those of nmfamd_engine_upload_dense on the same values bit for bit.  Statuses and nmfamd_engine_last_error texts
+ * are the host entry's: NMFAMD_INVALID_ARGUMENT for a value that breaks the rule (the engine is then without a valid V), NMFAMD_VALUE_RANGE as there.
+ * Refused on an engine with sparse_compute or missing_values (its dense input becomes triplets on the host) and on a weighted engine. */
+NMFAMD_API int nmfamd_engine_upload_dense_device(nmfamd_engine* e, const void* V, long ld, int layout);
+/* Replaces nmfamd_engine_upload_dense_weighted: V and Omega (m x n each, layouts independent of each other) in device memory.  The joint value rule is evaluated
+ * on the device; with more than one kind of violation the one reported is: a bad weight, then a bad entry of V, then "at least one weight has to be > 0".  The
+ * resident images equal the host entry's bit for bit; the sum of the weights (rmsd's divisor) is added in double as one partial per 64 x 64 tile and then in tile
+ * order -- a function of the input and the shape only, within m n 2^-53 (relative) of the host entry's sum.  Refused on an engine that is not weighted. */
+NMFAMD_API int nmfamd_engine_upload_dense_weighted_device(nmfamd_engine* e, const void* V, long ldv, int layout_v, const void* Omega, long ldo, int layout_o);
+/* Replace nmfamd_engine_set_factors / _get_factors: W (m x r) and H (r x n) in device memory, each in its own layout; a null pointer leaves that factor (its ld and
+ * layout are then not looked at).  set invalidates what nmfamd_engine_set_factors invalidates and writes exact zeros into the panels' padding; get returns what
+ * nmfamd_engine_get_factors returns (nsNMF: W S) and writes the m x r / r x n block only -- bytes in the gap of ld stay as they are. */
+NMFAMD_API int nmfamd_engine_set_factors_device(nmfamd_engine* e, const void* W, long ldw, int layout_w, const void* H, long ldh, int layout_h);
+NMFAMD_API int nmfamd_engine_get_factors_device(nmfamd_engine* e, void* W, long ldw, int layout_w, void* H, long ldh, int layout_h);
+/* No kernel, no engine: what the pointer check sees.  kind: 0 not known to the runtime (ordinary host memory, NULL), 1 device memory, 2 pinned host memory,
+ * 3 anything else (managed, array); device: the HIP device it belongs to (-1 for kind 0); bytes_from_p: bytes from p to the end of its allocation (0 unless
+ * kind = 1; an allocator that carves tensors out of larger blocks reports the block's end).  NMFAMD_NO_DEVICE without a HIP device. */
+NMFAMD_API int nmfamd_device_pointer_info(const void* p, int* kind, int* device, unsigned long long* bytes_from_p);
+
 /* Uniform (0,1] fill, the same seed for both factors (source/init/RandomValueStrategy.cpp:29-70). */
 NMFAMD_API int nmfamd_engine_randomize(nmfamd_engine* e, unsigned seed, int w, int h);
 

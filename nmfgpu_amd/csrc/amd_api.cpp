@@ -341,6 +341,33 @@ int nmfamd_engine_get_factors(nmfamd_engine* e, void* W, long ldw, void* H, long
 	                   [&](Engine<double>& g) { return g.get_factors((double*)W, ldw, (double*)H, ldh); });
 }
 
+int nmfamd_engine_upload_dense_device(nmfamd_engine* e, const void* V, long ld, int layout) {
+	return dispatch(e, [&](Engine<float>& g) { return g.upload_dense_device((const float*)V, ld, layout); },
+	                   [&](Engine<double>& g) { return g.upload_dense_device((const double*)V, ld, layout); });
+}
+
+int nmfamd_engine_upload_dense_weighted_device(nmfamd_engine* e, const void* V, long ldv, int layout_v, const void* Omega, long ldo, int layout_o) {
+	return dispatch(e, [&](Engine<float>& g) { return g.upload_dense_weighted_device((const float*)V, ldv, layout_v, (const float*)Omega, ldo, layout_o); },
+	                   [&](Engine<double>& g) { return g.upload_dense_weighted_device((const double*)V, ldv, layout_v, (const double*)Omega, ldo, layout_o); });
+}
+
+int nmfamd_engine_set_factors_device(nmfamd_engine* e, const void* W, long ldw, int layout_w, const void* H, long ldh, int layout_h) {
+	return dispatch(e, [&](Engine<float>& g) { return g.set_factors_device((const float*)W, ldw, layout_w, (const float*)H, ldh, layout_h); },
+	                   [&](Engine<double>& g) { return g.set_factors_device((const double*)W, ldw, layout_w, (const double*)H, ldh, layout_h); });
+}
+
+int nmfamd_engine_get_factors_device(nmfamd_engine* e, void* W, long ldw, int layout_w, void* H, long ldh, int layout_h) {
+	return dispatch(e, [&](Engine<float>& g) { return g.get_factors_device((float*)W, ldw, layout_w, (float*)H, ldh, layout_h); },
+	                   [&](Engine<double>& g) { return g.get_factors_device((double*)W, ldw, layout_w, (double*)H, ldh, layout_h); });
+}
+
+int nmfamd_device_pointer_info(const void* p, int* kind, int* device, unsigned long long* bytes_from_p) {
+	if (!kind || !device || !bytes_from_p) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) { *kind = 0; *device = -1; *bytes_from_p = 0; return NMFAMD_NO_DEVICE; }
+	device_pointer_info(p, kind, device, bytes_from_p);
+	return NMFAMD_OK;
+}
+
 int nmfamd_engine_randomize(nmfamd_engine* e, unsigned seed, int w, int h) {
 	return dispatch(e, [&](Engine<float>& g) { return g.randomize_factors(seed, w != 0, h != 0); },
 	                   [&](Engine<double>& g) { return g.randomize_factors(seed, w != 0, h != 0); });

@@ -417,6 +417,7 @@ Status Engine<T>::allocate_buffers() {
 	const long panelW = (long)RP_ * mpad_, panelH = (long)RP_ * npad_, rr = (long)RP_ * RP_;
 	auto dalloc = [&](T** p, long elems) { return buffers_.device(p, (size_t)elems * sizeof(T), true, stream_); };      // (zero-filled)
 	auto bytes = [&](auto** p, size_t count, bool zero = false) { return buffers_.device(p, count, zero, stream_); };
+	HIPX(hipGetDevice(&device_));      // (the device entries compare a caller's pointer against it)
 	if (bf16_) {
 		HIPX(bytes(&Vb_, 16 * (size_t)planW_.xtiles * ksW_ * 256));
 		HIPX(bytes(&Vtb_, 16 * (size_t)planH_.xtiles * ksH_ * 256));
@@ -690,14 +691,166 @@ Status Engine<T>::beta_check_values(const T* values, long count, long ld, long r
 	for (long j = 0; j < count; ++j)
 		for (long i = 0; i < rows; ++i) {
 			const T v = values[(size_t)j * ld + i];
-			if (!std::isfinite(v) || v < T(0) || (is && v == T(0))) {
-				last_error_ = beta_ == 0   ? "Itakura-Saito divergence: every entry of V has to be finite and > 0"
-				              : beta_ == 1 ? "dense KL divergence: every entry of V has to be finite and >= 0"
-				              : is         ? "beta-divergence with beta <= 0: every entry of V has to be finite and > 0"
-				                           : "beta-divergence with beta > 0: every entry of V has to be finite and >= 0";
-				return ST_INVALID;
-			}
+			if (!std::isfinite(v) || v < T(0) || (is && v == T(0))) { last_error_ = beta_value_fault(); return ST_INVALID; }
 		}
+	return ST_OK;
+}
+
+template <typename T>
+const char* Engine<T>::beta_value_fault() const {
+	return beta_ == 0   ? "Itakura-Saito divergence: every entry of V has to be finite and > 0"
+	       : beta_ == 1 ? "dense KL divergence: every entry of V has to be finite and >= 0"
+	       : beta_ <= 0 ? "beta-divergence with beta <= 0: every entry of V has to be finite and > 0"
+	                    : "beta-divergence with beta > 0: every entry of V has to be finite and >= 0";
+}
+
+// ---- device-resident input and output (docs/DEVICE_IO.md) ---------------------------------------
+
+void device_pointer_info(const void* p, int* kind, int* device, unsigned long long* bytes_from_p) {
+	*kind = 0; *device = -1; *bytes_from_p = 0;
+	if (p == nullptr) return;
+	hipPointerAttribute_t attr;
+	std::memset(&attr, 0, sizeof(attr));
+	if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return; }      // (older runtimes answer an ordinary host pointer with an error)
+	if (attr.type == hipMemoryTypeUnregistered) return;
+	*device = attr.device;
+	if (attr.type == hipMemoryTypeHost) { *kind = 2; return; }
+	if (attr.type != hipMemoryTypeDevice || attr.isManaged) { *kind = 3; return; }
+	*kind = 1;
+	hipDeviceptr_t base = nullptr; size_t size = 0;
+	if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return; }
+	const uintptr_t b = (uintptr_t)base, q = (uintptr_t)p;
+	if (q >= b && q - b < size) *bytes_from_p = (unsigned long long)(size - (q - b));
+}
+
+template <typename T>
+Status Engine<T>::check_device_matrix(const char* name, const void* p, long ld, int layout, long rows, long cols) {
+	const std::string n(name);
+	if (p == nullptr) return refuse(n + ": null pointer");
+	if (layout != 0 && layout != 1) return refuse(n + ": layout has to be 0 (column-major) or 1 (row-major)");
+	const long inner = layout == 0 ? rows : cols, outer = layout == 0 ? cols : rows;
+	if (ld < inner) return refuse(n + ": leading dimension below the " + (layout == 0 ? "row count (column-major)" : "column count (row-major)"));
+	if ((uintptr_t)p % sizeof(T) != 0) return refuse(n + ": pointer not aligned to the element size");
+	int kind = 0, dev = -1; unsigned long long avail = 0;
+	device_pointer_info(p, &kind, &dev, &avail);
+	if (kind == 0) return refuse(n + ": not device memory (a pointer the HIP runtime does not know: host memory goes through the host entry)");
+	if (kind == 2) return refuse(n + ": not device memory (pinned host memory goes through the host entry)");
+	if (kind != 1) return refuse(n + ": not device memory (managed or array memory is not taken)");
+	if (dev != device_) return refuse(n + ": memory of another device than the engine's");
+	const unsigned long long need = ((unsigned long long)(outer - 1) * (unsigned long long)ld + (unsigned long long)inner) * sizeof(T);
+	if (outer > 0 && need > avail) return refuse(n + ": the extent (outer - 1) * ld + inner reaches past the end of the allocation");
+	return ST_OK;
+}
+
+template <typename T>
+Status Engine<T>::upload_dense_device(const T* V, long ld, int layout) {
+	if (weighted_) { last_error_ = "weighted NMF: V is uploaded together with its weights (upload_dense_weighted)"; return ST_INVALID; }
+	if (sparse_) { last_error_ = "device upload: an engine with 'sparseCompute' or 'missingValues' builds its triplets on the host and takes dense input from host memory only"; return ST_INVALID; }
+	if (Status st = check_device_matrix("V", V, ld, layout, m_, n_)) return st;
+	if (beta_dense_) beta_uploaded_ = false;
+	HIPX(hipDeviceSynchronize());      // whatever stream produced V has finished
+	T* Vcol = V_;
+	const bool staged = tiled_ || bf16_;
+	if (staged) {
+		Vcol = nullptr;
+		hipError_t e = buffers_.device(&Vcol, sizeof(T) * (size_t)(mpad_ * npad_), false, stream_);      // (the import writes every element of the image)
+		if (e != hipSuccess) { buffers_.release(Vcol); return hip_fail(e, "hipMalloc(staging)"); }
+	}
+	const int rule = beta_dense_ ? (beta_ <= 0 ? 2 : 1) : 0;
+	int flags = 0;
+	hipError_t e = hipSuccess;
+	if (rule != 0) e = hipMemsetAsync(range_flag_, 0, sizeof(int), stream_);
+	if (e == hipSuccess) e = launch_import_dense<T>(V, ld, layout, m_, n_, Vcol, mpad_, mpad_, npad_, rule, range_flag_, stream_);
+	if (e == hipSuccess && rule != 0) {
+		e = hipMemcpyAsync(&flags, range_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_);
+		if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+	}
+	Status st = ST_OK;
+	if (e != hipSuccess) st = hip_fail(e, "launch_import_dense(V)");
+	else if (flags & IMPORT_BAD_VALUE) { last_error_ = beta_value_fault(); st = ST_INVALID; }
+	else st = finish_upload(Vcol);
+	if (staged) buffers_.release(Vcol);
+	if (beta_dense_ && st == ST_OK) beta_uploaded_ = true;
+	return st;
+}
+
+template <typename T>
+Status Engine<T>::upload_dense_weighted_device(const T* V, long ldv, int layout_v, const T* Omega, long ldo, int layout_o) {
+	if (!weighted_) { last_error_ = "weighted upload: the engine was not created with 'weighted' = 1"; return ST_INVALID; }
+	if (Status st = check_device_matrix("V", V, ldv, layout_v, m_, n_)) return st;
+	if (Status st = check_device_matrix("Omega", Omega, ldo, layout_o, m_, n_)) return st;
+	beta_uploaded_ = false;
+	HIPX(hipDeviceSynchronize());
+	const bool is = beta_ <= 0;
+	const long parts = import_weighted_parts(mpad_, npad_);
+	double* part = nullptr;
+	hipError_t e = buffers_.device(&part, sizeof(double) * (size_t)parts, false, stream_);
+	if (e != hipSuccess) { buffers_.release(part); return hip_fail(e, "hipMalloc(weight sums)"); }
+	std::vector<double> h_part((size_t)parts);
+	int flags = 0;
+	e = hipMemsetAsync(range_flag_, 0, sizeof(int), stream_);
+	if (e == hipSuccess) e = launch_import_weighted<T>(V, ldv, layout_v, Omega, ldo, layout_o, m_, n_, V_, Om_, mpad_, mpad_, npad_, is ? 1 : 0, range_flag_, part, stream_);
+	if (e == hipSuccess) e = hipMemcpyAsync(&flags, range_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_);
+	if (e == hipSuccess) e = hipMemcpyAsync(h_part.data(), part, sizeof(double) * (size_t)parts, hipMemcpyDeviceToHost, stream_);
+	if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+	buffers_.release(part);
+	if (e != hipSuccess) return hip_fail(e, "launch_import_weighted(V, Omega)");
+	if (flags & IMPORT_BAD_WEIGHT) { last_error_ = "weighted NMF: every weight has to be finite and >= 0"; return ST_INVALID; }
+	if (flags & IMPORT_BAD_VALUE) {
+		last_error_ = is ? "weighted NMF with beta <= 0: every entry of V with a weight > 0 has to be finite and > 0"
+		                 : "weighted NMF with beta > 0: every entry of V with a weight > 0 has to be finite and >= 0";
+		return ST_INVALID;
+	}
+	if (!(flags & IMPORT_SOME_WEIGHT)) { last_error_ = "weighted NMF: at least one weight has to be > 0"; return ST_INVALID; }
+	double sum_w = 0;
+	for (long i = 0; i < parts; ++i) sum_w += h_part[(size_t)i];      // in index order: a function of the input and the shape only
+	if (Status st = finish_upload(V_)) return st;
+	HIPX(launch_transpose<T>(Om_, mpad_, m_, n_, Omt_, npad_, stream_));
+	HIPX(hipStreamSynchronize(stream_));
+	sum_w_ = sum_w;
+	beta_uploaded_ = true;
+	return ST_OK;
+}
+
+template <typename T>
+Status Engine<T>::set_factors_device(const T* W, long ldw, int layout_w, const T* H, long ldh, int layout_h) {
+	if (W) { if (Status st = check_device_matrix("W", W, ldw, layout_w, m_, r_)) return st; }
+	if (H) { if (Status st = check_device_matrix("H", H, ldh, layout_h, r_, n_)) return st; }
+	online_stale_ = true;
+	HIPX(hipDeviceSynchronize());
+	if (W) {
+		fused_ready_ = false; w_pending_ = false; f32w_pending_ = false; f64_pending_ = false; f64_product_ahead_ = false; kl_scale_pending_ = false; gram_w_ready_ = false; wx3_valid_ = false; hx3_valid_ = false; wtb_valid_ = false; tri_gw_ready_ = false; qx3_holds_g_ = false; h_product_ahead_ = false;
+		tri_scale_pending_ = false; tri_scale_from_gram_ = false; kl_sw_ready_ = false; w_rows_stale_ = false;
+		HIPX(launch_import_panel<T>(W, ldw, layout_w, true, r_, m_, Wt_, RP_, mpad_, stream_));
+	}
+	if (H) {
+		hx3_valid_ = false; hb_valid_ = false;
+		gram_h_partials_ = false;
+		HIPX(launch_import_panel<T>(H, ldh, layout_h, false, r_, n_, H_, RP_, npad_, stream_));
+	}
+	HIPX(hipStreamSynchronize(stream_));
+	return ST_OK;
+}
+
+template <typename T>
+Status Engine<T>::get_factors_device(T* W, long ldw, int layout_w, T* H, long ldh, int layout_h) {
+	if (W) { if (Status st = check_device_matrix("W", W, ldw, layout_w, m_, r_)) return st; }
+	if (H) { if (Status st = check_device_matrix("H", H, ldh, layout_h, r_, n_)) return st; }
+	HIPX(hipDeviceSynchronize());      // (no stream still writes or reads the destination)
+	if (one_pass_) { if (Status s = onepass_check()) return s; }
+	if (Status s = materialize_w()) return s;
+	if (W) {
+		const T* src = Wt_;
+		if (alg_ == ALG_NSNMF) {
+			const T off = (T)prm_.theta / (T)(unsigned)r_;
+			const T diag = (T)((1.0 - (T)prm_.theta) + off);
+			HIPX(launch_smooth_panel<T>(Wt_, Ws_, RP_, r_, mpad_, off, diag, stream_));
+			src = Ws_;
+		}
+		HIPX(launch_export_panel<T>(src, RP_, mpad_, true, r_, m_, W, ldw, layout_w, stream_));
+	}
+	if (H) HIPX(launch_export_panel<T>(H_, RP_, npad_, false, r_, n_, H, ldh, layout_h, stream_));
+	HIPX(hipStreamSynchronize(stream_));
 	return ST_OK;
 }
 

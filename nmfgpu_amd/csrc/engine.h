@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include <functional>
+#include <string>
 #include <vector>
 
 #include "device_buffers.h"
@@ -24,6 +25,10 @@ struct DeviceFacts {
 	size_t free_bytes = 0;                // free device memory before the engine allocates anything
 };
 hipError_t device_facts(DeviceFacts* out);
+
+// What the runtime knows about a pointer, without an engine and without a kernel: kind 0 not known to the runtime (ordinary host memory), 1 device memory, 2 pinned
+// host memory, 3 anything else (managed, array); device: where it lives (-1 for kind 0); bytes_from_p: bytes from p to the end of its allocation (0 unless kind = 1).
+void device_pointer_info(const void* p, int* kind, int* device, unsigned long long* bytes_from_p);
 
 // ALG_HALS: coordinate descent (kernels_hals.hip, docs/HALS.md) -- the generic launch sequence only, single-engine runs only (no three-phase / sharded form)
 // ALG_NENMF: the HALS iteration with accelerated projected-gradient steps in place of the sweeps (kernels_nenmf.hip, docs/NENMF.md); HALS's limits
@@ -206,10 +211,27 @@ public:
 	// of the engine's beta where Omega > 0 and is not looked at (stored as 0) where Omega = 0.  A second call replaces both.
 	Status upload_dense_weighted(const T* V, long ldv, const T* Omega, long ldo);
 	bool is_weighted() const { return weighted_; }
+	// The same two uploads from DEVICE memory of the engine's device (docs/DEVICE_IO.md): layout 0 column-major (ld >= m), 1 row-major (ld >= n).  The matrix is
+	// imported into the column-major staging image by kernels_import.hip, which evaluates the value rules of the host upload in the same pass; everything behind the
+	// staging image (finish_upload, the weights' transpose) is the host upload's code, so the resident images and the error terms are the host upload's bit for bit
+	// -- only the sum of the weights is added in another order (one partial per workgroup, then in index order).  Statuses and last_error() texts are the host
+	// upload's; with several kinds of violation: a bad weight, then a bad entry of V, then "at least one weight".  Ordering: the call runs hipDeviceSynchronize()
+	// before its first read, so a matrix produced on any stream of the device is complete, and returns after the engine's stream is idle.  The source is never
+	// written.  ST_INVALID with last_error() before any device work for a pointer that is null, not device memory of the engine's device (host and pinned host
+	// memory included), not aligned to the element, or whose extent (outer - 1) * ld + inner does not lie inside its allocation; for ld below the inner extent and
+	// for another layout; and on an engine with sparse_compute / missing_values (their dense input becomes triplets on the host).
+	Status upload_dense_device(const T* V, long ld, int layout);
+	Status upload_dense_weighted_device(const T* V, long ldv, int layout_v, const T* Omega, long ldo, int layout_o);
 
 	// W: host m x r (ld), H: host r x n (ld).  Either pointer may be null (leave as is).
 	Status set_factors(const T* W, long ldw, const T* H, long ldh);
 	Status get_factors(T* W, long ldw, T* H, long ldh);   // nsNMF returns W S, like the reference
+	// ... to and from DEVICE memory, in either layout (W: m x r, H: r x n; 0 column-major, 1 row-major), with the semantics of the host forms (a null pointer leaves
+	// that factor; what set_factors invalidates; nsNMF returns W S) and the pointer checks and the ordering of upload_dense_device: hipDeviceSynchronize() before the
+	// first access, return after the engine's stream is idle -- so any stream may have written the input and any stream may read the output.  get writes the m x r /
+	// r x n block only: the bytes in the gap of ld stay as they are.
+	Status set_factors_device(const T* W, long ldw, int layout_w, const T* H, long ldh, int layout_h);
+	Status get_factors_device(T* W, long ldw, int layout_w, T* H, long ldh, int layout_h);
 	// h_first_column: global index of this engine's first column (column shards draw their part of ONE stream)
 	Status randomize_factors(unsigned seed, bool w, bool h, long h_first_column = 0);
 
@@ -388,6 +410,12 @@ private:
 	Status iterate_beta(bool compute_error, bool constant_w);     // dense beta-divergence multiplicative update (kernels_beta.hip, docs/DIVERGENCE.md)
 	Status beta_refuses(const char* what);            // ... nor of the dense beta-divergence update
 	Status beta_check_values(const T* values, long count, long ld, long rows);   // upload: beta <= 0 needs finite values > 0, beta > 0 finite values >= 0
+	const char* beta_value_fault() const;             // ... the text of a violation
+	// the check of a caller's device matrix (rows x cols, layout, ld) before any device work: ST_OK, or ST_INVALID with last_error() naming `name` and what is wrong
+	Status check_device_matrix(const char* name, const void* p, long ld, int layout, long rows, long cols);
+	Status refuse(std::string text) { error_text_ = std::move(text); last_error_ = error_text_.c_str(); return ST_INVALID; }
+	std::string error_text_;                          // owns a composed last_error_ text
+	int device_ = -1;                                 // the HIP device the buffers live on (allocate_buffers)
 	Status fetch_error_terms(int count_n);            // enqueue the copies, do not wait
 	void finalize_error(bool resolve);
 	void record_begin(int kind = 0);

@@ -348,6 +348,27 @@ hipError_t launch_transpose(const T* src, long lds, int rows, int cols, T* dst, 
 template <typename T>
 hipError_t launch_column_sumsq(const T* V, long ldv, int rows, int cols, T* ps, hipStream_t stream, int* range_flag = nullptr);
 
+// ---- device-resident input and output (kernels_import.hip, docs/DEVICE_IO.md) ----
+// layout: 0 column-major (ld >= rows), 1 row-major (ld >= cols); src is DEVICE memory, read only.  The bits OR-ed into *flags (an integer atomic: independent of order):
+enum { IMPORT_BAD_VALUE = 1, IMPORT_BAD_WEIGHT = 2, IMPORT_SOME_WEIGHT = 4 };
+// src (rows x cols) -> the column-major image dst (ld ldd >= rows_pad; rows_pad, cols_pad multiples of 64), written over the whole rows_pad x cols_pad: 0 beyond
+// rows x cols.  rule: 0 none (flags may be null), 1 every entry finite and >= 0, 2 finite and > 0; a violation sets IMPORT_BAD_VALUE.
+template <typename T>
+hipError_t launch_import_dense(const T* src, long ld, int layout, int rows, int cols, T* dst, long ldd, long rows_pad, long cols_pad, int rule, int* flags, hipStream_t stream);
+// The joint rule of the weighted upload: IMPORT_BAD_WEIGHT for a weight that is not finite or < 0, IMPORT_BAD_VALUE for an entry of V that is not finite, < 0 (or,
+// with positive_rule, = 0) under a weight > 0, IMPORT_SOME_WEIGHT when a weight is > 0.  Vdst holds 0 wherever the weight is 0; Odst the weights.  wsum_part:
+// import_weighted_parts(rows_pad, cols_pad) doubles, one partial sum of the weights per workgroup (the caller adds them in index order).
+template <typename T>
+hipError_t launch_import_weighted(const T* V, long ldv, int layoutV, const T* Omega, long ldo, int layoutO, int rows, int cols, T* Vdst, T* Odst, long ldd, long rows_pad,
+                                  long cols_pad, int positive_rule, int* flags, double* wsum_part, hipStream_t stream);
+long import_weighted_parts(long rows_pad, long cols_pad);
+// A caller's factor, W (len x r; is_w) or H (r x len), to or from the panel [len_pad][RP].  Import writes the whole panel (exact zeros at coordinates >= r and entries
+// >= len); export writes the len x r / r x len block only, never the gap of ld.
+template <typename T>
+hipError_t launch_import_panel(const T* src, long ld, int layout, bool is_w, int r, int len, T* panel, int RP, long len_pad, hipStream_t stream);
+template <typename T>
+hipError_t launch_export_panel(const T* panel, int RP, long len_pad, bool is_w, int r, int len, T* dst, long ld, int layout, hipStream_t stream);
+
 // format: 1 CSR (ptr = rowPtr, idx = column indices), 2 CSC (ptr = columnPtr, idx = row indices),
 // 3 COO (idx = row indices, idx2 = column indices); outer = rows (CSR) / columns (CSC).
 template <typename T>

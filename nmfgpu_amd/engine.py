@@ -73,6 +73,65 @@ def _ld(a: np.ndarray) -> int:
     return a.strides[1] // a.itemsize if a.shape[1] > 1 else max(a.shape[0], 1)
 
 
+COLUMN_MAJOR, ROW_MAJOR = 0, 1
+
+
+def device_matrix(obj, shape, dtype, writable: bool = False):
+    """(ptr, ld, layout) of a 2-D device array for the device entries of Engine (docs/DEVICE_IO.md): ptr the address of element (0, 0), ld the leading dimension in
+    elements, layout COLUMN_MAJOR or ROW_MAJOR.  obj: anything with __cuda_array_interface__ (a torch tensor on the GPU, a cupy array); nothing is imported and no
+    library is called.  Accepted: no strides or C-contiguous strides (row-major, ld = columns), and exactly one unit stride with the other one at least the inner
+    extent (that layout with that ld: a .T view, a slice of a taller or wider array).  TypeError for an object without the interface, another dtype, and a
+    read-only array with writable=True; ValueError for another shape and for strides no (ptr, ld, layout) describes."""
+    iface = getattr(obj, "__cuda_array_interface__", None)
+    if not isinstance(iface, dict):
+        raise TypeError(f"a device array with __cuda_array_interface__ is needed, got {type(obj).__name__}")
+    dt = np.dtype(dtype)
+    try:
+        have = np.dtype(iface["typestr"])
+    except TypeError:
+        have = None
+    if have != dt:
+        raise TypeError(f"the device array must be {dt}, got {iface.get('typestr')!r}")
+    shape = tuple(int(s) for s in shape)
+    if tuple(iface["shape"]) != shape or len(shape) != 2:
+        raise ValueError(f"the device array must have shape {shape}, got {tuple(iface['shape'])}")
+    ptr, read_only = iface["data"]
+    if writable and read_only:
+        raise TypeError("the device array is read-only")
+    rows, cols = shape
+    strides = iface.get("strides")
+    if strides is None:
+        return int(ptr or 0), max(cols, 1), ROW_MAJOR
+    if len(strides) != 2:
+        raise ValueError(f"two strides are needed, got {strides!r}")
+    if any(s <= 0 for s in strides):
+        raise ValueError(f"strides must be positive, got {tuple(strides)}")
+    if any(s % dt.itemsize for s in strides):
+        raise ValueError(f"strides must be multiples of the item size {dt.itemsize}, got {tuple(strides)}")
+    sr, sc = (s // dt.itemsize for s in strides)
+    if sc == 1 and sr != 1 and sr >= cols:
+        return int(ptr or 0), sr, ROW_MAJOR
+    if sr == 1 and sc != 1 and sc >= rows:
+        return int(ptr or 0), sc, COLUMN_MAJOR
+    if sr == 1 and sc == 1:      # (a single row or a single column: either layout describes it)
+        if rows == 1:
+            return int(ptr or 0), 1, COLUMN_MAJOR
+        if cols == 1:
+            return int(ptr or 0), 1, ROW_MAJOR
+    raise ValueError(f"strides {tuple(strides)} (bytes) of a {shape} array: exactly one of them has to be the item size and the other one at least the inner extent")
+
+
+def device_pointer_info(ptr: int) -> dict:
+    """What the pointer check of the device entries sees (nmfamd_device_pointer_info; no kernel, no engine): {"kind": "unknown" | "device" | "pinned" | "other",
+    "device": index or -1, "bytes_from_p": bytes from ptr to the end of its allocation (0 unless "device")}."""
+    lib = library()
+    kind, dev, avail = C.c_int(), C.c_int(), C.c_ulonglong()
+    st = lib.nmfamd_device_pointer_info(C.c_void_p(int(ptr)), C.byref(kind), C.byref(dev), C.byref(avail))
+    if st != 0:
+        raise EngineError(st, "nmfamd_device_pointer_info")
+    return {"kind": ("unknown", "device", "pinned", "other")[kind.value], "device": dev.value, "bytes_from_p": int(avail.value)}
+
+
 def _count(v) -> int:
     """A sweep count as the C int it travels as; anything that is not a whole number is refused here, since the C side would only see it truncated."""
     if isinstance(v, bool) or int(v) != v:
@@ -268,6 +327,39 @@ class Engine:
             self._create()
             st = call()
         self._check(st, what)
+
+    def _dev(self, obj, shape, writable=False):
+        """(ptr, ld, layout) of a device array (device_matrix), or the triple itself where the caller holds a raw device pointer: the library checks that one."""
+        if isinstance(obj, tuple) and len(obj) == 3:
+            return int(obj[0] or 0), int(obj[1]), int(obj[2])
+        return device_matrix(obj, shape, self.dtype, writable)
+
+    def upload_device(self, V, weights=None):
+        """upload() for a V that lies in the memory of the engine's GPU (docs/DEVICE_IO.md): V, and weights on a weighted engine, are device arrays of the engine's
+        dtype and shape (m, n) with __cuda_array_interface__ -- torch tensors, row-major or column-major, views with a leading dimension included (device_matrix) --
+        or raw (ptr, ld, layout) triples.  They are read where they lie, never written, and everything that follows equals upload() of the same values bit for
+        bit (rmsd of a weighted engine: within m n 2^-53).  Work enqueued on any stream of the device is waited for first.  Engines with sparse_compute or
+        missing_values refuse it."""
+        vp, vld, vlay = self._dev(V, (self.m, self.n))
+        if weights is not None:
+            wp, wld, wlay = self._dev(weights, (self.m, self.n))
+            self._check(self._lib.nmfamd_engine_upload_dense_weighted_device(self._h, C.c_void_p(vp), C.c_long(vld), vlay, C.c_void_p(wp), C.c_long(wld), wlay),
+                        "upload_dense_weighted_device")
+            return
+        self._upload(lambda: self._lib.nmfamd_engine_upload_dense_device(self._h, C.c_void_p(vp), C.c_long(vld), vlay), "upload_dense_device")
+
+    def set_factors_device(self, W, H):
+        """set_factors() from device arrays (W: (m, r), H: (r, n), either layout, see upload_device); None leaves that factor."""
+        wp, wld, wlay = self._dev(W, (self.m, self.r)) if W is not None else (None, 0, 0)
+        hp, hld, hlay = self._dev(H, (self.r, self.n)) if H is not None else (None, 0, 0)
+        self._check(self._lib.nmfamd_engine_set_factors_device(self._h, C.c_void_p(wp), C.c_long(wld), wlay, C.c_void_p(hp), C.c_long(hld), hlay), "set_factors_device")
+
+    def get_factors_device(self, W_out, H_out):
+        """get_factors() into caller-supplied writable device arrays (W_out: (m, r), H_out: (r, n), either layout); None skips that factor.  Only the m x r / r x n
+        elements are written.  Returns after the engine's stream is idle: any stream may read the arrays."""
+        wp, wld, wlay = self._dev(W_out, (self.m, self.r), True) if W_out is not None else (None, 0, 0)
+        hp, hld, hlay = self._dev(H_out, (self.r, self.n), True) if H_out is not None else (None, 0, 0)
+        self._check(self._lib.nmfamd_engine_get_factors_device(self._h, C.c_void_p(wp), C.c_long(wld), wlay, C.c_void_p(hp), C.c_long(hld), hlay), "get_factors_device")
 
     def upload_sparse(self, fmt: int, values: np.ndarray, a: np.ndarray, b: np.ndarray, base: int = 0):
         values = np.ascontiguousarray(values, dtype=self.dtype)
