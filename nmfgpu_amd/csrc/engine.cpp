@@ -568,7 +568,7 @@ Status Engine<T>::allocate_buffers() {
 template <typename T>
 Status Engine<T>::finish_upload(T* Vcol) {
 	int odd_values = 0;
-	h_product_ahead_ = false; f64_product_ahead_ = false;
+	state_.v_replaced();
 	HIPX(hipMemsetAsync(range_flag_, 0, sizeof(int), stream_));
 	HIPX(launch_column_sumsq<T>(Vcol, mpad_, m_, n_, psN_, stream_, x3_ ? range_flag_ : nullptr));
 	h_vtv_.resize(n_);
@@ -629,18 +629,22 @@ Status Engine<T>::upload_dense(const T* V, long ld) {
 			}
 		return upload_triplets(rows, cols, vals);
 	}
+	return upload_image(true, [&](T* Vcol) {
+		HIPX(hipMemcpy2DAsync(Vcol, mpad_ * sizeof(T), V, ld * sizeof(T), m_ * sizeof(T), n_, hipMemcpyHostToDevice, stream_));
+		return ST_OK;
+	});
+}
+
+// Every dense upload behind its checks: the column-major image (V_, or a staging buffer where the resident images are tiled or bf16; zeroed: the fill leaves gaps), its fill, finish_upload()
+template <typename T> template <typename Fill>
+Status Engine<T>::upload_image(bool zeroed, Fill fill) {
+	DeviceBuffers staging;      // freed on every way out
 	T* Vcol = V_;
-	const bool staged = tiled_ || bf16_;
-	if (staged) {
-		Vcol = nullptr;
-		hipError_t e = buffers_.device(&Vcol, sizeof(T) * (size_t)(mpad_ * npad_), true, stream_);
-		if (e != hipSuccess) { buffers_.release(Vcol); return hip_fail(e, "hipMalloc / hipMemsetAsync(staging)"); }
-	}
-	hipError_t e = hipMemcpy2DAsync(Vcol, mpad_ * sizeof(T), V, ld * sizeof(T), m_ * sizeof(T), n_, hipMemcpyHostToDevice, stream_);
-	Status st = e == hipSuccess ? finish_upload(Vcol) : hip_fail(e, "hipMemcpy2DAsync(V)");
-	if (staged) buffers_.release(Vcol);
-	if (beta_dense_ && st == ST_OK) beta_uploaded_ = true;
-	return st;
+	if (tiled_ || bf16_) HIPX(staging.device(&Vcol, sizeof(T) * (size_t)(mpad_ * npad_), zeroed, stream_));
+	if (Status st = fill(Vcol)) return st;
+	if (Status st = finish_upload(Vcol)) return st;
+	if (beta_dense_) beta_uploaded_ = true;
+	return ST_OK;
 }
 
 // Weighted engines: V and its weights.  The values are checked jointly on the host (the weights alone, then V where its weight is > 0), the sum of the weights is
@@ -651,36 +655,46 @@ Status Engine<T>::upload_dense_weighted(const T* V, long ldv, const T* Omega, lo
 	if (!weighted_) { last_error_ = "weighted upload: the engine was not created with 'weighted' = 1"; return ST_INVALID; }
 	if (!V || !Omega || ldv < m_ || ldo < m_) return ST_INVALID;
 	beta_uploaded_ = false;
-	const bool is = beta_ <= 0;
 	double sum_w = 0;
-	bool any = false;
+	int seen = 0;      // (IMPORT_SOME_WEIGHT once a weight > 0 was met)
 	std::vector<T> clean((size_t)m_ * (size_t)n_);
 	for (long j = 0; j < n_; ++j)
 		for (long i = 0; i < m_; ++i) {
 			const T w = Omega[(size_t)j * ldo + i];
-			if (!std::isfinite(w) || w < T(0)) { last_error_ = "weighted NMF: every weight has to be finite and >= 0"; return ST_INVALID; }
+			if (!std::isfinite(w) || w < T(0)) return refuse_weighted(IMPORT_BAD_WEIGHT);
 			T v = T(0);
 			if (w > T(0)) {
 				v = V[(size_t)j * ldv + i];
-				if (!std::isfinite(v) || v < T(0) || (is && v == T(0))) {
-					last_error_ = is ? "weighted NMF with beta <= 0: every entry of V with a weight > 0 has to be finite and > 0"
-					                 : "weighted NMF with beta > 0: every entry of V with a weight > 0 has to be finite and >= 0";
-					return ST_INVALID;
-				}
-				any = true;
+				if (!std::isfinite(v) || v < T(0) || (beta_ <= 0 && v == T(0))) return refuse_weighted(IMPORT_BAD_VALUE);
+				seen = IMPORT_SOME_WEIGHT;
 				sum_w += (double)w;
 			}
 			clean[(size_t)j * m_ + i] = v;
 		}
-	if (!any) { last_error_ = "weighted NMF: at least one weight has to be > 0"; return ST_INVALID; }
-	hipError_t e = hipMemcpy2DAsync(V_, mpad_ * sizeof(T), clean.data(), m_ * sizeof(T), m_ * sizeof(T), n_, hipMemcpyHostToDevice, stream_);
-	if (e != hipSuccess) return hip_fail(e, "hipMemcpy2DAsync(V)");
-	if (Status st = finish_upload(V_)) return st;      // (V_ is the column-major image; Vt_ its transpose; synchronises)
+	if (Status st = refuse_weighted(seen)) return st;
+	HIPX(hipMemcpy2DAsync(V_, mpad_ * sizeof(T), clean.data(), m_ * sizeof(T), m_ * sizeof(T), n_, hipMemcpyHostToDevice, stream_));
 	HIPX(hipMemcpy2DAsync(Om_, mpad_ * sizeof(T), Omega, ldo * sizeof(T), m_ * sizeof(T), n_, hipMemcpyHostToDevice, stream_));
+	return finish_weighted_upload(sum_w);
+}
+
+// What both forms of the weighted upload refuse, by the flags of kernels_import.hip in their precedence (the host form stops at the first bad element: one flag)
+template <typename T>
+Status Engine<T>::refuse_weighted(int flags) {
+	if (flags & IMPORT_BAD_WEIGHT) last_error_ = "weighted NMF: every weight has to be finite and >= 0";
+	else if (flags & IMPORT_BAD_VALUE) last_error_ = beta_ <= 0 ? "weighted NMF with beta <= 0: every entry of V with a weight > 0 has to be finite and > 0"
+	                                                            : "weighted NMF with beta > 0: every entry of V with a weight > 0 has to be finite and >= 0";
+	else if (!(flags & IMPORT_SOME_WEIGHT)) last_error_ = "weighted NMF: at least one weight has to be > 0";
+	else return ST_OK;
+	return ST_INVALID;
+}
+
+// ... and what both forms end with, V_ and Om_ holding the column-major images: the resident images and the error terms of V, the transpose of the weights
+template <typename T>
+Status Engine<T>::finish_weighted_upload(double sum_w) {
+	if (Status st = finish_upload(V_)) return st;      // (V_ is the column-major image; Vt_ its transpose; synchronises)
 	HIPX(launch_transpose<T>(Om_, mpad_, m_, n_, Omt_, npad_, stream_));
 	HIPX(hipStreamSynchronize(stream_));
-	sum_w_ = sum_w;
-	beta_uploaded_ = true;
+	sum_w_ = sum_w; beta_uploaded_ = true;
 	return ST_OK;
 }
 
@@ -749,29 +763,15 @@ Status Engine<T>::upload_dense_device(const T* V, long ld, int layout) {
 	if (Status st = check_device_matrix("V", V, ld, layout, m_, n_)) return st;
 	if (beta_dense_) beta_uploaded_ = false;
 	HIPX(hipDeviceSynchronize());      // whatever stream produced V has finished
-	T* Vcol = V_;
-	const bool staged = tiled_ || bf16_;
-	if (staged) {
-		Vcol = nullptr;
-		hipError_t e = buffers_.device(&Vcol, sizeof(T) * (size_t)(mpad_ * npad_), false, stream_);      // (the import writes every element of the image)
-		if (e != hipSuccess) { buffers_.release(Vcol); return hip_fail(e, "hipMalloc(staging)"); }
-	}
-	const int rule = beta_dense_ ? (beta_ <= 0 ? 2 : 1) : 0;
-	int flags = 0;
-	hipError_t e = hipSuccess;
-	if (rule != 0) e = hipMemsetAsync(range_flag_, 0, sizeof(int), stream_);
-	if (e == hipSuccess) e = launch_import_dense<T>(V, ld, layout, m_, n_, Vcol, mpad_, mpad_, npad_, rule, range_flag_, stream_);
-	if (e == hipSuccess && rule != 0) {
-		e = hipMemcpyAsync(&flags, range_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_);
-		if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-	}
-	Status st = ST_OK;
-	if (e != hipSuccess) st = hip_fail(e, "launch_import_dense(V)");
-	else if (flags & IMPORT_BAD_VALUE) { last_error_ = beta_value_fault(); st = ST_INVALID; }
-	else st = finish_upload(Vcol);
-	if (staged) buffers_.release(Vcol);
-	if (beta_dense_ && st == ST_OK) beta_uploaded_ = true;
-	return st;
+	return upload_image(false, [&](T* Vcol) {      // (not zeroed: the import writes every element of the image)
+		const int rule = beta_dense_ ? (beta_ <= 0 ? 2 : 1) : 0;
+		int flags = 0;
+		if (rule != 0) HIPX(hipMemsetAsync(range_flag_, 0, sizeof(int), stream_));
+		HIPX(launch_import_dense<T>(V, ld, layout, m_, n_, Vcol, mpad_, mpad_, npad_, rule, range_flag_, stream_));
+		if (rule != 0) { HIPX(hipMemcpyAsync(&flags, range_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_)); HIPX(hipStreamSynchronize(stream_)); }
+		if (flags & IMPORT_BAD_VALUE) { last_error_ = beta_value_fault(); return ST_INVALID; }
+		return ST_OK;
+	});
 }
 
 template <typename T>
@@ -781,53 +781,31 @@ Status Engine<T>::upload_dense_weighted_device(const T* V, long ldv, int layout_
 	if (Status st = check_device_matrix("Omega", Omega, ldo, layout_o, m_, n_)) return st;
 	beta_uploaded_ = false;
 	HIPX(hipDeviceSynchronize());
-	const bool is = beta_ <= 0;
 	const long parts = import_weighted_parts(mpad_, npad_);
+	DeviceBuffers scratch;      // freed on every way out
 	double* part = nullptr;
-	hipError_t e = buffers_.device(&part, sizeof(double) * (size_t)parts, false, stream_);
-	if (e != hipSuccess) { buffers_.release(part); return hip_fail(e, "hipMalloc(weight sums)"); }
+	HIPX(scratch.device(&part, sizeof(double) * (size_t)parts, false, stream_));
 	std::vector<double> h_part((size_t)parts);
 	int flags = 0;
-	e = hipMemsetAsync(range_flag_, 0, sizeof(int), stream_);
-	if (e == hipSuccess) e = launch_import_weighted<T>(V, ldv, layout_v, Omega, ldo, layout_o, m_, n_, V_, Om_, mpad_, mpad_, npad_, is ? 1 : 0, range_flag_, part, stream_);
-	if (e == hipSuccess) e = hipMemcpyAsync(&flags, range_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_);
-	if (e == hipSuccess) e = hipMemcpyAsync(h_part.data(), part, sizeof(double) * (size_t)parts, hipMemcpyDeviceToHost, stream_);
-	if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-	buffers_.release(part);
-	if (e != hipSuccess) return hip_fail(e, "launch_import_weighted(V, Omega)");
-	if (flags & IMPORT_BAD_WEIGHT) { last_error_ = "weighted NMF: every weight has to be finite and >= 0"; return ST_INVALID; }
-	if (flags & IMPORT_BAD_VALUE) {
-		last_error_ = is ? "weighted NMF with beta <= 0: every entry of V with a weight > 0 has to be finite and > 0"
-		                 : "weighted NMF with beta > 0: every entry of V with a weight > 0 has to be finite and >= 0";
-		return ST_INVALID;
-	}
-	if (!(flags & IMPORT_SOME_WEIGHT)) { last_error_ = "weighted NMF: at least one weight has to be > 0"; return ST_INVALID; }
+	HIPX(hipMemsetAsync(range_flag_, 0, sizeof(int), stream_));
+	HIPX(launch_import_weighted<T>(V, ldv, layout_v, Omega, ldo, layout_o, m_, n_, V_, Om_, mpad_, mpad_, npad_, beta_ <= 0 ? 1 : 0, range_flag_, part, stream_));
+	HIPX(hipMemcpyAsync(&flags, range_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_));
+	HIPX(hipMemcpyAsync(h_part.data(), part, sizeof(double) * (size_t)parts, hipMemcpyDeviceToHost, stream_));
+	HIPX(hipStreamSynchronize(stream_));
+	if (Status st = refuse_weighted(flags)) return st;
 	double sum_w = 0;
 	for (long i = 0; i < parts; ++i) sum_w += h_part[(size_t)i];      // in index order: a function of the input and the shape only
-	if (Status st = finish_upload(V_)) return st;
-	HIPX(launch_transpose<T>(Om_, mpad_, m_, n_, Omt_, npad_, stream_));
-	HIPX(hipStreamSynchronize(stream_));
-	sum_w_ = sum_w;
-	beta_uploaded_ = true;
-	return ST_OK;
+	return finish_weighted_upload(sum_w);
 }
 
 template <typename T>
 Status Engine<T>::set_factors_device(const T* W, long ldw, int layout_w, const T* H, long ldh, int layout_h) {
 	if (W) { if (Status st = check_device_matrix("W", W, ldw, layout_w, m_, r_)) return st; }
 	if (H) { if (Status st = check_device_matrix("H", H, ldh, layout_h, r_, n_)) return st; }
-	online_stale_ = true;
+	state_.factors_touched();
 	HIPX(hipDeviceSynchronize());
-	if (W) {
-		fused_ready_ = false; w_pending_ = false; f32w_pending_ = false; f64_pending_ = false; f64_product_ahead_ = false; kl_scale_pending_ = false; gram_w_ready_ = false; wx3_valid_ = false; hx3_valid_ = false; wtb_valid_ = false; tri_gw_ready_ = false; qx3_holds_g_ = false; h_product_ahead_ = false;
-		tri_scale_pending_ = false; tri_scale_from_gram_ = false; kl_sw_ready_ = false; w_rows_stale_ = false;
-		HIPX(launch_import_panel<T>(W, ldw, layout_w, true, r_, m_, Wt_, RP_, mpad_, stream_));
-	}
-	if (H) {
-		hx3_valid_ = false; hb_valid_ = false;
-		gram_h_partials_ = false;
-		HIPX(launch_import_panel<T>(H, ldh, layout_h, false, r_, n_, H_, RP_, npad_, stream_));
-	}
+	if (W) { state_.w_set(); HIPX(launch_import_panel<T>(W, ldw, layout_w, true, r_, m_, Wt_, RP_, mpad_, stream_)); }
+	if (H) { state_.h_set(); HIPX(launch_import_panel<T>(H, ldh, layout_h, false, r_, n_, H_, RP_, npad_, stream_)); }
 	HIPX(hipStreamSynchronize(stream_));
 	return ST_OK;
 }
@@ -837,18 +815,9 @@ Status Engine<T>::get_factors_device(T* W, long ldw, int layout_w, T* H, long ld
 	if (W) { if (Status st = check_device_matrix("W", W, ldw, layout_w, m_, r_)) return st; }
 	if (H) { if (Status st = check_device_matrix("H", H, ldh, layout_h, r_, n_)) return st; }
 	HIPX(hipDeviceSynchronize());      // (no stream still writes or reads the destination)
-	if (one_pass_) { if (Status s = onepass_check()) return s; }
-	if (Status s = materialize_w()) return s;
-	if (W) {
-		const T* src = Wt_;
-		if (alg_ == ALG_NSNMF) {
-			const T off = (T)prm_.theta / (T)(unsigned)r_;
-			const T diag = (T)((1.0 - (T)prm_.theta) + off);
-			HIPX(launch_smooth_panel<T>(Wt_, Ws_, RP_, r_, mpad_, off, diag, stream_));
-			src = Ws_;
-		}
-		HIPX(launch_export_panel<T>(src, RP_, mpad_, true, r_, m_, W, ldw, layout_w, stream_));
-	}
+	const T* src = nullptr;
+	if (Status s = export_panel_w(W != nullptr, &src)) return s;
+	if (W) HIPX(launch_export_panel<T>(src, RP_, mpad_, true, r_, m_, W, ldw, layout_w, stream_));
 	if (H) HIPX(launch_export_panel<T>(H_, RP_, npad_, false, r_, n_, H, ldh, layout_h, stream_));
 	HIPX(hipStreamSynchronize(stream_));
 	return ST_OK;
@@ -895,34 +864,25 @@ Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const
 		if (prm_.is_masked() && vals.empty()) { last_error_ = "missing values: no stored entry inside the matrix"; return ST_INVALID; }
 		return upload_triplets(rows, cols, vals);
 	}
+	DeviceBuffers scratch;      // the caller's arrays on the device: freed on every way out
 	T* d_val = nullptr; int *d_a = nullptr, *d_b = nullptr;
-	T* Vcol = nullptr;
 	const int outer = format == 1 ? m_ : n_;
 	const long na = format == 3 ? nnz : (long)outer + 1;
-	Status st = ST_OK;
-	do {
-		hipError_t e;
-		if ((e = buffers_.device(&d_val, sizeof(T) * (size_t)std::max<long>(nnz, 1), false, stream_)) != hipSuccess ||
-		    (e = buffers_.device(&d_a, sizeof(int) * (size_t)std::max<long>(na, 1), false, stream_)) != hipSuccess ||
-		    (e = buffers_.device(&d_b, sizeof(int) * (size_t)std::max<long>(nnz, 1), false, stream_)) != hipSuccess) { st = hip_fail(e, "hipMalloc(sparse staging)"); break; }
-		if (nnz > 0) {
-			if ((e = hipMemcpyAsync(d_val, values, sizeof(T) * nnz, hipMemcpyHostToDevice, stream_)) != hipSuccess ||
-			    (e = hipMemcpyAsync(d_b, b, sizeof(int) * nnz, hipMemcpyHostToDevice, stream_)) != hipSuccess) { st = hip_fail(e, "hipMemcpyAsync(sparse)"); break; }
-		}
-		if (na > 0 && (e = hipMemcpyAsync(d_a, a, sizeof(int) * na, hipMemcpyHostToDevice, stream_)) != hipSuccess) { st = hip_fail(e, "hipMemcpyAsync(sparse ptr)"); break; }
-		if ((tiled_ || bf16_) && (e = buffers_.device(&Vcol, sizeof(T) * (size_t)(mpad_ * npad_), false, stream_)) != hipSuccess) { st = hip_fail(e, "hipMalloc(staging)"); break; }
-		if (!(tiled_ || bf16_)) Vcol = V_;
-		if ((e = hipMemsetAsync(Vcol, 0, sizeof(T) * (size_t)(mpad_ * npad_), stream_)) != hipSuccess) { st = hip_fail(e, "hipMemsetAsync(V)"); break; }
+	HIPX(scratch.device(&d_val, sizeof(T) * (size_t)std::max<long>(nnz, 1), false, stream_));
+	HIPX(scratch.device(&d_a, sizeof(int) * (size_t)std::max<long>(na, 1), false, stream_));
+	HIPX(scratch.device(&d_b, sizeof(int) * (size_t)std::max<long>(nnz, 1), false, stream_));
+	if (nnz > 0) {
+		HIPX(hipMemcpyAsync(d_val, values, sizeof(T) * nnz, hipMemcpyHostToDevice, stream_));
+		HIPX(hipMemcpyAsync(d_b, b, sizeof(int) * nnz, hipMemcpyHostToDevice, stream_));
+	}
+	if (na > 0) HIPX(hipMemcpyAsync(d_a, a, sizeof(int) * na, hipMemcpyHostToDevice, stream_));
+	return upload_image(false, [&](T* Vcol) {      // (not zeroed: cleared here, V_ included where it is the image)
+		HIPX(hipMemsetAsync(Vcol, 0, sizeof(T) * (size_t)(mpad_ * npad_), stream_));
 		// CSR: ptr = a (rowPtr), idx = b (columns); CSC: ptr = a (columnPtr), idx = b (rows); COO: idx = a (rows), idx2 = b (columns)
-		if (format == 3) e = launch_densify<T>(3, d_val, nullptr, d_a, d_b, nnz, 0, base, Vcol, mpad_, m_, n_, stream_);
-		else e = launch_densify<T>(format, d_val, d_a, d_b, nullptr, nnz, outer, base, Vcol, mpad_, m_, n_, stream_);
-		if (e != hipSuccess) { st = hip_fail(e, "densify"); break; }
-		st = finish_upload(Vcol);
-		if (beta_dense_ && st == ST_OK) beta_uploaded_ = true;
-	} while (0);
-	if (tiled_ || bf16_) buffers_.release(Vcol);
-	buffers_.release(d_val, d_a, d_b);
-	return st;
+		if (format == 3) HIPX(launch_densify<T>(3, d_val, nullptr, d_a, d_b, nnz, 0, base, Vcol, mpad_, m_, n_, stream_));
+		else HIPX(launch_densify<T>(format, d_val, d_a, d_b, nullptr, nnz, outer, base, Vcol, mpad_, m_, n_, stream_));
+		return ST_OK;
+	});
 }
 
 // The CSR and CSC images built on the device from the caller's arrays as they are (kernels_sparse_setup.hip; reference: the device-side conversions of
@@ -1010,20 +970,18 @@ Status Engine<T>::upload_sparse_device(int format, const T* values, const int* a
 
 template <typename T>
 Status Engine<T>::set_factors(const T* W, long ldw, const T* H, long ldh) {
-	online_stale_ = true;      // (a minibatch engine starts again from A = W, B = 1, as scikit-learn does at the start of a fit)
+	state_.factors_touched();
 	if (W) {
 		if (ldw < m_) return ST_INVALID;
-		fused_ready_ = false; w_pending_ = false; f32w_pending_ = false; f64_pending_ = false; f64_product_ahead_ = false; kl_scale_pending_ = false; gram_w_ready_ = false; wx3_valid_ = false; hx3_valid_ = false; wtb_valid_ = false; tri_gw_ready_ = false; qx3_holds_g_ = false; h_product_ahead_ = false;
-		tri_scale_pending_ = false; tri_scale_from_gram_ = false; kl_sw_ready_ = false; w_rows_stale_ = false;
+		state_.w_set();
 		// host m x r (column-major) -> staging m x r (ld mpad) -> Wt panel (element (c, i) at [i * RP + c])
 		HIPX(hipMemcpy2DAsync(stage_, mpad_ * sizeof(T), W, ldw * sizeof(T), m_ * sizeof(T), r_, hipMemcpyHostToDevice, stream_));
 		HIPX(hipMemsetAsync(Wt_, 0, sizeof(T) * (size_t)RP_ * mpad_, stream_));
 		HIPX(launch_transpose<T>(stage_, mpad_, m_, r_, Wt_, RP_, stream_));
 	}
 	if (H) {
-		hx3_valid_ = false; hb_valid_ = false;
 		if (ldh < r_) return ST_INVALID;
-		gram_h_partials_ = false;
+		state_.h_set();
 		HIPX(hipMemsetAsync(H_, 0, sizeof(T) * (size_t)RP_ * npad_, stream_));
 		HIPX(hipMemcpy2DAsync(H_, RP_ * sizeof(T), H, ldh * sizeof(T), r_ * sizeof(T), n_, hipMemcpyHostToDevice, stream_));
 	}
@@ -1031,20 +989,22 @@ Status Engine<T>::set_factors(const T* W, long ldw, const T* H, long ldh) {
 	return ST_OK;
 }
 
+// *src: the panel get_factors / get_factors_device read W from -- pending scales folded in; nsNMF: W S in Ws_ (storeFactorization, AlgorithmNonSmoothNMF.h:221-225)
 template <typename T>
-Status Engine<T>::get_factors(T* W, long ldw, T* H, long ldh) {
+Status Engine<T>::export_panel_w(bool want_w, const T** src) {
 	if (one_pass_) { if (Status s = onepass_check()) return s; }
 	if (Status s = materialize_w()) return s;
+	*src = Wt_;
+	if (want_w && alg_ == ALG_NSNMF) { HIPX(smooth_panel(Wt_, Ws_, mpad_)); *src = Ws_; }
+	return ST_OK;
+}
+
+template <typename T>
+Status Engine<T>::get_factors(T* W, long ldw, T* H, long ldh) {
+	const T* src = nullptr;
+	if (Status s = export_panel_w(W != nullptr && ldw >= m_, &src)) return s;
 	if (W) {
-		if (ldw < m_) return ST_INVALID;
-		const T* src = Wt_;
-		if (alg_ == ALG_NSNMF) {
-			// storeFactorization returns W S (AlgorithmNonSmoothNMF.h:221-225)
-			const T off = (T)prm_.theta / (T)(unsigned)r_;
-			const T diag = (T)((1.0 - (T)prm_.theta) + off);
-			HIPX(launch_smooth_panel<T>(Wt_, Ws_, RP_, r_, mpad_, off, diag, stream_));
-			src = Ws_;
-		}
+		if (ldw < m_) return ST_INVALID;      // (behind materialize_w, which folds pending scales and so changes the bits of later iterations)
 		HIPX(launch_transpose<T>(src, RP_, r_, m_, stage_, mpad_, stream_));
 		HIPX(hipMemcpy2DAsync(W, ldw * sizeof(T), stage_, mpad_ * sizeof(T), m_ * sizeof(T), r_, hipMemcpyDeviceToHost, stream_));
 	}
@@ -1059,11 +1019,9 @@ Status Engine<T>::get_factors(T* W, long ldw, T* H, long ldh) {
 template <typename T>
 Status Engine<T>::randomize_factors(unsigned seed, bool w, bool h, long h_first_column) {
 	// The reference seeds W's and H's generators identically (RandomValueStrategy.cpp:53-69).
-	online_stale_ = true;
-	if (w) { h_product_ahead_ = false; f64_product_ahead_ = false; kl_sw_ready_ = false; fused_ready_ = false; w_pending_ = false; f32w_pending_ = false; f64_pending_ = false; kl_scale_pending_ = false; gram_w_ready_ = false; wx3_valid_ = false; hx3_valid_ = false; wtb_valid_ = false; tri_gw_ready_ = false; qx3_holds_g_ = false; tri_scale_pending_ = false; tri_scale_from_gram_ = false; w_rows_stale_ = false; }
-	if (h) { gram_h_partials_ = false; hx3_valid_ = false; hb_valid_ = false; }
-	if (w) HIPX(launch_fill_uniform<T>(Wt_, RP_, r_, m_, mpad_, seed, stream_));
-	if (h) HIPX(launch_fill_uniform<T>(H_, RP_, r_, n_, npad_, seed, stream_, h_first_column));
+	state_.factors_touched();
+	if (w) { state_.w_set(); HIPX(launch_fill_uniform<T>(Wt_, RP_, r_, m_, mpad_, seed, stream_)); }
+	if (h) { state_.h_set(); HIPX(launch_fill_uniform<T>(H_, RP_, r_, n_, npad_, seed, stream_, h_first_column)); }
 	return ST_OK;
 }
 
@@ -1173,7 +1131,7 @@ Status Engine<T>::mu64_update(bool is_w, const T* slabs, int S, long slab_stride
 		if (peers != nullptr && !gram_image_) return ST_INVALID;
 		// nsNMF: the smoothing matrix goes around the H update's r x r product (the launches on either side work on the unsmoothed W image and on the image of S H)
 		SmoothAround ns;
-		ns.off = (float)prm_.theta / (float)(unsigned)r_; ns.diag = (float)((1.0 - (float)prm_.theta) + ns.off); ns.r = r_;
+		ns.off = smoothing_constants().off; ns.diag = smoothing_constants().diag; ns.r = r_;
 		const bool smooth = alg_ == ALG_NSNMF && !is_w;
 		if (alg_ == ALG_NSNMF && !gram_image_) return ST_INVALID;
 		if (gram_image_) HIPX(launch_mu64_update32(is_w ? 1 : 0, P, slabs, S, slab_stride, Q, scale_, eps, ps, len, len_pad, is_w ? G_ : nullptr, compute_error ? 1 : 0, stream_, xo, xks, peers,
@@ -1459,23 +1417,23 @@ Status Engine<T>::h_step(bool compute_error) {
 template <typename T>
 Status Engine<T>::h_step_impl(bool compute_error) {
 	const T eps = std::numeric_limits<T>::epsilon();
-	h_product_ahead_ = false; f64_product_ahead_ = false;                           // (the three-phase API enqueues its own W^T V)
+	state_.h_product_ahead = false; state_.f64_product_ahead = false;                           // (the three-phase API enqueues its own W^T V)
 	if constexpr (std::is_same<T, float>::value) {
 		if (fused_capable()) {
 			// sharded form of the four-launch iteration (kernels_mu64.hip): K_H + U_H here
-			if (!fused_ready_) {
+			if (!state_.fused_ready) {
 				if (!gram_image_) HIPX(launch_mu64_gram_partials(Wt_, (int)mpad_, gramW_part_, stream_));
 				normalize_next_ = 0;
-				fused_ready_ = true;
+				state_.fused_ready = true;
 			}
 			GramReduceArgs rgW = gram_args(true, G_, scale_, normalize_next_);
-			if (Status s = product_h(Wt_, &rgW, x3_ && wx3_valid_)) return s;
+			if (Status s = product_h(Wt_, &rgW, x3_ && state_.wx3_valid)) return s;
 			if (Status s = mu64_update(false, slabs_, planH_.splits, slab_stride_, rgW.ksplit > 1 ? reinterpret_cast<const T*>(Gpart_) : G_, compute_error)) return s;
-			hx3_valid_ = x3_;
+			state_.hx3_valid = x3_;
 			return ST_OK;
 		}
 	}
-	hx3_valid_ = false;
+	state_.hx3_valid = false;
 	if constexpr (std::is_same<T, float>::value) {
 		if (tri_) {
 			// The fragments hold bf16(W) as the panel stores it -- unsmoothed, without the pending column scale D; the product's output gets both:
@@ -1483,11 +1441,10 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 			GramReduceArgs ride = {nullptr, 0, nullptr, nullptr, 0};
 			if (Status s = tri_prepare_w(&ride)) return s;
 			if (Status s = product_h(Wt_, ride.tri_frags != nullptr ? &ride : nullptr, true)) return s;
-			T off, diag;
-			tri_smoothing(&off, &diag);
+			const auto [off, diag] = smoothing_constants();
 			PanelTriExtras ex;
 			ex.num_transform = true;
-			if (tri_scale_pending_) { ex.num_colsq = colsq_; ex.num_colsq_parts = colsq_parts_; }
+			if (state_.tri_scale_pending) { ex.num_colsq = colsq_; ex.num_colsq_parts = colsq_parts_; }
 			ex.num_a = (float)(diag - off); ex.num_b = (float)off; ex.r = r_;
 			// ... and the denominator S D G D S H from the Gram matrix as the reduction left it (its split image is in qx3_): D and S around the product
 			ex.den_transform = true;
@@ -1497,43 +1454,41 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 			ex.frag_out = Hb_; ex.frag_KS = ksW_; ex.frag_a = (float)(diag - off); ex.frag_b = (float)off;
 			// (old_as_bf16 stays off here: the H update is bound by what a CU can ingest, not by its MFMAs -- 28.3 -> 27.7 us -- and H's distance from the
 			// fp64 oracle doubles, 5.7e-5 -> 1.5e-4 after 10 iterations; the W update gains 11 us at no measurable cost, tri_update_w)
-			// (qx3_holds_g_: the Gram reduction left the split image of W^T W in qx3_ -- Q = nullptr tells the update kernel so; else it packs Gw_raw_)
-			HIPX(launch_panel_update<T>(PANEL_MU, H_, slabs_, planH_.splits, slab_stride_, qx3_holds_g_ ? nullptr : reinterpret_cast<const T*>(Gw_raw_), RP_, (int)npad_, eps,
+			// (state_.qx3_holds_g: the Gram reduction left the split image of W^T W in qx3_ -- Q = nullptr tells the update kernel so; else it packs Gw_raw_)
+			HIPX(launch_panel_update<T>(PANEL_MU, H_, slabs_, planH_.splits, slab_stride_, state_.qx3_holds_g ? nullptr : reinterpret_cast<const T*>(Gw_raw_), RP_, (int)npad_, eps,
 			                            compute_error ? psN_ : nullptr, n_, nullptr, nullptr, stream_, nullptr, nullptr, 0, qx3_, &ex));
-			qx3_holds_g_ = false;
-			hb_valid_ = true;
+			state_.qx3_holds_g = false;
+			state_.hb_valid = true;
 			return ST_OK;
 		}
 	}
 	if (Status s = materialize_w()) return s;
 	const T* F = Wt_;
 	if (alg_ == ALG_NSNMF) {
-		const T off = (T)prm_.theta / (T)(unsigned)r_;
-		const T diag = (T)((1.0 - (T)prm_.theta) + off);
-		HIPX(launch_smooth_panel<T>(Wt_, Ws_, RP_, r_, mpad_, off, diag, stream_));
+		HIPX(smooth_panel(Wt_, Ws_, mpad_));
 		F = Ws_;
 	}
-	if (!(gram_w_ready_ && F == Wt_)) HIPX(launch_gram<T>(F, RP_, m_, gram_parts_, gram_part_, G_, stream_));
-	gram_w_ready_ = false;      // consumed (the inverse passenger / update below read G_; W changes in the W step)
+	if (!(state_.gram_w_ready && F == Wt_)) HIPX(launch_gram<T>(F, RP_, m_, gram_parts_, gram_part_, G_, stream_));
+	state_.gram_w_ready = false;      // consumed (the inverse passenger / update below read G_; W changes in the W step)
 	const int S = planH_.splits;
 	if (hals_family(alg_)) {
 		// coordinate sweep over every column of H against G = W^T W and the summed slabs of W^T V; ps: the per-column terms of tr(H^T W^T V), as PANEL_MU
 		// writes them.  No split image of the new H: the next product packs its operand itself.
-		if (Status s = product_h(F, nullptr, x3_ && wx3_valid_ && F == Wt_)) return s;
+		if (Status s = product_h(F, nullptr, x3_ && state_.wx3_valid && F == Wt_)) return s;
 		// (penalties: G and the slabs stay raw -- ps and the trace of the error term read them)
 		// (sweeps_h sweeps against this one G and these slabs, in one launch; one sweep is launch_panel_sweep_hals)
 		// (a sweep tolerance: the counts are maximum counts and every column stops by itself, kernels_hals_dyn.hip)
 		// (NeNMF: steps_h projected-gradient steps in the same place, kernels_nenmf.hip)
 		if (Status s = family_step(false, H_, G_, S, (int)npad_, n_, compute_error ? psN_ : nullptr, nullptr, (T)prm_.l1H, (T)prm_.l2H)) return s;
-		hx3_valid_ = false;
+		state_.hx3_valid = false;
 		return ST_OK;
 	}
 	if (alg_ == ALG_MU || alg_ == ALG_NSNMF) {
-		if (Status s = product_h(F, nullptr, x3_ && wx3_valid_ && F == Wt_)) return s;
+		if (Status s = product_h(F, nullptr, x3_ && state_.wx3_valid && F == Wt_)) return s;
 		const bool emit = x3_ && alg_ == ALG_MU && panel_update_delivers_gram(RP_, sizeof(T));   // nsNMF's W step consumes the smoothed panel
 		HIPX(launch_panel_update<T>(PANEL_MU, H_, slabs_, S, slab_stride_, G_, RP_, (int)npad_, eps,
 		                            compute_error ? psN_ : nullptr, n_, nullptr, nullptr, stream_, nullptr, emit ? Hx3_ : nullptr, ksW_, qx3_));
-		hx3_valid_ = emit;
+		state_.hx3_valid = emit;
 	} else {
 		T off = 0, diag = 0;
 		if (alg_ == ALG_GDCLS) diag = (T)prm_.lambda;
@@ -1551,11 +1506,11 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 			if constexpr (std::is_same<T, float>::value) {
 				GramReduceArgs rg = {nullptr, 0, nullptr, nullptr, 0};
 				rg.inv_a = G_; rg.inv_out = Qinv_; rg.inv_offdiag = off; rg.inv_diag = diag; rg.inv_r = r_;
-				if (Status s = product_h(F, &rg, x3_ && wx3_valid_ && F == Wt_)) return s;
+				if (Status s = product_h(F, &rg, x3_ && state_.wx3_valid && F == Wt_)) return s;
 			}
 		} else {
 			if (Status s = normal_inverse_fork(G_, off, diag)) return s;
-			if (Status s = product_h(F, nullptr, x3_ && wx3_valid_ && F == Wt_)) return s;
+			if (Status s = product_h(F, nullptr, x3_ && state_.wx3_valid && F == Wt_)) return s;
 			if (Status s = normal_inverse_join()) return s;
 		}
 		const bool emit = x3_ && panel_update_delivers_gram(RP_, sizeof(T));
@@ -1565,8 +1520,8 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 		if constexpr (std::is_same<T, float>::value) { if (gram_from_update() && !(alg_ == ALG_GDCLS && emit && RP_ == 64 && passengers_ride(planWx_) && h_partials_unneeded_)) hpart = gramH_part_; }
 		HIPX(launch_panel_update<T>(PANEL_LS, H_, slabs_, S, slab_stride_, Qinv_, RP_, (int)npad_, eps,
 		                            nullptr, n_, nullptr, nullptr, stream_, hpart, emit ? Hx3_ : nullptr, ksW_, qx3_));
-		hx3_valid_ = emit;
-		gram_h_partials_ = hpart != nullptr;
+		state_.hx3_valid = emit;
+		state_.gram_h_partials = hpart != nullptr;
 	}
 	return ST_OK;
 }
@@ -1586,14 +1541,13 @@ Status Engine<T>::w_products(T* exchange) {
 			// a team of one: w_finish() sums the split-K slabs itself, as iterate_mu64() does -- no pass over the panel in between
 			// (nsNMF: the H update of h_step left the split image of S H; without it -- no H step since the factors were set -- the smoothed panel is packed here)
 			const T* Fh = H_;
-			if (alg_ == ALG_NSNMF && !(x3_ && hx3_valid_)) {
-				const T off = (T)prm_.theta / (T)(unsigned)r_;
-				HIPX(launch_smooth_panel<T>(H_, Hs_, RP_, r_, npad_, off, (T)((1.0 - (T)prm_.theta) + off), stream_));
+			if (alg_ == ALG_NSNMF && !(x3_ && state_.hx3_valid)) {
+				HIPX(smooth_panel(H_, Hs_, npad_));
 				Fh = Hs_;
 			}
-			if (sole_rank_ && gram_image_) return product_w(Fh, &rgH, nullptr, x3_ && hx3_valid_);
+			if (sole_rank_ && gram_image_) return product_w(Fh, &rgH, nullptr, x3_ && state_.hx3_valid);
 			// one K slice (short column shards) writes the exchange panel itself
-			if (Status s = product_w(Fh, &rgH, exchange, x3_ && hx3_valid_)) return s;
+			if (Status s = product_w(Fh, &rgH, exchange, x3_ && state_.hx3_valid)) return s;
 			if (planW_.splits > 1) HIPX(launch_reduce_slabs<T>(slabs_, planW_.splits, slab_stride_, exchange, (long)RP_ * mpad_, stream_));
 			return ST_OK;
 		}
@@ -1610,9 +1564,7 @@ Status Engine<T>::w_products(T* exchange) {
 	const T* Fh = H_;
 	if (alg_ == ALG_NSNMF) {
 		// the smoothed local columns S H_g enter both sums (AlgorithmNonSmoothNMF.h:194-197,213)
-		const T off = (T)prm_.theta / (T)(unsigned)r_;
-		const T diag = (T)((1.0 - (T)prm_.theta) + off);
-		HIPX(launch_smooth_panel<T>(H_, Hs_, RP_, r_, npad_, off, diag, stream_));
+		HIPX(smooth_panel(H_, Hs_, npad_));
 		Fh = Hs_;
 	}
 	HIPX(launch_gram<T>(Fh, RP_, n_, gram_parts_, gram_part_, ex_hht, stream_));
@@ -1639,7 +1591,7 @@ Status Engine<T>::w_finish(const T* exchange, bool compute_error) {
 		if (compute_error) HIPX(launch_trace_small<T>(ex_hht, G2_, RP_, r_, psR_, stream_));      // G2_: W^T W saved before the regulariser (h_step)
 		T* wpart = nullptr;
 		if constexpr (std::is_same<T, float>::value) { if (gram_from_update()) wpart = gramW_part_; }
-		wx3_valid_ = false;
+		state_.wx3_valid = false;
 		if (!ls_family) {
 			HIPX(launch_panel_update<T>(PANEL_MU, Wt_, exchange, 1, 0, ex_hht, RP_, (int)mpad_, eps, nullptr, m_, sumsq_part_, compute_error ? numW_ : nullptr, stream_,
 			                            wpart, nullptr, 0, qx3_));
@@ -1673,9 +1625,9 @@ Status Engine<T>::w_finish(const T* exchange, bool compute_error) {
 			// U_W on the all-reduced sums: one "slab" (the exchange panel), Q = the reduced H H^T  (a team of one: the split-K slabs as w_products left them)
 			if (sole_rank_ && gram_image_) { if (Status s = mu64_update(true, slabs_, planW_.splits, slab_stride_, ex_hht, compute_error)) return s; }
 			else if (Status s = mu64_update(true, exchange, 1, 0, ex_hht, compute_error)) return s;
-			wx3_valid_ = x3_;
+			state_.wx3_valid = x3_;
 			normalize_next_ = 1;
-			w_pending_ = true;
+			state_.w_pending = true;
 			if (compute_error) { if (Status s = fetch_error_terms(n_)) return s; }
 			return ST_OK;
 		}
@@ -1689,8 +1641,8 @@ Status Engine<T>::w_finish(const T* exchange, bool compute_error) {
 		HIPX(launch_trace_small<T>(ex_hht, wtw, RP_, r_, psR_, stream_, tri_trace_scale()));
 		if (Status s = fetch_error_terms(n_)) return s;
 	}
-	wx3_valid_ = false;
-	if (tri_) return tri_update_w(exchange, 1, 0, (sole_rank_ && qx3_holds_hht_) ? nullptr : ex_hht);
+	state_.wx3_valid = false;
+	if (tri_) return tri_update_w(exchange, 1, 0, (sole_rank_ && state_.qx3_holds_hht) ? nullptr : ex_hht);
 	HIPX(launch_panel_update<T>(PANEL_MU, Wt_, exchange, 1, 0, ex_hht, RP_, (int)mpad_, eps, nullptr, m_, sumsq_part_, nullptr, stream_, nullptr, nullptr, 0, qx3_));
 	HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, panel_update_parts(RP_, sizeof(T), (int)mpad_), stream_));
 	return ST_OK;
@@ -1711,9 +1663,9 @@ Status Engine<T>::w_finish_peers(const T* const* exchanges, int count, bool comp
 		const float* Q = hhts.p[0];
 		if (count > 1) { HIPX(launch_sum_peers(hhts, HHt_, RP_ * RP_, stream_)); Q = HHt_; }
 		if (Status s = mu64_update(true, nullptr, count, 0, Q, compute_error, &panels)) return s;
-		wx3_valid_ = x3_;
+		state_.wx3_valid = x3_;
 		normalize_next_ = 1;
-		w_pending_ = true;
+		state_.w_pending = true;
 		if (compute_error) { if (Status s = fetch_error_terms(n_)) return s; }
 	}
 	return ST_OK;
@@ -1763,9 +1715,9 @@ Status Engine<T>::w_normalize_rows(long row0, long rows, T* colsq) {
 		if (tri_) {
 			// the same pass leaves the bf16 fragments of the normalised rows for the next W^T V (unsmoothed: S is applied to the product's output)
 			HIPX(launch_finish_panel_bf16(Wt_, RP_, r_, row0, rows, colsq, colsq == colsq_ ? colsq_parts_ : 1, 0.0f, 1.0f, Wtb_, ksH_, stream_));
-			tri_rows_cover_ = row0 == 0 && rows == mpad_;
-			wtb_valid_ = tri_rows_cover_;
-			tri_gw_ready_ = false;
+			state_.tri_rows_cover = row0 == 0 && rows == mpad_;
+			state_.wtb_valid = state_.tri_rows_cover;
+			state_.tri_gw_ready = false;
 			return ST_OK;
 		}
 	}
@@ -1775,35 +1727,27 @@ Status Engine<T>::w_normalize_rows(long row0, long rows, T* colsq) {
 
 // ---- padded rank 256, bf16 product operands (kernels_tri.hip) ---------------------------------------------------------------------
 template <typename T>
-void Engine<T>::tri_smoothing(T* offdiag, T* diag) const {
-	if (alg_ == ALG_NSNMF) {
-		*offdiag = (T)prm_.theta / (T)(unsigned)r_;
-		*diag = (T)((1.0 - (T)prm_.theta) + *offdiag);
-	} else { *offdiag = 0; *diag = 1; }
-}
-
-template <typename T>
 Status Engine<T>::tri_prepare_w(GramReduceArgs* ride) {
 	if constexpr (std::is_same<T, float>::value) {
 		const bool wide = qx3_ != nullptr && panel_update_wide_available(RP_);
-		if (!wtb_valid_) {
+		if (!state_.wtb_valid) {
 			if (Status s = ensure_w_rows()) return s;      // (the fp32 rows of the other ranks first: engine.h, w_fragment_exchange)
 			// plain re-rounding of the panel as it lies (no smoothing, no normalisation: W is as the caller / the gather left it)
 			HIPX(launch_finish_panel_bf16(Wt_, RP_, r_, 0, mpad_, nullptr, 0, 0.0f, 1.0f, Wtb_, ksH_, stream_));
-			wtb_valid_ = true;
+			state_.wtb_valid = true;
 		}
-		if (!tri_gw_ready_) {
+		if (!state_.tri_gw_ready) {
 			// W^T W of the ROUNDED W (the matrix the product multiplies V with), as the reduction leaves it: Gw_raw_ and its split image are NOT normalised
 			// and not smoothed -- the H update applies D and S around its r x r product (PanelTriExtras::den_transform), the error term's trace applies D
 			// (AlgorithmNonSmoothNMF.h:201-202 wants the unsmoothed W^T W).  Round 3 first ran k_smooth_gram here (6.5 us) and a staging launch for D (4.7 us).
 			// The diagonal of the matrix IS the new pending scale: sums of squares of the rounded columns (one "staged" vector).
 			if (ride != nullptr && tri_ride_w_) {
 				// as passengers of the W^T V launch the caller is about to make: every consumer (H update, error trace, the next W update's pending scale) runs behind it
-				ride->tri_frags = Wtb_; ride->tri_ks = ksH_; ride->tri_partial = gram_tri_part_; ride->tri_counters = tri_ride_counters_; ride->G = Gw_raw_; ride->tri_x3 = wide ? qx3_ : nullptr; ride->tri_diag = tri_scale_from_gram_ ? colsq_ : nullptr;
-			} else HIPX(launch_gram_tri_bf16_image(Wtb_, RP_, ksH_, num_cus_, gram_tri_part_, Gw_raw_, wide ? qx3_ : nullptr, tri_scale_from_gram_ ? colsq_ : nullptr, num_cus_, stream_));
-			if (tri_scale_from_gram_) { colsq_parts_ = 1; tri_scale_from_gram_ = false; }
-			tri_gw_ready_ = true;
-			qx3_holds_g_ = wide;
+				ride->tri_frags = Wtb_; ride->tri_ks = ksH_; ride->tri_partial = gram_tri_part_; ride->tri_counters = tri_ride_counters_; ride->G = Gw_raw_; ride->tri_x3 = wide ? qx3_ : nullptr; ride->tri_diag = state_.tri_scale_from_gram ? colsq_ : nullptr;
+			} else HIPX(launch_gram_tri_bf16_image(Wtb_, RP_, ksH_, num_cus_, gram_tri_part_, Gw_raw_, wide ? qx3_ : nullptr, state_.tri_scale_from_gram ? colsq_ : nullptr, num_cus_, stream_));
+			if (state_.tri_scale_from_gram) { colsq_parts_ = 1; state_.tri_scale_from_gram = false; }
+			state_.tri_gw_ready = true;
+			state_.qx3_holds_g = wide;
 		}
 	}
 	return ST_OK;
@@ -1815,19 +1759,18 @@ Status Engine<T>::tri_prepare_w(GramReduceArgs* ride) {
 template <typename T>
 Status Engine<T>::tri_prepare_h(T* hht, bool local_q, GramReduceArgs* ride) {
 	if constexpr (std::is_same<T, float>::value) {
-		if (!hb_valid_) {
+		if (!state_.hb_valid) {
 			// H did not come from this engine's H update (set_factors / randomize between the two half-steps): one finishing pass makes the fragments
-			T off, diag;
-			tri_smoothing(&off, &diag);
+			const auto [off, diag] = smoothing_constants();
 			HIPX(launch_finish_panel_bf16(H_, RP_, r_, 0, npad_, nullptr, 0, off, diag, Hb_, ksW_, stream_));
-			hb_valid_ = true;
+			state_.hb_valid = true;
 		}
 		const bool image = local_q && qx3_ != nullptr && panel_update_wide_available(RP_);
 		if (image && ride != nullptr && tri_ride_h_) { ride->tri_frags = Hb_; ride->tri_ks = ksW_; ride->tri_partial = gram_tri_part_; ride->tri_counters = tri_ride_counters_; ride->G = hht; ride->tri_x3 = qx3_; ride->tri_diag = nullptr; }      // (rides in the V (S H)^T launch)
 		else if (image) HIPX(launch_gram_tri_bf16_image(Hb_, RP_, ksW_, num_cus_, gram_tri_part_, hht, qx3_, nullptr, num_cus_, stream_));
 		else HIPX(launch_gram_tri_bf16(Hb_, RP_, ksW_, num_cus_, gram_tri_part_, hht, nullptr, 0, num_cus_, stream_));
-		qx3_holds_g_ = false;
-		qx3_holds_hht_ = image;
+		state_.qx3_holds_g = false;
+		state_.qx3_holds_hht = image;
 	}
 	return ST_OK;
 }
@@ -1842,24 +1785,24 @@ Status Engine<T>::tri_update_w(const T* num, int S, long stride, const T* hht) {
 	if constexpr (std::is_same<T, float>::value) {
 		const T eps = std::numeric_limits<T>::epsilon();
 		const int parts = panel_update_parts(RP_, sizeof(T), (int)mpad_);
-		wx3_valid_ = false;
+		state_.wx3_valid = false;
 		PanelTriExtras ex;
-		if (tri_scale_pending_) { ex.old_colsq = colsq_; ex.old_colsq_parts = colsq_parts_; }
+		if (state_.tri_scale_pending) { ex.old_colsq = colsq_; ex.old_colsq_parts = colsq_parts_; }
 		ex.frag_out = Wtb_; ex.frag_KS = ksH_;
 		// the old rows enter W (SH)(SH)^T rounded to bf16: 63.7 -> 52.3 us, W's distance from the fp64 oracle unchanged (3.4e-4 vs 3.2e-4 after 10 iterations,
 		// 1.17e-3 vs 1.16e-3 after 40, tools/tri_accuracy.py); NMFAMD_TRI_FP32_DEN=1 keeps the six-term product
 		ex.old_as_bf16 = tri_w_den_bf16_;
 		HIPX(launch_panel_update<T>(PANEL_MU, Wt_, num, S, stride, hht, RP_, (int)mpad_, eps, nullptr, m_, nullptr, nullptr, stream_, nullptr, nullptr, 0, qx3_, &ex));
-		qx3_holds_g_ = qx3_holds_hht_ = false;
+		state_.qx3_holds_g = state_.qx3_holds_hht = false;
 		// The new pending scale comes out of the next Gram reduction (tri_prepare_w): d(c) = 1 / sqrt(sum of squares of the ROUNDED column c) -- the column
 		// norms of the matrix the product multiplies with; they differ from the fp32 norms by ~1e-5 relative (zero-mean rounding over m rows).  Every consumer
 		// (H update, next W update, error trace, materialize_w) runs after that reduction.
-		tri_scale_pending_ = true;
-		tri_scale_from_gram_ = true;
+		state_.tri_scale_pending = true;
+		state_.tri_scale_from_gram = true;
 		(void)parts;
-		wtb_valid_ = true;
-		tri_rows_cover_ = true;
-		tri_gw_ready_ = false;
+		state_.wtb_valid = true;
+		state_.tri_rows_cover = true;
+		state_.tri_gw_ready = false;
 		return ST_OK;
 	}
 	return ST_INVALID;
@@ -1894,21 +1837,20 @@ Status Engine<T>::iterate_fused32w(bool compute_error) {
 	if constexpr (std::is_same<T, float>::value) {
 		const float eps = std::numeric_limits<float>::epsilon();
 		const bool ns = alg_ == ALG_NSNMF;
-		const float off = ns ? (float)prm_.theta / (float)(unsigned)r_ : 0.f;
-		const float diag = ns ? (float)((1.0 - (float)prm_.theta) + off) : 1.f;
+		const auto [off, diag] = smoothing_constants();      // (the identity unless nsNMF)
 		const int norm_parts = panel_update_parts(RP_, sizeof(T), (int)mpad_);
-		const float* dscale = f32w_pending_ ? f32w_scale_ : nullptr;
+		const float* dscale = state_.f32w_pending ? f32w_scale_ : nullptr;
 		// H step
 		if (f32w_ride_h_ > 0) {
 			GramReduceArgs rg = {nullptr, 0, nullptr, nullptr, 0};
 			rg.wide_P = Wt_; rg.wide_len = m_; rg.wide_parts = f32w_ride_h_; rg.wide_partial = gram_part_;
-			if (Status s = product_h(Wt_, &rg, wx3_valid_)) return s;
-			HIPX(launch_gram_reduce_x3(gram_part_, f32w_ride_h_, RP_, G_, qx3_, f32w_pending_ ? sumsq_part_ : nullptr, norm_parts, f32w_scale_, stream_));
+			if (Status s = product_h(Wt_, &rg, state_.wx3_valid)) return s;
+			HIPX(launch_gram_reduce_x3(gram_part_, f32w_ride_h_, RP_, G_, qx3_, state_.f32w_pending ? sumsq_part_ : nullptr, norm_parts, f32w_scale_, stream_));
 		} else {
-			HIPX(launch_gram_wide_fused_f32(Wt_, RP_, m_, gram_parts_, gram_part_, G_, qx3_, f32w_pending_ ? sumsq_part_ : nullptr, norm_parts, f32w_scale_, stream_));
-			if (Status s = product_h(Wt_, nullptr, wx3_valid_)) return s;
+			HIPX(launch_gram_wide_fused_f32(Wt_, RP_, m_, gram_parts_, gram_part_, G_, qx3_, state_.f32w_pending ? sumsq_part_ : nullptr, norm_parts, f32w_scale_, stream_));
+			if (Status s = product_h(Wt_, nullptr, state_.wx3_valid)) return s;
 		}
-		wx3_valid_ = true;
+		state_.wx3_valid = true;
 		PanelFusedF32 fh;
 		fh.h_side = 1; fh.scale = dscale; fh.r = r_;
 		if (ns) { fh.smooth = 1; fh.off = off; fh.diag = diag; fh.smooth_out = Hs_; }
@@ -1926,7 +1868,7 @@ Status Engine<T>::iterate_fused32w(bool compute_error) {
 			HIPX(launch_gram_wide_fused_f32(Fh, RP_, n_, gram_parts_, gram_part_, HHt_, qx3_, nullptr, 0, nullptr, stream_));
 			if (Status s = product_w(Fh, nullptr, nullptr, true)) return s;
 		}
-		hx3_valid_ = !ns;
+		state_.hx3_valid = !ns;
 		// tr((S H)(S H)^T W^T W) with the W^T W of this iteration's H step (the pending scale applied on the way: D G D)
 		if (compute_error) HIPX(launch_trace_small<T>(HHt_, G_, RP_, r_, psR_, stream_, nullptr, dscale));
 		PanelFusedF32 fw;
@@ -1934,9 +1876,9 @@ Status Engine<T>::iterate_fused32w(bool compute_error) {
 		fw.x3_out = Wx3_; fw.x3_ks = ksH_;
 		HIPX(launch_panel_update_wide_f32(PANEL_MU, Wt_, slabs_, planW_.splits, slab_stride_, nullptr, RP_, (int)mpad_, eps, nullptr, m_, sumsq_part_, nullptr,
 		                                  stream_, qx3_, nullptr, &fw));
-		f32w_pending_ = true;
-		wx3_valid_ = true;          // (of the panel as it lies)
-		gram_w_ready_ = false;
+		state_.f32w_pending = true;
+		state_.wx3_valid = true;          // (of the panel as it lies)
+		state_.gram_w_ready = false;
 		if (compute_error) { if (Status s = fetch_error_terms(n_)) return s; }
 	}
 	return ST_OK;
@@ -1966,7 +1908,7 @@ Status Engine<T>::fused64_product_h() {
 		struct RideGuard { const GramRideF64*& p; ~RideGuard() { p = nullptr; } } guard{ride64_};
 		GramRideF64 gw = {};
 		gw.P = Wt_; gw.len = m_; gw.slices = f64_slices_h_; gw.partial = f64_partial_; gw.counters = f64_counters_; gw.G = G_;
-		gw.sumsq_part = f64_pending_ ? sumsq_part_ : nullptr; gw.sumsq_parts = panel_update_parts(RP_, sizeof(T), (int)mpad_); gw.scale_out = f64_scale_;
+		gw.sumsq_part = state_.f64_pending ? sumsq_part_ : nullptr; gw.sumsq_parts = panel_update_parts(RP_, sizeof(T), (int)mpad_); gw.scale_out = f64_scale_;
 		if (const char* e = tuning_env("NMFAMD_RIDE64_STOP")) gw.stop = std::atoi(e);
 		gw.stamps = f64_stamps_;
 		gw.items = f64_items_h_;
@@ -1981,8 +1923,7 @@ Status Engine<T>::iterate_fused64(bool compute_error) {
 	if constexpr (std::is_same<T, double>::value) {
 		const double eps = std::numeric_limits<double>::epsilon();
 		const bool ns = alg_ == ALG_NSNMF;
-		const double off = ns ? prm_.theta / (double)(unsigned)r_ : 0.0;
-		const double diag = ns ? (1.0 - prm_.theta) + off : 1.0;
+		const auto [off, diag] = smoothing_constants();      // (the identity unless nsNMF)
 		struct RideGuard { const GramRideF64*& p; ~RideGuard() { p = nullptr; } } guard{ride64_};
 		// Error iterations of a single engine: the H update writes its n terms and the W update's trace workgroups their r terms straight into the pinned host
 		// buffer (its device address): no k_trace_small launch, no copy launch (as iterate_mu64 does since round 5) -- 1.2 us per iteration on average at the
@@ -1993,11 +1934,11 @@ Status Engine<T>::iterate_fused64(bool compute_error) {
 		T* const ps_n = ps_direct_ ? pin_psN_dev_ : psN_;
 		T* const ps_r = ps_direct_ ? pin_psN_dev_ + ps_stride_ : psR_;
 		// 1 (already enqueued by begin_next_iteration() behind the previous error iteration: nothing has touched W, V or the scratch since)
-		if (f64_product_ahead_) f64_product_ahead_ = false;
+		if (state_.f64_product_ahead) state_.f64_product_ahead = false;
 		else if (Status s = fused64_product_h()) return s;
 		// 2
 		PanelFusedF64 fh = {};
-		const double* dscale = f64_pending_ ? f64_scale_ : nullptr;
+		const double* dscale = state_.f64_pending ? f64_scale_ : nullptr;
 		fh.h_side = (dscale != nullptr || ns) ? 1 : 0;      // (a normalised W and no smoothing: G_ is W^T W as the update needs it)
 		fh.scale = dscale; fh.r = r_;
 		if (ns) { fh.smooth = 1; fh.off = off; fh.diag = diag; fh.smooth_out = Hs_; }
@@ -2023,9 +1964,9 @@ Status Engine<T>::iterate_fused64(bool compute_error) {
 		fw.stamps = f64_stamps_ != nullptr ? f64_stamps_ + 3l * 4096 * 8 : nullptr;
 		if (RP_ == 64) HIPX(launch_panel_update64_f64(PANEL_MU, Wt_, slabs_, planW_.splits, slab_stride_, HHt_, (int)mpad_, eps, nullptr, m_, sumsq_part_, nullptr, stream_, &fw));
 		else HIPX(launch_panel_update_wide_f64(PANEL_MU, Wt_, slabs_, planW_.splits, slab_stride_, HHt_, RP_, (int)mpad_, eps, nullptr, m_, sumsq_part_, nullptr, stream_, &fw));
-		f64_pending_ = true;
-		gram_w_ready_ = false;
-		hx3_valid_ = false; wx3_valid_ = false;
+		state_.f64_pending = true;
+		state_.gram_w_ready = false;
+		state_.hx3_valid = false; state_.wx3_valid = false;
 		if (compute_error) { if (Status s = fetch_error_terms(n_)) return s; }
 	}
 	return ST_OK;
@@ -2058,12 +1999,12 @@ Status Engine<T>::normalize_w(bool from_gram_partials, int norm_parts) {
 			// the scaling pass also leaves the split image of the normalised W for the next W^T V
 			HIPX(launch_mu64_apply_scale(Wt_, (int)mpad_, scale_, stream_, x3_ ? Wx3_ : nullptr, ksH_));
 			}
-			wx3_valid_ = x3_;
-			gram_w_ready_ = true;
+			state_.wx3_valid = x3_;
+			state_.gram_w_ready = true;
 			return ST_OK;
 		}
 	}
-	gram_w_ready_ = false;
+	state_.gram_w_ready = false;
 	HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, norm_parts, stream_));
 	return ST_OK;
 }
@@ -2071,10 +2012,10 @@ Status Engine<T>::normalize_w(bool from_gram_partials, int norm_parts) {
 template <typename T>
 Status Engine<T>::ensure_w_rows() {
 	// (row-block sharded run with the fragment exchange: whoever wants the WHOLE fp32 panel gets the other ranks' rows first -- a collective, engine.h)
-	if (w_rows_stale_) {
+	if (state_.w_rows_stale) {
 		if (!w_gather_hook_) { last_error_ = "the fp32 rows of the other ranks' blocks were not gathered (the sharded run that owns the exchange is closed)"; return ST_INVALID; }
 		if (Status s = w_gather_hook_()) return s;
-		w_rows_stale_ = false;
+		state_.w_rows_stale = false;
 	}
 	return ST_OK;
 }
@@ -2082,45 +2023,45 @@ Status Engine<T>::ensure_w_rows() {
 template <typename T>
 Status Engine<T>::materialize_w(bool whole_panel) {
 	if (whole_panel) { if (Status s = ensure_w_rows()) return s; }
-	if (f32w_pending_) {
+	if (state_.f32w_pending) {
 		// the fused fp32 iteration at padded ranks >= 128 left W unnormalised (and the split image of THAT panel in Wx3_)
 		HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, panel_update_parts(RP_, sizeof(T), (int)mpad_), stream_));
-		f32w_pending_ = false;
-		wx3_valid_ = false;
-		gram_w_ready_ = false;
+		state_.f32w_pending = false;
+		state_.wx3_valid = false;
+		state_.gram_w_ready = false;
 	}
-	if (kl_scale_pending_) {
+	if (state_.kl_scale_pending) {
 		// the KL iteration left W unnormalised (iterate_kl): the pass it skipped
 		HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, (int)(mpad_ / 128), stream_));
-		kl_scale_pending_ = false;
+		state_.kl_scale_pending = false;
 	}
-	if (f64_pending_) {
+	if (state_.f64_pending) {
 		// the fused double-precision iteration left W unnormalised: the second half of kernel::normalizeColumns, as the generic iteration runs it after every W update
 		HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, panel_update_parts(RP_, sizeof(T), (int)mpad_), stream_));
-		f64_pending_ = false;
-		f64_product_ahead_ = false;      // (an ahead launch multiplied with the unnormalised panel and its pending scale)
-		gram_w_ready_ = false;
+		state_.f64_pending = false;
+		state_.f64_product_ahead = false;      // (an ahead launch multiplied with the unnormalised panel and its pending scale)
+		state_.gram_w_ready = false;
 	}
 	if constexpr (std::is_same<T, float>::value) {
-		if (w_pending_) {
+		if (state_.w_pending) {
 			// column norms from the partial Grams of the unnormalised W, then W <- W diag(scale)
 			GramReduceArgs rg = gram_args(true, G2_, scale_, 1);
 			if (Status s = standalone_gram(rg)) return s;
 			HIPX(launch_mu64_apply_scale(Wt_, (int)mpad_, scale_, stream_));
-			w_pending_ = false;
-			fused_ready_ = false;
-			h_product_ahead_ = false; f64_product_ahead_ = false;
-			wx3_valid_ = false;
+			state_.w_pending = false;
+			state_.fused_ready = false;
+			state_.h_product_ahead = false; state_.f64_product_ahead = false;
+			state_.wx3_valid = false;
 		}
-		if (tri_scale_pending_) {
-			if (tri_scale_from_gram_) { if (Status s = tri_prepare_w()) return s; }      // (the scale of the last W update comes out of the Gram reduction)
+		if (state_.tri_scale_pending) {
+			if (state_.tri_scale_from_gram) { if (Status s = tri_prepare_w()) return s; }      // (the scale of the last W update comes out of the Gram reduction)
 			// rank-256 bf16 path: W <- W diag(d), d from the staged sums of squares; the fragments (of the unscaled panel) are re-made on demand, the Gram matrices already
 			// describe the normalised W
 			HIPX(launch_scale_panel_tri(Wt_, RP_, mpad_, colsq_, colsq_parts_, nullptr, stream_));
-			tri_scale_pending_ = false;
-			wtb_valid_ = false;
-			tri_gw_ready_ = false;        // (Gw_raw_ and its image describe the unscaled panel)
-			qx3_holds_g_ = false;
+			state_.tri_scale_pending = false;
+			state_.wtb_valid = false;
+			state_.tri_gw_ready = false;        // (Gw_raw_ and its image describe the unscaled panel)
+			state_.qx3_holds_g = false;
 		}
 	}
 	return ST_OK;
@@ -2131,8 +2072,8 @@ template <typename T>
 Status Engine<T>::iterate_onepass(bool compute_error) {
 #ifdef NMFAMD_DIAG_BUILD
 	if constexpr (std::is_same<T, float>::value) {
-		if (!fused_ready_) { normalize_next_ = 0; fused_ready_ = true; }
-		if (!wx3_valid_) { HIPX(launch_pack_panel_x3(Wt_, RP_, m_, Wx3_, ksH_, stream_)); wx3_valid_ = true; }
+		if (!state_.fused_ready) { normalize_next_ = 0; state_.fused_ready = true; }
+		if (!state_.wx3_valid) { HIPX(launch_pack_panel_x3(Wt_, RP_, m_, Wx3_, ksH_, stream_)); state_.wx3_valid = true; }
 		GramReduceArgs rgW = gram_args(true, G_, scale_, normalize_next_);
 		rgW.ksplit = 0; rgW.spread = 0; rgW.G = G_;       // (the persistent launch reads the finished matrix)
 		if (Status s = standalone_gram(rgW)) return s;
@@ -2159,10 +2100,10 @@ Status Engine<T>::iterate_onepass(bool compute_error) {
 		HIPX(launch_reduce_partials<float>(op_hh_part_, ONEPASS_XCDS * ONEPASS_GROUP, 4096, HHt_, 4096, stream_));
 		if (compute_error) HIPX(launch_reduce_partials<float>(op_ps4_, 4, npad_, psN_, n_, stream_));   // the four owner waves' parts of the per-column terms
 		if (Status s = mu64_update(true, op_slabs_, ONEPASS_XCDS, (long)RP_ * mpad_, HHt_, compute_error)) return s;
-		wx3_valid_ = x3_;
-		hx3_valid_ = false;
+		state_.wx3_valid = x3_;
+		state_.hx3_valid = false;
 		normalize_next_ = 1;
-		w_pending_ = true;
+		state_.w_pending = true;
 		if (compute_error) {
 			if (Status s = fetch_error_terms(n_)) return s;
 			if (Status s = onepass_check()) return s;
@@ -2209,22 +2150,22 @@ Status Engine<T>::iterate_mu64(bool compute_error) {
 		ps_direct_ = compute_error && gram_image_ && !error_terms_stay_ && pin_psN_dev_ != nullptr && !no_direct;
 		if (ps_direct_) finalize_error(false);
 		struct DirectGuard { bool& f; ~DirectGuard() { f = false; } } direct_guard{ps_direct_};
-		if (!fused_ready_) {
+		if (!state_.fused_ready) {
 			if (!gram_image_) HIPX(launch_mu64_gram_partials(Wt_, (int)mpad_, gramW_part_, stream_));
 			normalize_next_ = 0;
-			fused_ready_ = true;
+			state_.fused_ready = true;
 		}
 		GramReduceArgs rgW = gram_args(true, G_, scale_, normalize_next_);
-		if (h_product_ahead_) h_product_ahead_ = false;      // (begin_next_iteration() enqueued exactly this launch)
-		else if (Status s = product_h(Wt_, &rgW, x3_ && wx3_valid_)) return s;
+		if (state_.h_product_ahead) state_.h_product_ahead = false;      // (begin_next_iteration() enqueued exactly this launch)
+		else if (Status s = product_h(Wt_, &rgW, x3_ && state_.wx3_valid)) return s;
 		if (Status s = mu64_update(false, slabs_, planH_.splits, slab_stride_, rgW.ksplit > 1 ? reinterpret_cast<const T*>(Gpart_) : G_, compute_error)) return s;
 		GramReduceArgs rgH = gram_args(false, HHt_, nullptr, 0);
 		if (Status s = product_w(H_, &rgH, nullptr, x3_)) return s;
 		if (Status s = mu64_update(true, slabs_, planW_.splits, slab_stride_, HHt_, compute_error)) return s;
-		wx3_valid_ = x3_;
-		hx3_valid_ = false;
+		state_.wx3_valid = x3_;
+		state_.hx3_valid = false;
 		normalize_next_ = 1;
-		w_pending_ = true;
+		state_.w_pending = true;
 		if (compute_error) {
 			if (Status s = fetch_error_terms(n_)) return s;
 		}
@@ -2236,17 +2177,17 @@ template <typename T>
 Status Engine<T>::begin_next_iteration() {
 	if constexpr (std::is_same<T, double>::value) {
 		// the fused double-precision iteration: its first launch writes the split-K slabs, G_ and the scale vector -- scratch the next iterate() overwrites anyway
-		if (!fused64_capable() || f64_partial_ == nullptr || !f64_pending_ || f64_product_ahead_ || prm_.divergence != 0) return ST_OK;
+		if (!fused64_capable() || f64_partial_ == nullptr || !state_.f64_pending || state_.f64_product_ahead || prm_.divergence != 0) return ST_OK;
 		const bool sampled = timing_now_;
 		timing_now_ = false;
 		const Status s = fused64_product_h();
 		timing_now_ = sampled;
 		if (s != ST_OK) return s;
-		f64_product_ahead_ = true;
+		state_.f64_product_ahead = true;
 		return ST_OK;
 	}
 	if constexpr (std::is_same<T, float>::value) {
-		if (!fused_capable() || one_pass_ || !fused_ready_ || h_product_ahead_ || prm_.divergence != 0 || !x3_ || !wx3_valid_) return ST_OK;
+		if (!fused_capable() || one_pass_ || !state_.fused_ready || state_.h_product_ahead || prm_.divergence != 0 || !x3_ || !state_.wx3_valid) return ST_OK;
 		GramReduceArgs rgW = gram_args(true, G_, scale_, normalize_next_);
 		// (not sampled: the launch belongs to the NEXT iteration -- or to none, when the threshold ends the run here)
 		const bool sampled = timing_now_;
@@ -2254,7 +2195,7 @@ Status Engine<T>::begin_next_iteration() {
 		const Status s = product_h(Wt_, &rgW, true);
 		timing_now_ = sampled;
 		if (s != ST_OK) return s;
-		h_product_ahead_ = true;
+		state_.h_product_ahead = true;
 	}
 	return ST_OK;
 }
@@ -2404,9 +2345,7 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 			if (Status s = tri_prepare_h(HHt_, true, !constant_w ? &tri_ride : nullptr)) return s;
 			hht_done = true;
 		} else if (alg_ == ALG_NSNMF) {
-			const T off = (T)prm_.theta / (T)(unsigned)r_;
-			const T diag = (T)((1.0 - (T)prm_.theta) + off);
-			HIPX(launch_smooth_panel<T>(H_, Hs_, RP_, r_, npad_, off, diag, stream_));
+			HIPX(smooth_panel(H_, Hs_, npad_));
 			Fh = Hs_;
 		}
 		// GDCLS at padded rank 64 on the split-operand path (round 4): H H^T only feeds the W update, which runs AFTER the product against V -- so it is taken from
@@ -2414,8 +2353,8 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 		// matrices out of the H update.  (The ALS family inverts H H^T beside the product and needs it before.)
 		bool hht_rides = false;
 		if constexpr (std::is_same<T, float>::value) {
-			hht_rides = !constant_w && alg_ == ALG_GDCLS && x3_ && hx3_valid_ && Fh == H_ && RP_ == 64 && !gram_h_partials_ && passengers_ride(planWx_);
-			if (!hht_rides && gram_h_partials_ && Fh == H_) {
+			hht_rides = !constant_w && alg_ == ALG_GDCLS && x3_ && state_.hx3_valid && Fh == H_ && RP_ == 64 && !state_.gram_h_partials && passengers_ride(planWx_);
+			if (!hht_rides && state_.gram_h_partials && Fh == H_) {
 				// H H^T from the partial Gram matrices the H update left behind
 				HIPX(launch_gram64_from_partials(gramH_part_, (int)(npad_ / 64), HHt_, nullptr, stream_));
 				hht_done = true;
@@ -2449,7 +2388,7 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				if constexpr (std::is_same<T, float>::value) {
 					GramReduceArgs rg = {nullptr, 0, nullptr, nullptr, 0};
 					rg.inv_a = HHt_; rg.inv_out = Qinv_; rg.inv_offdiag = offW; rg.inv_diag = diagW; rg.inv_r = r_;
-					if (Status s = product_w(Fh, &rg, nullptr, x3_ && hx3_valid_ && Fh == H_)) return s;
+					if (Status s = product_w(Fh, &rg, nullptr, x3_ && state_.hx3_valid && Fh == H_)) return s;
 				}
 			} else if (hht_rides) {
 				if constexpr (std::is_same<T, float>::value) {
@@ -2460,7 +2399,7 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 					if (compute_error) HIPX(launch_trace_small<T>(HHt_, G2_, RP_, r_, psR_, stream_, tri_trace_scale()));
 				}
 			} else {
-				if (Status s = product_w(Fh, tri_ride.tri_frags != nullptr ? &tri_ride : nullptr, nullptr, tri_ || (x3_ && hx3_valid_ && Fh == H_))) return s;
+				if (Status s = product_w(Fh, tri_ride.tri_frags != nullptr ? &tri_ride : nullptr, nullptr, tri_ || (x3_ && state_.hx3_valid && Fh == H_))) return s;
 				// (rank 256, H H^T rode in that launch: the error term's trace of H H^T against the unsmoothed W^T W of this iteration's H step, AlgorithmNonSmoothNMF.h:201-202)
 				if (compute_error && tri_ride.tri_frags != nullptr) HIPX(launch_trace_small<T>(HHt_, reinterpret_cast<const T*>(Gw_raw_), RP_, r_, psR_, stream_, tri_trace_scale()));
 			}
@@ -2468,8 +2407,8 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				// coordinate sweep over every row of W against H H^T and the summed slabs of V H^T, then the column normalisation that keeps W H:
 				// W(:, c) / d(c), H(c, :) d(c) -- applied to H at once, no pending scale.  With a penalty there is no normalisation: it keeps W H but not the
 				// penalty terms, and without it one iteration is one pass of scikit-learn's coordinate descent (docs/HALS.md).
-				wx3_valid_ = false;
-				gram_w_ready_ = false;
+				state_.wx3_valid = false;
+				state_.gram_w_ready = false;
 				if (prm_.hals_penalised()) {
 					if (Status s = family_step(true, Wt_, HHt_, S, (int)mpad_, m_, nullptr, nullptr, (T)prm_.l1W, (T)prm_.l2W)) return s;
 				} else {
@@ -2480,9 +2419,9 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				const bool gd_err = alg_ == ALG_GDCLS && compute_error;
 				T* wpart = nullptr;
 				if constexpr (std::is_same<T, float>::value) { if (gram_from_update()) wpart = gramW_part_; }
-				wx3_valid_ = false;
+				state_.wx3_valid = false;
 				if (tri_) {
-					if (Status s = tri_update_w(slabs_, S, slab_stride_, qx3_holds_hht_ ? nullptr : HHt_)) return s;
+					if (Status s = tri_update_w(slabs_, S, slab_stride_, state_.qx3_holds_hht ? nullptr : HHt_)) return s;
 				} else {
 					HIPX(launch_panel_update<T>(PANEL_MU, Wt_, slabs_, S, slab_stride_, HHt_, RP_, (int)mpad_, eps,
 					                            nullptr, m_, sumsq_part_, gd_err ? numW_ : nullptr, stream_, wpart, nullptr, 0, qx3_));
@@ -2498,7 +2437,7 @@ Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 				if (compute_error) HIPX(hipMemcpyAsync(Wold_, Wt_, sizeof(T) * (size_t)RP_ * mpad_, hipMemcpyDeviceToDevice, stream_));
 				T* wpart = nullptr;
 				if constexpr (std::is_same<T, float>::value) { if (gram_from_update()) wpart = gramW_part_; }
-				wx3_valid_ = false;
+				state_.wx3_valid = false;
 				HIPX(launch_panel_update<T>(PANEL_LS, Wt_, slabs_, S, slab_stride_, Qinv_, RP_, (int)mpad_, eps,
 				                            nullptr, m_, sumsq_part_, compute_error ? numW_ : nullptr, stream_, wpart, nullptr, 0, qx3_));
 				if (compute_error) {
@@ -2667,7 +2606,7 @@ Status Engine<T>::iterate_kl(bool compute_error) {
 	// (a_scale), the H update's numerator is D (Wt^T Q), the W update reads its old rows as Wt D.  materialize_w() folds the scale in for everybody else.
 	const bool keep_pending = !two_pass && std::getenv("NMFAMD_NO_FUSED_MU") == nullptr;
 	if (!keep_pending) { if (Status st = materialize_w()) return st; }
-	const T* dsc = kl_scale_pending_ ? kl_scale_ : nullptr;
+	const T* dsc = state_.kl_scale_pending ? kl_scale_ : nullptr;
 	// H step (no error terms here: they refer to the pair (W_{k-1}, H_k) of the second evaluation).  One pass over the CSC
 	// image: quotient and numerator W^T Q together, one gathered row of W per stored entry (kernels_sparse.hip, k_kl_fused).
 	record_begin();
@@ -2681,7 +2620,7 @@ Status Engine<T>::iterate_kl(bool compute_error) {
 	}
 	record_end();
 	// the column sums of W: from the partial sums its last update left (round 4), or by a pass over the panel when W was set from outside
-	if (!kl_sw_ready_) HIPX(launch_panel_rowsum<T>(Wt_, RP_, (int)mpad_, rowsum_part_, sW_, stream_));
+	if (!state_.kl_sw_ready) HIPX(launch_panel_rowsum<T>(Wt_, RP_, (int)mpad_, rowsum_part_, sW_, stream_));
 	// ... and the update of H leaves the partial row sums of the NEW H (the W step's denominators) in rowsum_part_: one small launch instead of a pass over H
 	if (!two_pass && kl_blocks_h_ > 1) HIPX(launch_kl_update<T>(H_, kl_part_, sW_, RP_, (int)npad_, eps, nullptr, stream_, kl_blocks_h_, (long)RP_ * npad_, rowsum_part_, dsc));
 	else HIPX(launch_kl_update<T>(H_, slabs_, sW_, RP_, (int)npad_, eps, nullptr, stream_, 1, 0, rowsum_part_, dsc));
@@ -2727,8 +2666,8 @@ Status Engine<T>::iterate_kl(bool compute_error) {
 	// colsum of the NORMALISED W = (sum of the new column) / (its norm), both from the update's per-workgroup partials (norm_parts = mpad / 128 of each); and the
 	// pending scale itself
 	HIPX(launch_kl_sums<T>(rowsum_part_, sumsq_part_, norm_parts, RP_, sW_, stream_, keep_pending ? kl_scale_ : nullptr));
-	kl_sw_ready_ = true;
-	if (keep_pending) kl_scale_pending_ = true;
+	state_.kl_sw_ready = true;
+	if (keep_pending) state_.kl_scale_pending = true;
 	else HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, norm_parts, stream_));
 	return ST_OK;
 }
@@ -2795,7 +2734,7 @@ Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
 	const T l1W = (T)prm_.l1W, l1H = (T)prm_.l1H, l2W = (T)prm_.l2W, l2H = (T)prm_.l2H;
 	const int partsH = (int)(npad_ / 128), partsW = (int)(mpad_ / 128);
 	// H step: X = the column-major image (row j of X = column j of V)
-	if (kl && !kl_sw_ready_) { HIPX(launch_panel_rowsum<T>(Wt_, RP_, (int)mpad_, rowsum_part_, sW_, stream_)); kl_sw_ready_ = true; }
+	if (kl && !state_.kl_sw_ready) { HIPX(launch_panel_rowsum<T>(Wt_, RP_, (int)mpad_, rowsum_part_, sW_, stream_)); state_.kl_sw_ready = true; }
 	record_begin();
 	if (weighted_)
 		HIPX(launch_beta_fused_weighted<T>(V_, Om_, mpad_, H_, Wt_, RP_, beta, true, false, eps, betaH_, slabs_, beta_den_, slab_stride_, (T*)nullptr, (T*)nullptr, 0,
@@ -2837,7 +2776,7 @@ Status Engine<T>::iterate_beta(bool compute_error, bool constant_w) {
 	if (kl) {
 		// as iterate_kl: the column sums of the NORMALISED W from the update's partials, then the normalisation itself; penalised: the sums of W as it is
 		HIPX(launch_kl_sums<T>(rowsum_part_, penalised ? (const T*)nullptr : sumsq_part_, partsW, RP_, sW_, stream_));
-		kl_sw_ready_ = true;
+		state_.kl_sw_ready = true;
 		if (!penalised) HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, sumsq_part_, partsW, stream_));
 	} else if (!penalised) {
 		// (the weighted beta = 1: the columns of W normalised, H not rescaled, as above -- without the column sums nobody reads)
@@ -2862,8 +2801,8 @@ Status Engine<T>::iterate_beta_minibatch(bool compute_error) {
 	const bool kl = beta == 1;
 	const T l1W = (T)prm_.l1W, l1H = (T)prm_.l1H, l2W = (T)prm_.l2W, l2H = (T)prm_.l2H;
 	const int partsW = (int)(mpad_ / BETA_ROWS_PER_WG);
-	if (online_stale_) { HIPX(launch_beta_online_reset<T>(Wt_, online_A_, online_B_, (long)RP_ * mpad_, stream_)); online_stale_ = false; }
-	if (kl && !kl_sw_ready_) { HIPX(launch_panel_rowsum<T>(Wt_, RP_, (int)mpad_, rowsum_part_, sW_, stream_)); kl_sw_ready_ = true; }
+	if (state_.online_stale) { HIPX(launch_beta_online_reset<T>(Wt_, online_A_, online_B_, (long)RP_ * mpad_, stream_)); state_.online_stale = false; }
+	if (kl && !state_.kl_sw_ready) { HIPX(launch_panel_rowsum<T>(Wt_, RP_, (int)mpad_, rowsum_part_, sW_, stream_)); state_.kl_sw_ready = true; }
 	for (long c0 = 0; c0 < n_; c0 += batch_) {
 		const int blen = (int)std::min<long>(batch_, n_ - c0), bpad = (int)pad128(blen);
 		const bool full = blen == batch_;
@@ -2985,7 +2924,7 @@ Status Engine<T>::kl_w_finish(const T* exchange, bool compute_error) {
 	// the error terms in the exchange buffer were (or were not) produced by w_products() under the flag h_step() latched: a caller asking for the
 	// other thing here would read terms that are not there
 	if (compute_error != kl_err_iter_) { last_error_ = "kl: w_finish(compute_error) differs from the h_step(compute_error) of the same iteration"; return ST_INVALID; }
-	kl_sw_ready_ = false;
+	state_.kl_sw_ready = false;
 	const T eps = std::numeric_limits<T>::epsilon();
 	const int norm_parts = (int)(mpad_ / 128);
 	const T* num = exchange;

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "device_buffers.h"
+#include "engine_state.h"
 #include "kernels.h"
 
 namespace nmfamd {
@@ -223,11 +224,11 @@ public:
 	Status upload_dense_device(const T* V, long ld, int layout);
 	Status upload_dense_weighted_device(const T* V, long ldv, int layout_v, const T* Omega, long ldo, int layout_o);
 
-	// W: host m x r (ld), H: host r x n (ld).  Either pointer may be null (leave as is).
+	// W: host m x r (ld), H: host r x n (ld).  Either pointer may be null (leave as is).  PanelState: factors_touched, then w_set / h_set for the factor given.
 	Status set_factors(const T* W, long ldw, const T* H, long ldh);
 	Status get_factors(T* W, long ldw, T* H, long ldh);   // nsNMF returns W S, like the reference
 	// ... to and from DEVICE memory, in either layout (W: m x r, H: r x n; 0 column-major, 1 row-major), with the semantics of the host forms (a null pointer leaves
-	// that factor; what set_factors invalidates; nsNMF returns W S) and the pointer checks and the ordering of upload_dense_device: hipDeviceSynchronize() before the
+	// that factor; the transitions of set_factors; nsNMF returns W S) and the pointer checks and the ordering of upload_dense_device: hipDeviceSynchronize() before the
 	// first access, return after the engine's stream is idle -- so any stream may have written the input and any stream may read the output.  get writes the m x r /
 	// r x n block only: the bytes in the gap of ld stay as they are.
 	Status set_factors_device(const T* W, long ldw, int layout_w, const T* H, long ldh, int layout_h);
@@ -238,7 +239,7 @@ public:
 	// The W^T V launch (and its Gram passengers) of the NEXT iteration, enqueued ahead of it: it writes the split-K slabs, G and the column scale -- scratch the
 	// next iterate() would overwrite anyway -- so a caller that is about to block on this iteration's error value (nmfgpu::compute: the threshold test decides
 	// whether there is a next iteration) keeps the device busy meanwhile.  Rank-64 fused path only; a no-op elsewhere.  The next iterate() skips the launch;
-	// set_factors / randomize / upload in between make it void.
+	// a W or a V from outside in between makes it void (PanelState::w_set, v_replaced; a new H alone does not: the launch reads W and V).
 	Status begin_next_iteration();
 	// One iteration.  With compute_error the frobenius()/rmsd() values are refreshed (host sync).
 	Status iterate(bool compute_error, bool constant_w);
@@ -293,7 +294,7 @@ public:
 	// blocks of every rank have been gathered into w_panel(), w_rows_replaced() drops what was derived from the old W.
 	Status w_update_rows(const T* num_rows, const T* hht, long row0, long rows, bool compute_error, T* colsq);
 	Status w_normalize_rows(long row0, long rows, T* colsq);
-	void w_rows_replaced() { kl_sw_ready_ = false; kl_scale_pending_ = false; fused_ready_ = false; w_pending_ = false; f32w_pending_ = false; f64_pending_ = false; f64_product_ahead_ = false; h_product_ahead_ = false; gram_w_ready_ = false; wx3_valid_ = false; tri_gw_ready_ = false; qx3_holds_g_ = false; tri_scale_pending_ = false; tri_scale_from_gram_ = false; if (!tri_rows_cover_) wtb_valid_ = false; }
+	void w_rows_replaced() { state_.w_rows_replaced(); }
 	T* w_panel() { return Wt_; }
 	double beta() const { return beta_; }      // the beta of a dense divergence engine, in the precision of T
 	int kl_blocks(bool w_step) const { return prm_.divergence != 0 && !beta_dense_ ? (w_step ? kl_blocks_w_ : kl_blocks_h_) : 0; }
@@ -312,13 +313,10 @@ public:
 	void* w_fragments() { return Wtb_; }
 	long w_fragment_words_per_row() const { return RP_ / 2; }
 	// the fragments of every rank's rows have been gathered into w_fragments(); stale: the fp32 rows of the other ranks were not
-	void w_fragments_gathered(bool stale) {
-		kl_sw_ready_ = false; kl_scale_pending_ = false; fused_ready_ = false; w_pending_ = false; f32w_pending_ = false; f64_pending_ = false; f64_product_ahead_ = false; h_product_ahead_ = false; gram_w_ready_ = false; wx3_valid_ = false; tri_gw_ready_ = false; qx3_holds_g_ = false;
-		tri_scale_pending_ = false; tri_scale_from_gram_ = false; wtb_valid_ = true; w_rows_stale_ = stale;
-	}
+	void w_fragments_gathered(bool stale) { state_.w_fragments_gathered(stale); }
 	void set_w_gather_hook(std::function<Status()> hook) { w_gather_hook_ = std::move(hook); }
-	void w_rows_gathered() { w_rows_stale_ = false; }
-	bool w_rows_stale() const { return w_rows_stale_; }
+	void w_rows_gathered() { state_.w_rows_stale = false; }
+	bool w_rows_stale() const { return state_.w_rows_stale; }
 	Status materialize() { return materialize_w(); }
 	// error terms of the last error iteration (host copies): n_local per-column terms and r terms
 	const std::vector<T>& terms_htwtv() { finalize_error(false); return h_psN_; }
@@ -398,7 +396,11 @@ private:
 	Status normal_inverse_join();
 	bool passengers_ride(const FactorProductPlan& plan) const; // split-operand product, rank 64: the Gram passengers find CUs beside the product blocks
 	bool inverse_rides(const FactorProductPlan& plan) const;   // the inverse can be a passenger workgroup of the product launch
-	Status finish_upload(T* Vcol);
+	Status finish_upload(T* Vcol);                   // (its first statement is PanelState::v_replaced)
+	template <typename Fill> Status upload_image(bool zeroed, Fill fill);   // every dense upload behind its checks: staging image, fill(T* Vcol), finish_upload, release; a new input path is a fill
+	Status refuse_weighted(int flags);               // the three refusals of a weighted upload by IMPORT_* flags, in their precedence; ST_OK if none
+	Status finish_weighted_upload(double sum_w);     // ... and its tail: finish_upload(V_), Omt_, the synchronisation, sum_w_, beta_uploaded_
+	Status export_panel_w(bool want_w, const T** src);   // get_factors / get_factors_device: one-pass check, materialize_w, nsNMF's W S; *src = the panel to read W from
 	Status upload_triplets(std::vector<int>& rows, std::vector<int>& cols, std::vector<T>& vals);   // sparse mode: builds CSR + CSC on the host (the fall-back of upload_sparse_device)
 	Status upload_sparse_device(int format, const T* values, const int* a, const int* b, long nnz, int base, bool* fallback);   // ... on the device (kernels_sparse_setup.hip)
 	Status setup_kl_blocks();
@@ -440,6 +442,7 @@ private:
 
 	T *V_ = nullptr, *Vt_ = nullptr;
 	T *Wt_ = nullptr, *H_ = nullptr;          // factor panels
+	PanelState state_;                        // which derived buffers describe them and V, and the transitions of the entries that change one from outside (engine_state.h)
 	T *Ws_ = nullptr, *Hs_ = nullptr;         // nsNMF: smoothed copies (W S)^T and S H
 	T *slabs_ = nullptr;
 	T *numW_ = nullptr;                       // reduced (V H^T)^T panel (LS family error terms, sharded runs)
@@ -475,7 +478,6 @@ private:
 	// NMFAMD_ONE_IMAGE.
 	bool one_image_ = false;
 	int img_th_ = 128;        // rows per tile of the V image: 16 with one resident image (both kernel forms read contiguously), else the plan's
-	bool wx3_valid_ = false, hx3_valid_ = false;   // Wx3_ / Hx3_ hold the split image of the current Wt_ / H_
 	void *Wx3_ = nullptr, *Hx3_ = nullptr;
 	void* qx3_ = nullptr;     // split image of the r x r operand of the wide fp32 panel update
 	FactorProductPlan planHx_, planWx_;
@@ -511,8 +513,8 @@ private:
 	bool weighted_ = false;
 	// ... minibatch (prm_.batch_size > 0): batch_ columns per step, rho_ = forget_factor^(min(batch_, n) / n) in the precision of T; the plans of the two half-steps
 	// of a full batch (betaHb_, betaWb_) and of the remainder batch (betaHr_, betaWr_); online_A_ / online_B_ the accumulated numerator and denominator panels of W
-	// ([mpad][RP], set to W and 1 before the first step after the factors were set: online_stale_)
-	bool minibatch_ = false, online_stale_ = true;
+	// ([mpad][RP], set to W and 1 before the first step after the factors were set: PanelState::online_stale)
+	bool minibatch_ = false;
 	long batch_ = 0;
 	double rho_ = 0;
 	BetaPlan betaHb_, betaWb_, betaHr_, betaWr_;
@@ -529,54 +531,38 @@ private:
 	int gram_ksplit_ = 1;            // K slices of the W^T W passengers (gram_image.h): > 1 for column shards narrower than config 2
 	float* Gpart_ = nullptr;         // [GRAM_KSPLIT_MAX][4096] unscaled slices of W^T W (the H update adds and scales them, and stores G_)
 	float* wsq_part_ = nullptr;      // [mpad / 32][64] partial sums of squares of the rows the last W update wrote (k_mu64_update32<true>): the pending column scale's source
-	bool fused_ready_ = false, w_pending_ = false;
-	bool h_product_ahead_ = false;   // begin_next_iteration() has enqueued the W^T V launch of the next iteration_mu64 (cleared by whatever changes W, H or V)
 	// split-operand path: Gram matrices from the split images (gram_image.h), 32-column update kernel -- no partial Gram matrices
 	bool gram_image_ = false;
 	GramReduceArgs gram_args(bool of_w, float* G, float* scale, int normalize) const;
 	Status standalone_gram(const GramReduceArgs& rg);
 	Status mu64_update(bool is_w, const T* slabs, int S, long slab_stride, const T* Q, bool compute_error, const PeerSlabs* peers = nullptr);
-	// generic rank-64 fp32 path: the update kernel leaves partial Gram matrices of what it wrote (gram_from_update())
-	bool gram_w_ready_ = false;      // G_ holds W^T W of the current (normalised) W
 	// padded rank 256 with bf16 product operands (kernels_tri.hip): one pass per factor between its update and the product that streams
 	// it (normalise + smooth + bf16 fragments), Gram matrices of the smoothed panels from the unsmoothed ones (S G S)
 	bool tri_ = false;
 	unsigned* tri_ride_counters_ = nullptr;          // arrival counters of the Gram passengers (tri_gram_tile.h): zero between launches
 	bool tri_ride_w_ = false, tri_ride_h_ = false;   // the Gram matrix of W / of S H rides in the W^T V / V (S H)^T launch (Engine::plan leaves TRI_PASSENGERS CUs free)
-	bool wtb_valid_ = false;         // Wtb_ holds the bf16 fragments of the current W as it lies in Wt_ (unsmoothed; without the pending column scale)
-	bool tri_scale_pending_ = false; // W = Wt_ diag(d), d(c) = 1 / sqrt(staged sums in colsq_): the column normalisation of the last W update has not been folded into the panel
-	bool tri_scale_from_gram_ = false; // ... and its sums of squares are still to come out of the next Gram reduction (tri_prepare_w), into colsq_
 	bool sole_rank_ = false;
-	T* kl_scale_ = nullptr;          // KL iteration: W's pending column scale d (RP factors, from k_kl_sums) ...
-	bool kl_scale_pending_ = false;  // ... Wt_ holds the unnormalised result of the last KL W update (materialize_w folds d in)
-	bool kl_sw_ready_ = false;       // sW_ holds the column sums of the current W (left by its last KL update; a W set from outside needs the pass over the panel)
+	T* kl_scale_ = nullptr;          // KL iteration: W's pending column scale d (RP factors, from k_kl_sums; PanelState::kl_scale_pending)
 	bool kl_err_iter_ = false;       // sharded KL: h_step's compute_error, for the W-side evaluation in w_products
 	long err_total_columns_ = 0;     // sharded runs: columns of the whole matrix (0: this engine's own n)
 	Status kl_h_step();
 	Status kl_w_products(T* exchange, bool compute_error);
 	Status kl_w_finish(const T* exchange, bool compute_error);
 	bool tri_w_den_bf16_ = true;     // the W update's r x r product takes the old rows rounded to bf16 (NMFAMD_TRI_FP32_DEN=1: six-term fp32-accurate product)
-	bool hb_valid_ = false;          // Hb_ holds the bf16 fragments of the current smoothed H (written by the H update)
 	// Gw_raw_ holds W^T W without the pending scale: what the error term's trace multiplies it with
-	const T* tri_trace_scale() const { return (tri_ && tri_scale_pending_) ? reinterpret_cast<const T*>(colsq_) : nullptr; }
-	bool tri_gw_ready_ = false;      // Gw_raw_ / G_ describe the current W
-	bool tri_rows_cover_ = false;    // the last w_normalize_rows() covered every row of W
-	bool w_rows_stale_ = false;      // row-block sharded run with the fragment exchange: the fp32 rows of the other ranks' blocks in Wt_ are those of an earlier iteration
+	const T* tri_trace_scale() const { return (tri_ && state_.tri_scale_pending) ? reinterpret_cast<const T*>(colsq_) : nullptr; }
 	std::function<Status()> w_gather_hook_;
 	int colsq_parts_ = 1;            // staged partial vectors in colsq_ (kernels_tri.hip: launch_colsq_stage)
 	float *gram_tri_part_ = nullptr, *Gw_raw_ = nullptr, *Gh_raw_ = nullptr, *colsq_ = nullptr;
-	bool qx3_holds_g_ = false, qx3_holds_hht_ = false;   // qx3_ holds the split image of G_ / of the smoothed H H^T (k_smooth_gram)
-	void tri_smoothing(T* offdiag, T* diag) const;
+	struct Smoothing { T off, diag; };               // nsNMF's S = (1 - theta) I + theta / r 1 1^T as (off-diagonal, diagonal), in T: the one place that computes them; the identity (0, 1) on every other engine
+	Smoothing smoothing_constants() const { const T off = (T)prm_.theta / (T)(unsigned)r_; return alg_ == ALG_NSNMF ? Smoothing{off, (T)((1.0 - (T)prm_.theta) + off)} : Smoothing{T(0), T(1)}; }
+	hipError_t smooth_panel(const T* P, T* Ps, long len_pad) { const auto [off, diag] = smoothing_constants(); return launch_smooth_panel<T>(P, Ps, RP_, r_, len_pad, off, diag, stream_); }
 	Status tri_prepare_w(GramReduceArgs* ride = nullptr);          // Wtb_, Gw_raw_, G_ for the H step (ride: the Gram matrix as passengers of the product launch that follows, tri_gram_tile.h)
 	Status tri_prepare_h(T* hht, bool local_q, GramReduceArgs* ride = nullptr);    // Hb_, Gh_raw_, hht (= the Gram matrix of the smoothed H) for the W step
 	Status tri_update_w(const T* num, int S, long stride, const T* hht);   // W update + normalisation + everything tri_prepare_w() would do
-	// fused double-precision iteration (round 6, iterate_fused64): Wt_ holds the UNNORMALISED result of the last W update, sumsq_part_ its per-workgroup sums of squares;
-	// the column scale is applied by the consumers (kernels_f64.hip: gram_ride_f64 -> f64_scale_, PanelFusedF64) -- materialize_w() folds it into the panel
-	bool f32w_pending_ = false;                      // fused fp32 iteration at padded ranks >= 128: Wt_ unnormalised, sumsq_part_ holds its sums of squares, Wx3_ its split image
-	float* f32w_scale_ = nullptr;                    // ... the pending column scale (k_gram_reduce_x3)
+	// fused double-precision iteration (round 6, iterate_fused64; PanelState::f64_pending): the column scale is applied by the consumers (kernels_f64.hip: gram_ride_f64 -> f64_scale_, PanelFusedF64) -- materialize_w() folds it into the panel
+	float* f32w_scale_ = nullptr;                    // fused fp32 iteration at padded ranks >= 128: the pending column scale (k_gram_reduce_x3)
 	int f32w_ride_h_ = 0, f32w_ride_w_ = 0;         // ... K slices per super-block of W^T W / H H^T that ride the product launches as passenger workgroups (0: a launch of their own)
-	bool f64_pending_ = false;
-	bool f64_product_ahead_ = false;                 // begin_next_iteration() has enqueued launch 1 of the next iterate_fused64 (cleared by whatever changes W, H or V)
 	Status fused64_product_h();
 	double *f64_scale_ = nullptr, *f64_partial_ = nullptr;
 	unsigned* f64_counters_ = nullptr;
@@ -584,7 +570,6 @@ private:
 	int f64_slices_h_ = 0, f64_slices_w_ = 0;        // K slices of the Gram passengers riding in the W^T V / V H^T launch
 	const GramRideF64* ride64_ = nullptr;            // set around a product_h / product_w call
 	unsigned long long* f64_stamps_ = nullptr;       // measurement builds (NMFAMD_F64_STAMPS = file): [4 launches][4096][8] stamps of the LAST fused iteration, written out by the destructor
-	bool gram_h_partials_ = false;   // gramH_part_ describes the current H
 	bool h_partials_unneeded_ = false; // set by iterate() around its H step: GDCLS takes H H^T from the split image beside the product against V
 	int normalize_next_ = 0;
 	T *psN_ = nullptr, *psR_ = nullptr;
