@@ -633,9 +633,48 @@ NMFAMD_API int nmfamd_op_sddmm_quotient_f32(const int* ptr, const int* idx, cons
                                             float* q, float* t_vwh, float* t_kl);
 NMFAMD_API int nmfamd_op_sddmm_quotient_f64(const int* ptr, const int* idx, const double* val, long nnz, const double* A, const double* B, long b_rows, int RP, int rows,
                                             double* q, double* t_vwh, double* t_kl);
+/* The extras of the fused iterations' launch for nmfamd_op_panel_update_* below (PanelFusedF32 / PanelFusedF64, csrc/kernels.h). */
+typedef struct nmfamd_panel_fused {
+	const void* old_scale;    /* RP values or NULL (W side): every old value is read as old(y, c) * old_scale[c] */
+	int h_side;               /* H side: Q is the raw Gram matrix, num <- S D num, den = S D Q D S old */
+	const void* scale;        /* RP values or NULL: the diagonal of D */
+	int smooth;               /* 0: S = I; else S = (diag - off) I + off 1 1^T on the first r rank rows */
+	double off, diag;
+	int r;
+	void* smooth_out;         /* [len_pad][RP] or NULL: S new (H side with smoothing), copied in and out like the other outputs */
+	float* x3_out;            /* fp32 only, [len_pad][RP] floats or NULL: the decoded split image of S new (of new without smoothing) */
+} nmfamd_panel_fused;
+/* One launch of the Frobenius panel update (docs/PANEL_UPDATE.md) on host arrays in panel layout, for tests: through launch_panel_update<T> with the arguments the
+ * engines pass, or -- `fused` given -- through the launchers the fused iterations call (fp32 at padded ranks 128 ... 512 with Q handed over as its split image; fp64 at
+ * padded rank 64 and 128 ... 512).  mode: 0 multiplicative, 1 least squares, 2 plain slab sum.  P [len_pad][RP] (updated in place), S slabs of [len_pad][RP] at
+ * slab_stride >= len_pad * RP elements (the gaps are not read), Q [RP][RP]; len_pad a multiple of 128.  Optional outputs (NULL: not requested, not allocated), each
+ * copied to the device before the launch and back after it, so that what the launch leaves alone keeps the caller's values: ps (len_pad), sumsq_part (sumsq_rows rows
+ * of RP, at least *parts of them), num_out [len_pad][RP], gram_partial (len_pad / 64 matrices of 64 x 64).  x3_out [len_pad][RP] floats: the split image of the new
+ * rows decoded by adding its three bf16 planes (a slot the launch did not write decodes to NaN).  split_q: the scratch for the split image of Q is given; tri: an
+ * all-default PanelTriExtras is given.  *parts = panel_update_parts().  NMFAMD_INVALID_ARGUMENT, with no output touched, wherever the launcher refuses. */
+NMFAMD_API int nmfamd_op_panel_update_f32(int mode, float* P, const float* slabs, int S, long slab_stride, const float* Q, int RP, int len_pad, int len_valid, float eps,
+                                          float* ps, float* sumsq_part, long sumsq_rows, float* num_out, float* gram_partial, float* x3_out, int split_q, int tri,
+                                          const nmfamd_panel_fused* fused, int* parts);
+NMFAMD_API int nmfamd_op_panel_update_f64(int mode, double* P, const double* slabs, int S, long slab_stride, const double* Q, int RP, int len_pad, int len_valid, double eps,
+                                          double* ps, double* sumsq_part, long sumsq_rows, double* num_out, double* gram_partial, float* x3_out, int split_q, int tri,
+                                          const nmfamd_panel_fused* fused, int* parts);
+/* Which kernel the last nmfamd_op_panel_update_* of the calling thread was sent to, where forms that return the same values share a launcher (csrc/panel_form.h):
+ * 0 a kernel outside kernels_wide.hip, 1 k_panel_update64_lds_f32, 2 k_panel_update_wide_f32 (32 rows per workgroup), 3 its fused instantiation,
+ * 4 k_panel_update_rows_mu (128 rows), 5 k_panel_update_wide64_mu (64 rows). */
+NMFAMD_API int nmfamd_op_panel_update_last_form(void);
+/* One launch of the rank-64 fused multiplicative update (kernels_mu64.hip): tile = 64 through launch_mu64_update (gram_partial: len_pad / 64 matrices of 64 x 64, may be
+ * NULL here, the kernel always writes them), tile = 32 through launch_mu64_update32 (colsq_part: len_pad / 32 vectors of 64, W side; qsplit in {2, 4, 8}: Q holds
+ * qsplit unscaled 64 x 64 slices and q_out receives the finished matrix; ns != 0: SmoothAround {ns_off, ns_diag, ns_r}).  P [len_pad][64], scale 64 values, ps len_pad
+ * values (H side: one term per valid column; W side: 64 terms, needs Gprev), x3_out [len_pad][64] floats: the decoded split image.  Outputs copied in and out as
+ * above; no peer slabs.  NMFAMD_INVALID_ARGUMENT where the launcher refuses, and for a combination that would have a kernel go through a NULL pointer. */
+NMFAMD_API int nmfamd_op_mu64_update_f32(int is_w, int tile, float* P, const float* slabs, int S, long slab_stride, const float* Q, const float* scale, float eps,
+                                         int len_pad, int len_valid, float* ps, const float* Gprev, int compute_error, float* gram_partial, float* colsq_part,
+                                         int qsplit, float* q_out, int ns, float ns_off, float ns_diag, int ns_r, float* x3_out);
 /* Test access to an engine's device intermediates in panel layout: which = 0 Wt, 1 H, 2 W^T W,
  * 3 H H^T, 4 slabs, 5 inverse, 6 V, 7 Vt; rank-256 fp32 engines also 8 W^T W as last reduced, 9 staged column sums of squares,
- * 10 / 11 the bf16 fragments of W / H as 4-byte words. */
+ * 10 / 11 the bf16 fragments of W / H as 4-byte words; fp32 engines on the rank-64 fused path also 20 the pending column scale of W (64 values) and 21 the Wt panel
+ * as it lies, unnormalised while that scale is pending (0 folds the scale in first), 22 the gram_k_slices unscaled K slices of W^T W (engines with more than one).
+ * A negative count is refused. */
 NMFAMD_API int nmfamd_engine_debug_read(nmfamd_engine* e, int which, void* out, long count);
 
 #ifdef __cplusplus

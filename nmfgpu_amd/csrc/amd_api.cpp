@@ -7,6 +7,7 @@
 #include <string>
 #include <memory>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nmfgpu_amd.h"
@@ -15,6 +16,7 @@
 #include "tuning.h"
 #include "host_init.h"
 #include "sharded.h"
+#include "panel_form.h"
 
 using namespace nmfamd;
 
@@ -1408,6 +1410,183 @@ int nmfamd_op_sddmm_quotient_f32(const int* ptr, const int* idx, const float* va
 int nmfamd_op_sddmm_quotient_f64(const int* ptr, const int* idx, const double* val, long nnz, const double* A, const double* B, long b_rows, int RP, int rows, double* q,
                                  double* t_vwh, double* t_kl) {
 	return op_sddmm_quotient<double>(ptr, idx, val, nnz, A, B, b_rows, RP, rows, q, t_vwh, t_kl);
+}
+
+} // extern "C"
+
+// Test entries of the Frobenius panel-update kernels (docs/PANEL_UPDATE.md): one launch through launch_panel_update<T> (or, with `fused`, through the launchers the
+// fused iterations call) and one through launch_mu64_update / launch_mu64_update32, on caller-supplied padded arrays.  The checks here only keep the kernels inside
+// the buffers; which combination of outputs a form accepts is the launchers' decision and comes back as NMFAMD_INVALID_ARGUMENT.
+namespace {
+// fp32 (len_pad, RP) from a split image in store_split3's layout (split3.h): the three planes added from the smallest up
+void decode_split_image(const std::vector<uint16_t>& img, int RP, long len_pad, float* out) {
+	const int NBT = RP / 32;
+	for (long y = 0; y < len_pad; ++y)
+		for (int c = 0; c < RP; ++c) {
+			float sum = 0.f;
+			for (int pl = 2; pl >= 0; --pl) {
+				const size_t idx = (((((size_t)(y / 16) * NBT + c / 32) * 3 + pl) * 2 + ((y / 8) & 1)) * 32 + (c & 31)) * 8 + (y & 7);
+				const uint32_t bits = (uint32_t)img[idx] << 16;
+				float f;
+				std::memcpy(&f, &bits, 4);
+				sum += f;
+			}
+			out[y * RP + c] = sum;
+		}
+}
+size_t split_image_bytes(int RP, long len_pad) { return (size_t)(len_pad / 16) * (RP / 32) * 3 * 64 * 16; }
+
+// an image buffer filled with bf16 NaNs, so that a slot the kernel leaves alone decodes to NaN
+hipError_t alloc_nan_image(DevBuf& b, size_t bytes) {
+	if (hipError_t e = b.alloc(bytes); e != hipSuccess) return e;
+	return hipMemset(b.p, 0xff, bytes);
+}
+
+template <typename T>
+int op_panel_update(int mode, T* P, const T* slabs, int S, long slab_stride, const T* Q, int RP, int len_pad, int len_valid, T eps, T* ps, T* sumsq_part, long sumsq_rows,
+                    T* num_out, T* gram_partial, float* x3_out, int split_q, int tri, const nmfamd_panel_fused* fused, int* parts) {
+	constexpr bool f32 = std::is_same<T, float>::value;
+	if (!P || !slabs || !Q || !parts || S < 1 || RP < 32 || RP > 512 || RP % 32 != 0 || len_pad < 128 || len_pad % 128 != 0 || len_valid < 0 || len_valid > len_pad ||
+	    slab_stride < (long)len_pad * RP || mode < PANEL_MU || mode > PANEL_SET || (sumsq_part && sumsq_rows < 1)) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	// (MODE_SET always runs the generic kernel, whose workgroups panel_update_parts() does not describe at a rank with a fast form: the engines ask for no partials there)
+	const int generic_parts = len_pad / panel_update_rows(RP, sizeof(T));
+	const int np = mode == PANEL_SET ? generic_parts : panel_update_parts(RP, sizeof(T), len_pad);
+	if (sumsq_part && sumsq_rows < std::max(np, generic_parts)) return NMFAMD_INVALID_ARGUMENT;
+	if (fused) {
+		// the launchers behind `fused` have no checks of their own for these
+		if (mode != PANEL_MU || gram_partial || x3_out || tri || num_out || (fused->smooth && (fused->r < 1 || fused->r > RP))) return NMFAMD_INVALID_ARGUMENT;
+		if (f32 ? !panel_update_wide_available(RP) : !(RP == 64 || panel_update_wide_f64_available(RP))) return NMFAMD_INVALID_ARGUMENT;
+		if ((fused->x3_out && !f32) || ((fused->smooth_out || fused->scale) && !fused->h_side)) return NMFAMD_INVALID_ARGUMENT;
+	}
+	const size_t panel = sizeof(T) * (size_t)len_pad * RP, all_slabs = sizeof(T) * (size_t)(((long)S - 1) * slab_stride + (long)len_pad * RP);
+	const size_t q_image = (size_t)3 * 16 * (RP / 16 + 1) * (RP / 32) * 64, image = split_image_bytes(RP, len_pad);
+	DevBuf dP, dS, dQ, dPs, dSq, dNum, dGram, dX3, dQx, dOs, dSc, dSm;
+	if (dP.alloc(panel) != hipSuccess || dS.alloc(all_slabs) != hipSuccess || dQ.alloc(sizeof(T) * (size_t)RP * RP) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+	if (hipMemcpy(dP.p, P, panel, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dS.p, slabs, all_slabs, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(dQ.p, Q, sizeof(T) * (size_t)RP * RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	// every optional output starts as the caller's array, so that what a launch leaves alone keeps the caller's sentinels
+	auto in = [](DevBuf& b, const void* src, size_t bytes) {
+		if (src == nullptr) return (int)NMFAMD_OK;
+		if (b.alloc(bytes) != hipSuccess) return (int)NMFAMD_NO_DEVICE_MEMORY;
+		return hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? (int)NMFAMD_OK : (int)NMFAMD_HIP_ERROR;
+	};
+	if (int st = in(dPs, ps, sizeof(T) * (size_t)len_pad)) return st;
+	if (int st = in(dSq, sumsq_part, sizeof(T) * (size_t)sumsq_rows * RP)) return st;
+	if (int st = in(dNum, num_out, panel)) return st;
+	if (int st = in(dGram, gram_partial, sizeof(T) * (size_t)(len_pad / 64) * 4096)) return st;
+	if (x3_out && alloc_nan_image(dX3, image) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+	if ((split_q || (fused && f32)) && dQx.alloc(q_image) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+	hipError_t err = hipSuccess;
+	panel_update_reset_form();
+	if (fused) {
+		if (int st = in(dOs, fused->old_scale, sizeof(T) * (size_t)RP)) return st;
+		if (int st = in(dSc, fused->scale, sizeof(T) * (size_t)RP)) return st;
+		if (int st = in(dSm, fused->smooth_out, panel)) return st;
+		if (fused->x3_out && alloc_nan_image(dX3, image) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+		if constexpr (f32) {
+			PanelFusedF32 fx;
+			fx.old_scale = (const float*)dOs.p; fx.h_side = fused->h_side; fx.scale = (const float*)dSc.p; fx.smooth = fused->smooth;
+			fx.off = (float)fused->off; fx.diag = (float)fused->diag; fx.r = fused->r; fx.smooth_out = (float*)dSm.p;
+			fx.x3_out = fused->x3_out ? dX3.p : nullptr; fx.x3_ks = len_pad / 16;
+			// the r x r operand as the fused iteration hands it over: its split image (A(c, k) = Q(k, c)), no fp32 matrix
+			err = launch_pack_panel_x3((const float*)dQ.p, RP, RP, dQx.p, RP / 16, nullptr);
+			if (err == hipSuccess)
+				err = launch_panel_update_wide_f32(mode, (float*)dP.p, (const float*)dS.p, S, slab_stride, nullptr, RP, len_pad, eps, (float*)dPs.p, len_valid, (float*)dSq.p,
+				                                   nullptr, nullptr, dQx.p, nullptr, &fx);
+		} else {
+			PanelFusedF64 fx = {};
+			fx.old_scale = (const double*)dOs.p; fx.h_side = fused->h_side; fx.scale = (const double*)dSc.p; fx.smooth = fused->smooth;
+			fx.off = fused->off; fx.diag = fused->diag; fx.r = fused->r; fx.smooth_out = (double*)dSm.p;
+			err = RP == 64 ? launch_panel_update64_f64(mode, (double*)dP.p, (const double*)dS.p, S, slab_stride, (const double*)dQ.p, len_pad, eps, (double*)dPs.p, len_valid,
+			                                           (double*)dSq.p, nullptr, nullptr, &fx)
+			               : launch_panel_update_wide_f64(mode, (double*)dP.p, (const double*)dS.p, S, slab_stride, (const double*)dQ.p, RP, len_pad, eps, (double*)dPs.p, len_valid,
+			                                              (double*)dSq.p, nullptr, nullptr, &fx);
+		}
+	} else {
+		const PanelTriExtras none = PanelTriExtras();
+		err = launch_panel_update<T>(mode, (T*)dP.p, (const T*)dS.p, S, slab_stride, (const T*)dQ.p, RP, len_pad, eps, (T*)dPs.p, len_valid, (T*)dSq.p, (T*)dNum.p, nullptr,
+		                             (T*)dGram.p, dX3.p, x3_out ? len_pad / 16 : 0, split_q ? dQx.p : nullptr, tri ? &none : nullptr);
+	}
+	if (err == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
+	if (err != hipSuccess || hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
+	auto out = [](void* dst, const DevBuf& b, size_t bytes) { return dst == nullptr || hipMemcpy(dst, b.p, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+	if (!out(P, dP, panel) || !out(ps, dPs, sizeof(T) * (size_t)len_pad) || !out(sumsq_part, dSq, sizeof(T) * (size_t)sumsq_rows * RP) || !out(num_out, dNum, panel) ||
+	    !out(gram_partial, dGram, sizeof(T) * (size_t)(len_pad / 64) * 4096) || (fused && !out(fused->smooth_out, dSm, panel))) return NMFAMD_HIP_ERROR;
+	float* image_out = fused ? fused->x3_out : x3_out;
+	if (image_out) {
+		std::vector<uint16_t> h(image / 2);
+		if (hipMemcpy(h.data(), dX3.p, image, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+		decode_split_image(h, RP, len_pad, image_out);
+	}
+	*parts = np;
+	return NMFAMD_OK;
+}
+} // namespace
+
+extern "C" {
+
+int nmfamd_op_panel_update_f32(int mode, float* P, const float* slabs, int S, long slab_stride, const float* Q, int RP, int len_pad, int len_valid, float eps, float* ps,
+                               float* sumsq_part, long sumsq_rows, float* num_out, float* gram_partial, float* x3_out, int split_q, int tri,
+                               const nmfamd_panel_fused* fused, int* parts) {
+	return op_panel_update<float>(mode, P, slabs, S, slab_stride, Q, RP, len_pad, len_valid, eps, ps, sumsq_part, sumsq_rows, num_out, gram_partial, x3_out, split_q, tri, fused, parts);
+}
+
+int nmfamd_op_panel_update_f64(int mode, double* P, const double* slabs, int S, long slab_stride, const double* Q, int RP, int len_pad, int len_valid, double eps, double* ps,
+                               double* sumsq_part, long sumsq_rows, double* num_out, double* gram_partial, float* x3_out, int split_q, int tri,
+                               const nmfamd_panel_fused* fused, int* parts) {
+	return op_panel_update<double>(mode, P, slabs, S, slab_stride, Q, RP, len_pad, len_valid, eps, ps, sumsq_part, sumsq_rows, num_out, gram_partial, x3_out, split_q, tri, fused, parts);
+}
+
+int nmfamd_op_panel_update_last_form(void) { return panel_update_last_form(); }
+
+int nmfamd_op_mu64_update_f32(int is_w, int tile, float* P, const float* slabs, int S, long slab_stride, const float* Q, const float* scale, float eps, int len_pad,
+                              int len_valid, float* ps, const float* Gprev, int compute_error, float* gram_partial, float* colsq_part, int qsplit, float* q_out,
+                              int ns, float ns_off, float ns_diag, int ns_r, float* x3_out) {
+	if (!P || !slabs || !Q || !scale || S < 1 || len_pad < 128 || len_pad % 128 != 0 || len_valid < 0 || len_valid > len_pad || slab_stride < (long)len_pad * 64 ||
+	    (tile != 32 && tile != 64) || qsplit < 0 || qsplit > 8) return NMFAMD_INVALID_ARGUMENT;
+	// what the kernels would read or write through a null pointer, and what the 64-column launcher has no argument for
+	if ((compute_error && (!ps || (is_w && !Gprev))) || (tile == 64 && (qsplit > 1 || ns || colsq_part || q_out)) || (tile == 32 && gram_partial) ||
+	    (colsq_part && !is_w) || (q_out && qsplit < 2)) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const size_t panel = sizeof(float) * (size_t)len_pad * 64, all_slabs = sizeof(float) * (size_t)(((long)S - 1) * slab_stride + (long)len_pad * 64);
+	const size_t qbytes = sizeof(float) * 4096 * (size_t)(qsplit > 1 ? qsplit : 1), image = split_image_bytes(64, len_pad), grams = sizeof(float) * (size_t)(len_pad / 64) * 4096;
+	DevBuf dP, dS, dQ, dScale, dPs, dGprev, dGram, dColsq, dQout, dX3;
+	if (dP.alloc(panel) != hipSuccess || dS.alloc(all_slabs) != hipSuccess || dQ.alloc(qbytes) != hipSuccess || dScale.alloc(sizeof(float) * 64) != hipSuccess ||
+	    alloc_nan_image(dX3, image) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+	if (hipMemcpy(dP.p, P, panel, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dS.p, slabs, all_slabs, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(dQ.p, Q, qbytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dScale.p, scale, sizeof(float) * 64, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	auto in = [](DevBuf& b, const void* src, size_t bytes) {
+		if (src == nullptr) return (int)NMFAMD_OK;
+		if (b.alloc(bytes) != hipSuccess) return (int)NMFAMD_NO_DEVICE_MEMORY;
+		return hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? (int)NMFAMD_OK : (int)NMFAMD_HIP_ERROR;
+	};
+	if (int st = in(dPs, ps, sizeof(float) * (size_t)len_pad)) return st;
+	if (int st = in(dGprev, Gprev, sizeof(float) * 4096)) return st;
+	if (int st = in(dColsq, colsq_part, sizeof(float) * (size_t)(len_pad / 32) * 64)) return st;
+	if (int st = in(dQout, q_out, sizeof(float) * 4096)) return st;
+	// (the 64-column kernel always writes its partial Gram matrices)
+	if (tile == 64) {
+		if (dGram.alloc(grams) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+		if (hipMemset(dGram.p, 0xff, grams) != hipSuccess) return NMFAMD_HIP_ERROR;
+	}
+	const SmoothAround sm = {ns_off, ns_diag, ns_r};
+	const hipError_t err =
+	    tile == 64 ? launch_mu64_update(is_w, (float*)dP.p, (const float*)dS.p, S, slab_stride, (const float*)dQ.p, (const float*)dScale.p, eps, (float*)dPs.p, len_valid, len_pad,
+	                                    (float*)dGram.p, (const float*)dGprev.p, compute_error, nullptr, x3_out ? dX3.p : nullptr, len_pad / 16)
+	               : launch_mu64_update32(is_w, (float*)dP.p, (const float*)dS.p, S, slab_stride, (const float*)dQ.p, (const float*)dScale.p, eps, (float*)dPs.p, len_valid, len_pad,
+	                                      (const float*)dGprev.p, compute_error, nullptr, dX3.p, len_pad / 16, nullptr, (float*)dColsq.p, qsplit, (float*)dQout.p, ns ? &sm : nullptr);
+	if (err == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
+	if (err != hipSuccess || hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
+	auto out = [](void* dst, const DevBuf& b, size_t bytes) { return dst == nullptr || hipMemcpy(dst, b.p, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+	if (!out(P, dP, panel) || !out(ps, dPs, sizeof(float) * (size_t)len_pad) || !out(colsq_part, dColsq, sizeof(float) * (size_t)(len_pad / 32) * 64) ||
+	    !out(q_out, dQout, sizeof(float) * 4096) || (tile == 64 && !out(gram_partial, dGram, grams))) return NMFAMD_HIP_ERROR;
+	if (x3_out) {
+		std::vector<uint16_t> h(image / 2);
+		if (hipMemcpy(h.data(), dX3.p, image, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+		decode_split_image(h, 64, len_pad, x3_out);
+	}
+	return NMFAMD_OK;
 }
 
 } // extern "C"

@@ -2954,6 +2954,7 @@ Status Engine<T>::kl_w_finish(const T* exchange, bool compute_error) {
 template <typename T>
 Status Engine<T>::debug_read(int which, T* out, long count) {
 	const T* src = nullptr; long avail = 0;
+	if (count < 0) return ST_INVALID;
 	switch (which) {
 	case 0: if (Status st = materialize_w()) return st; src = Wt_; avail = (long)RP_ * mpad_; break;
 	case 1: src = H_; avail = (long)RP_ * npad_; break;
@@ -2983,6 +2984,17 @@ Status Engine<T>::debug_read(int which, T* out, long count) {
 		const void* sp = ptrs[which - 12];
 		if (sp == nullptr || count > lens[which - 12]) return ST_INVALID;
 		HIPX(hipMemcpyAsync(out, sp, sizeof(T) * count, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipStreamSynchronize(stream_));
+		return ST_OK;
+	}
+	case 20: case 21: case 22: {
+		// the rank-64 fused iteration's operands (tests/test_gpu_mu64_update.py ties na.op_mu64_update to what the engine launches): 20 = the pending column scale
+		// of W the last product's passengers left (64 values), 21 = the Wt panel as it lies -- unnormalised while that scale is pending (0 folds the scale in first),
+		// 22 = the gram_k_slices unscaled K slices of W^T W the H update adds and scales (engines whose plan cuts the Gram passengers' K range)
+		if (sizeof(T) != 4 || !fused_capable() || scale_ == nullptr || (which == 22 && (Gpart_ == nullptr || gram_ksplit_ < 2))) return ST_INVALID;
+		const void* p = which == 20 ? (const void*)scale_ : which == 21 ? (const void*)Wt_ : (const void*)Gpart_;
+		if (count > (which == 20 ? 64l : which == 21 ? (long)RP_ * mpad_ : 4096l * gram_ksplit_)) return ST_INVALID;
+		HIPX(hipMemcpyAsync(out, p, sizeof(T) * count, hipMemcpyDeviceToHost, stream_));
 		HIPX(hipStreamSynchronize(stream_));
 		return ST_OK;
 	}

@@ -15,8 +15,14 @@
 #include "tuning.h"
 #include "split3.h"
 #include "gram_wide.h"
+#include "panel_form.h"
 
 namespace nmfamd {
+
+// test access: the form the last panel-update launch of this thread took (panel_form.h)
+static thread_local int g_last_panel_form = PANEL_FORM_OTHER;
+int panel_update_last_form() { return g_last_panel_form; }
+void panel_update_reset_form() { g_last_panel_form = PANEL_FORM_OTHER; }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -851,6 +857,7 @@ hipError_t launch_panel_update64_lds_f32(int mode, float* P, const float* slabs,
                                          float eps, float* ps, int len_valid, float* sumsq_part, float* num_out, hipStream_t stream, float* gram_partial,
                                          void* x3_out, int x3_ks) {
 	if ((mode != PANEL_MU && mode != PANEL_LS) || len_pad % 64 != 0) return hipErrorInvalidValue;
+	g_last_panel_form = PANEL_FORM_LDS64;
 	dim3 grid(len_pad / 64), block(256);
 	bf16x8* xo = reinterpret_cast<bf16x8*>(x3_out);
 	if (mode == PANEL_MU) hipLaunchKernelGGL((k_panel_update64_lds_f32<PANEL_MU>), grid, block, 0, stream, P, slabs, S, slab_stride, Q, eps, ps, len_valid, sumsq_part, num_out, gram_partial, xo, x3_ks);
@@ -1026,6 +1033,7 @@ static hipError_t launch_wide64(const float* P, float* Pout, const float* slabs,
 	const size_t max_bytes = sizeof(float) * (64 * (size_t)(128 * NCB + 4) + 256);
 	static std::atomic<unsigned long long> lds_done{0ull};
 	if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(&k_panel_update_wide64_mu<NCB>), (int)max_bytes, lds_done); e != hipSuccess) return e;
+	g_last_panel_form = PANEL_FORM_WIDE64;
 	hipLaunchKernelGGL((k_panel_update_wide64_mu<NCB>), dim3(len_pad / 64), dim3(256), lds_bytes, stream,
 	                   P, Pout, slabs, S, slab_stride, RP, eps, ps, len_valid, sumsq_part, reinterpret_cast<const bf16x8*>(qx3));
 	return hipGetLastError();
@@ -1246,6 +1254,7 @@ template <int NC>
 static hipError_t launch_rows_mu(const float* P, float* Pout, const float* slabs, int S, long slab_stride, int len_pad, float eps, float* ps, int len_valid,
                                  float* sumsq_part, hipStream_t stream, const void* qx3, const PanelTriExtras* tri) {
 	const int blocks = len_pad / 128;
+	g_last_panel_form = PANEL_FORM_ROWS128;
 	const float* old_colsq = tri ? tri->old_colsq : nullptr;
 	const int old_parts = tri ? tri->old_colsq_parts : 0;
 	bf16x8* frag = tri ? reinterpret_cast<bf16x8*>(tri->frag_out) : nullptr;
@@ -1293,6 +1302,7 @@ static hipError_t launch_wide(float* P, const float* slabs, int S, long slab_str
 	const size_t max_bytes = sizeof(float) * (2 * (size_t)WIDE_YB * (128 * NCB + 4) + 256 + extra + fxmax);
 	static std::atomic<unsigned long long> lds_done{0ull};
 	if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(&k_panel_update_wide_f32<MODE, NCB, FX>), (int)max_bytes, lds_done); e != hipSuccess) return e;
+	g_last_panel_form = FX ? PANEL_FORM_WIDE32_FUSED : PANEL_FORM_WIDE32;
 	hipLaunchKernelGGL((k_panel_update_wide_f32<MODE, NCB, FX>), dim3(len_pad / WIDE_YB), dim3(256), lds_bytes, stream,
 	                   P, slabs, S, slab_stride, Q, RP, eps, ps, len_valid, sumsq_part, num_out, reinterpret_cast<const bf16x8*>(qx3), tri, fx);
 	return hipGetLastError();

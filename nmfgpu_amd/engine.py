@@ -1224,6 +1224,119 @@ def op_sddmm_quotient(ptr: np.ndarray, idx: np.ndarray, val: np.ndarray, A: np.n
     return {"q": q, "t_vwh": tv, "t_kl": tk}
 
 
+class _PanelFused(C.Structure):
+    """nmfamd_panel_fused"""
+    _fields_ = [("old_scale", C.c_void_p), ("h_side", C.c_int), ("scale", C.c_void_p), ("smooth", C.c_int), ("off", C.c_double), ("diag", C.c_double),
+                ("r", C.c_int), ("smooth_out", C.c_void_p), ("x3_out", C.c_void_p)]
+
+
+PANEL_MODES = {"mu": 0, "ls": 1, "set": 2}
+# nmfamd_op_panel_update_last_form: the kernel of kernels_wide.hip a launch went to ("other": the generic kernel, the fp64 ones, the old rank-64 one)
+PANEL_FORMS = ("other", "lds64", "wide32", "wide32_fused", "rows128", "wide64")
+
+
+def op_panel_update(mode, P: np.ndarray, slabs: np.ndarray, Q: np.ndarray, len_valid: int, *, ps: Optional[np.ndarray] = None,
+                    sumsq_part: Optional[np.ndarray] = None, num_out: bool = False, gram_partial: bool = False, x3: bool = False, split_q: bool = False,
+                    fused: Optional[dict] = None, tri: bool = False, eps: Optional[float] = None, fill=np.nan):
+    """One launch of the Frobenius panel update (nmfamd_op_panel_update_*; docs/PANEL_UPDATE.md) on padded arrays: mode "mu" / "ls" / "set", P (len_pad, RP),
+    slabs (S, slab_stride) with slab_stride >= len_pad * RP (the rest of a row is a gap the kernel must not read), Q (RP, RP).  ps (len_pad values) and sumsq_part
+    (rows x RP, rows >= parts) are copied in before the launch, so what the kernel leaves alone keeps the caller's sentinels; num_out, gram_partial and x3 (the split
+    image of the new rows, decoded to float32) are allocated when asked for and start as `fill`.  split_q: the scratch for the split image of Q is handed over (wide
+    fp32 panels).  fused = dict(old_scale, h_side, scale, smooth, off, diag, r, smooth_out, x3), every key optional: the launch of the fused iterations (fp32 with Q as
+    its split image; fp64).  eps: the engines' (machine epsilon of the type) unless given.  Returns a dict: `P`, `ps`, `sumsq_part` (rows x RP), `num_out`,
+    `gram_partial` (len_pad / 64, 64, 64), `x3`, `smooth_out`, `parts`, `form` (one of PANEL_FORMS).  A combination the launcher refuses raises EngineError (status 1) with nothing launched."""
+    dt = np.dtype(P.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("float32 or float64")
+    mode = PANEL_MODES[mode] if isinstance(mode, str) else int(mode)
+    P = np.array(P, dtype=dt, order="C")
+    slabs = np.ascontiguousarray(slabs, dtype=dt); Q = np.ascontiguousarray(Q, dtype=dt)
+    len_pad, RP = P.shape
+    S, stride = slabs.shape
+    if Q.shape != (RP, RP) or stride < len_pad * RP:
+        raise ValueError("shapes: P (len_pad, RP); slabs (S, >= len_pad * RP); Q (RP, RP)")
+    real = C.c_float if dt == np.float32 else C.c_double
+    if ps is not None:
+        ps = np.array(ps, dtype=dt).reshape(-1)
+        if ps.size != len_pad:
+            raise ValueError("ps must hold len_pad values")
+    rows = 0
+    if sumsq_part is not None:
+        sumsq_part = np.array(sumsq_part, dtype=dt, order="C").reshape(-1, RP)
+        rows = sumsq_part.shape[0]
+    num = np.full((len_pad, RP), fill, dt) if num_out else None
+    gram = np.full((len_pad // 64, 64, 64), fill, dt) if gram_partial else None
+    image = np.full((len_pad, RP), fill, np.float32) if x3 else None
+    fx, smooth_out, keep = None, None, []
+    if fused is not None:
+        unknown = set(fused) - {"old_scale", "h_side", "scale", "smooth", "off", "diag", "r", "smooth_out", "x3"}
+        if unknown:
+            raise ValueError(f"fused: unknown keys {sorted(unknown)}")
+
+        def vec(name):
+            v = fused.get(name)
+            if v is None:
+                return None
+            v = np.ascontiguousarray(v, dtype=dt).reshape(-1)
+            if v.size != RP:
+                raise ValueError(f"fused[{name!r}] must hold RP values")
+            keep.append(v)
+            return v.ctypes.data
+        if fused.get("smooth_out"):
+            smooth_out = np.full((len_pad, RP), fill, dt)
+        if fused.get("x3"):
+            image = np.full((len_pad, RP), fill, np.float32)
+        fx = _PanelFused(vec("old_scale"), int(bool(fused.get("h_side", 0))), vec("scale"), int(bool(fused.get("smooth", 0))), float(fused.get("off", 0.0)),
+                         float(fused.get("diag", 1.0)), int(fused.get("r", 0)), smooth_out.ctypes.data if smooth_out is not None else None,
+                         image.ctypes.data if image is not None else None)
+    parts = C.c_int(0)
+    lib = library()
+    fn = lib.nmfamd_op_panel_update_f32 if dt == np.float32 else lib.nmfamd_op_panel_update_f64
+    st = fn(mode, _p(P), _p(slabs), S, C.c_long(stride), _p(Q), RP, len_pad, int(len_valid), real(np.finfo(dt).eps if eps is None else eps), _p(ps), _p(sumsq_part),
+            C.c_long(rows), _p(num), _p(gram), _p(image) if fused is None else None, int(bool(split_q)), int(bool(tri)), C.byref(fx) if fx is not None else None,
+            C.byref(parts))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_panel_update")
+    return {"P": P, "ps": ps, "sumsq_part": sumsq_part, "num_out": num, "gram_partial": gram, "x3": image, "smooth_out": smooth_out, "parts": parts.value,
+            "form": PANEL_FORMS[lib.nmfamd_op_panel_update_last_form()]}
+
+
+def op_mu64_update(is_w, P: np.ndarray, slabs: np.ndarray, Q: np.ndarray, scale: np.ndarray, len_valid: int, *, tile: int = 32, Gprev: Optional[np.ndarray] = None,
+                   compute_error: bool = False, qsplit: int = 0, ns: Optional[tuple] = None, colsq_part: bool = False, ps: Optional[np.ndarray] = None,
+                   gram_partial: bool = True, x3: bool = True, eps: Optional[float] = None, fill=np.nan):
+    """One launch of the rank-64 fused multiplicative update (nmfamd_op_mu64_update_f32; kernels_mu64.hip): tile = 64 through launch_mu64_update, tile = 32 through
+    launch_mu64_update32.  P (len_pad, 64) float32, slabs (S, slab_stride >= len_pad * 64), scale 64 values, Q (64, 64) -- or, with qsplit in (2, 4, 8), (qsplit, 64, 64)
+    unscaled slices, and `q_out` comes back.  ns = (off, diag, r): SmoothAround (H side, tile 32).  ps (len_pad values) is copied in first; compute_error on the W side
+    needs Gprev (64, 64).  Returns a dict: `P`, `ps`, `gram_partial` (tile 64; len_pad / 64, 64, 64), `colsq_part` (len_pad / 32, 64), `q_out`, `x3` (the decoded split
+    image); what was not asked for is None, what the launch leaves alone is `fill`."""
+    P = np.array(P, dtype=np.float32, order="C")
+    slabs = np.ascontiguousarray(slabs, dtype=np.float32); Q = np.ascontiguousarray(Q, dtype=np.float32); scale = np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+    len_pad, RP = P.shape
+    S, stride = slabs.shape
+    slices = int(qsplit) if int(qsplit) > 1 else 1
+    if RP != 64 or stride < len_pad * 64 or scale.size != 64 or Q.size != slices * 4096:
+        raise ValueError("shapes: P (len_pad, 64); slabs (S, >= len_pad * 64); scale 64; Q (64, 64) or (qsplit, 64, 64)")
+    if ps is not None:
+        ps = np.array(ps, dtype=np.float32).reshape(-1)
+        if ps.size != len_pad:
+            raise ValueError("ps must hold len_pad values")
+    if Gprev is not None:
+        Gprev = np.ascontiguousarray(Gprev, dtype=np.float32)
+        if Gprev.shape != (64, 64):
+            raise ValueError("Gprev (64, 64)")
+    gram = np.full((len_pad // 64, 64, 64), fill, np.float32) if gram_partial and tile == 64 else None
+    colsq = np.full((len_pad // 32, 64), fill, np.float32) if colsq_part else None
+    q_out = np.full((64, 64), fill, np.float32) if slices > 1 else None
+    image = np.full((len_pad, 64), fill, np.float32) if x3 else None
+    off, diag, r = (0.0, 1.0, 0) if ns is None else ns
+    st = library().nmfamd_op_mu64_update_f32(int(bool(is_w)), int(tile), _p(P), _p(slabs), S, C.c_long(stride), _p(Q), _p(scale),
+                                             C.c_float(np.finfo(np.float32).eps if eps is None else eps), len_pad, int(len_valid), _p(ps), _p(Gprev), int(bool(compute_error)),
+                                             _p(gram), _p(colsq), int(qsplit), _p(q_out), int(ns is not None), C.c_float(off), C.c_float(diag), int(r), _p(image))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_mu64_update")
+    return {"P": P, "ps": ps, "gram_partial": gram, "colsq_part": colsq, "q_out": q_out, "x3": image}
+
+
 def host_kmeans(data: np.ndarray, k: int, *, seed: int = 0, iterations: int = 100, threshold: float = 0.005):
     """The host-side Lloyd k-means behind computeKMeans and the KMeans*/EInNMF initialisers, without a
     device or context (nmfamd_host_kmeans_*).  Returns (clusters m x k, membership, passes)."""

@@ -42,6 +42,15 @@ def test_hals_test_entries_are_exported():
         assert name in _declared_c_symbols("nmfgpu_amd.h") and hasattr(lib, name), name
 
 
+def test_panel_update_test_entries_are_exported():
+    lib = na.library()
+    for name in ("nmfamd_op_panel_update_f32", "nmfamd_op_panel_update_f64", "nmfamd_op_mu64_update_f32"):
+        assert name in _declared_c_symbols("nmfgpu_amd.h") and hasattr(lib, name), name
+    # the Python mirror of nmfamd_panel_fused: four pointers, three ints and two doubles with C's padding
+    from nmfgpu_amd.engine import _PanelFused
+    assert C.sizeof(_PanelFused) == 72 and _PanelFused.off.offset == 32 and _PanelFused.smooth_out.offset == 56
+
+
 def test_struct_layout_matches_reference_table():
     # SURVEY.md section 8b, measured on the reference header with offsetof
     assert C.sizeof(na.MatrixDescription) == 44
