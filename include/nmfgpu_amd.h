@@ -480,6 +480,17 @@ NMFAMD_API int nmfamd_op_gram_f32(const float* P, long ldp, int r, int len, floa
 NMFAMD_API int nmfamd_op_gram_f64(const double* P, long ldp, int r, int len, double* G, long ldg);
 /* Ainv = (A + regulariser)^-1 for a host r x r matrix (offdiag / diag added as KernelFillMatrix.cu:29-45). */
 NMFAMD_API int nmfamd_op_inverse_f32(const float* A, long lda, int r, float offdiag, float diag, float* Ainv, long ldi);
+/* Test entry of the same inverse on every route that launches it (docs/INVERSE.md).  route 0: launch_inverse_small as the engines call it (Gauss-Jordan up to r = 64,
+ * Householder QR above); 1: the Householder route at any r; 2 / 3 (float, r <= 64): the Gauss-Jordan body as the passenger workgroup of the product launch that
+ * nmfamd_op_factor_product_f32 / nmfamd_op_factor_product_x3 make of A_prod (X x Y, column-major), F_prod (64 x Y) and OUT (64 x X) -- NULL / 0 on routes 0 and 1.
+ * Ainv_full: RP x RP (RP = the padded rank, returned in *rp_out: 64 up to r = 64, then the next multiple of 128 in float and of 64 in double), copied to the device
+ * before the launch and back whole after it.  A_after (RP x RP, or NULL): the device image of A starts as this array with the r x r block of A on top and is copied
+ * back as the launch left it.  NMFAMD_INVALID_ARGUMENT, with no output touched, for routes 2 and 3 in double or at r > 64 and wherever a launcher refuses
+ * (the fp32 MFMA product carries a passenger from 16 x-tiles on). */
+NMFAMD_API int nmfamd_op_inverse_ex_f32(const float* A, long lda, int r, float offdiag, float diag, int route, float* Ainv_full, float* A_after, int* rp_out,
+                                        const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT, long ldo);
+NMFAMD_API int nmfamd_op_inverse_ex_f64(const double* A, long lda, int r, double offdiag, double diag, int route, double* Ainv_full, double* A_after, int* rp_out,
+                                        const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT, long ldo);
 /* The passes between the update of a factor panel and the next product at padded rank 256 with bf16 product operands (129 <= r <= 256):
  * optional column normalisation (colsq: r sums of squares or NULL), nsNMF smoothing by theta, bf16 rounding; the Gram matrix of the panel and of
  * the smoothed panel.  P, P_out, pack_out: [len][ldp / r] rows of r values; G_raw, G_smooth: [r][r].  Outputs may be NULL. */

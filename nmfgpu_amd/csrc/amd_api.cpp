@@ -98,8 +98,12 @@ struct DevBuf {
 	hipError_t alloc(size_t bytes) { hipError_t e = hipMalloc(&p, bytes ? bytes : 16); if (e == hipSuccess) e = hipMemset(p, 0, bytes ? bytes : 16); return e; }
 };
 
+// the r x r inverse as the passenger workgroup of a product launch (nmfamd_op_inverse_ex_f32, routes 2 and 3): device buffers, GramReduceArgs::inv_*
+struct InversePassenger { const float* a; float* out; float offdiag, diag; int r; };
+
+// (passenger: a launcher that refuses it returns NMFAMD_INVALID_ARGUMENT with OUT untouched)
 template <typename T>
-int op_factor_product(const T* A, long lda, int X, int Y, const T* F, long ldf, int r, T* OUT, long ldo, bool use_valu, int* out_slabs) {
+int op_factor_product(const T* A, long lda, int X, int Y, const T* F, long ldf, int r, T* OUT, long ldo, bool use_valu, int* out_slabs, const InversePassenger* passenger = nullptr) {
 	if (!A || !F || !OUT || X <= 0 || Y <= 0 || r <= 0 || lda < X || ldf < r || ldo < r) return NMFAMD_INVALID_ARGUMENT;
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	const int RP = padded_rank(r, sizeof(T));
@@ -122,8 +126,10 @@ int op_factor_product(const T* A, long lda, int X, int Y, const T* F, long ldf, 
 		if (mfma) {
 			DevBuf dT;   // x-tiled image of A for the MFMA kernel
 			if (dT.alloc(sizeof(T) * Xp * Yp) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+			GramReduceArgs rg = {nullptr, 0, nullptr, nullptr, 0};
+			if (passenger) { rg.inv_a = passenger->a; rg.inv_out = passenger->out; rg.inv_offdiag = passenger->offdiag; rg.inv_diag = passenger->diag; rg.inv_r = passenger->r; }
 			e = launch_tile<float>((const float*)dA.p, Xp, X, Y, (float*)dT.p, plan.th * Yp, plan.th, false, nullptr);
-			if (e == hipSuccess) e = launch_factor_product_f32(plan, (const float*)dT.p, plan.th * Yp, (const float*)dF.p, RP, (float*)dS.p, slab_stride, nullptr);
+			if (e == hipSuccess) e = launch_factor_product_f32(plan, (const float*)dT.p, plan.th * Yp, (const float*)dF.p, RP, (float*)dS.p, slab_stride, nullptr, passenger ? &rg : nullptr);
 			if (e == hipSuccess) e = hipDeviceSynchronize();
 		}
 		else e = launch_factor_product_valu<T>((const T*)dA.p, Xp, (int)Xp, Y, (const T*)dF.p, RP, (T*)dS.p, nullptr);
@@ -138,6 +144,7 @@ int op_factor_product(const T* A, long lda, int X, int Y, const T* F, long ldf, 
 		}
 		else e = launch_factor_product_valu<T>((const T*)dA.p, Xp, (int)Xp, Y, (const T*)dF.p, RP, (T*)dS.p, nullptr);
 	}
+	if (passenger && (!mfma || !std::is_same<T, float>::value || e == hipErrorInvalidValue)) return NMFAMD_INVALID_ARGUMENT;
 	if (e != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (launch_reduce_slabs<T>((const T*)dS.p, S, slab_stride, (T*)dO.p, slab_stride, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (hipMemcpy2D(OUT, ldo * sizeof(T), dO.p, RP * sizeof(T), r * sizeof(T), X, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
@@ -648,7 +655,8 @@ int nmfamd_op_factor_product_bf16(const float* A, long lda, int X, int Y, const 
 }
 
 // x16: the x-tiled image in 16-row tiles (the engine's ONE resident image, read along its output index)
-static int op_factor_product_x3(const float* A, long lda, int X, int Y, const float* F, long ldf, int r, float* OUT, long ldo, int reps, double* avg_us, bool y_tiled, bool x16 = false) {
+static int op_factor_product_x3(const float* A, long lda, int X, int Y, const float* F, long ldf, int r, float* OUT, long ldo, int reps, double* avg_us, bool y_tiled, bool x16 = false,
+                                const InversePassenger* passenger = nullptr) {
 	if (!A || !F || !OUT || X <= 0 || Y <= 0 || r <= 0 || lda < X || ldf < r || ldo < r) return NMFAMD_INVALID_ARGUMENT;
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	int dev = 0; hipDeviceProp_t prop;
@@ -674,7 +682,10 @@ static int op_factor_product_x3(const float* A, long lda, int X, int Y, const fl
 	if (y_tiled) { if (launch_tile_transposed<float>((const float*)dA.p, Xp, X, Y, (float*)dT.p, tstride, 16, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR; }
 	else if (launch_tile<float>((const float*)dA.p, Xp, X, Y, (float*)dT.p, tstride, ith, false, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (launch_pack_panel_x3((const float*)dF.p, RP, Y, dFb.p, KS, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
-	if (launch_factor_product_x3(plan, (const float*)dT.p, tstride, dFb.p, RP, (float*)dS.p, slab_stride, nullptr, nullptr, nullptr, y_tiled, ith) != hipSuccess) return NMFAMD_HIP_ERROR;
+	GramReduceArgs rg = {nullptr, 0, nullptr, nullptr, 0};
+	if (passenger) { rg.inv_a = passenger->a; rg.inv_out = passenger->out; rg.inv_offdiag = passenger->offdiag; rg.inv_diag = passenger->diag; rg.inv_r = passenger->r; }
+	if (hipError_t e = launch_factor_product_x3(plan, (const float*)dT.p, tstride, dFb.p, RP, (float*)dS.p, slab_stride, nullptr, passenger ? &rg : nullptr, nullptr, y_tiled, ith); e != hipSuccess)
+		return passenger && e == hipErrorInvalidValue ? NMFAMD_INVALID_ARGUMENT : NMFAMD_HIP_ERROR;
 	if (launch_reduce_slabs<float>((const float*)dS.p, plan.splits, slab_stride, (float*)dO.p, slab_stride, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (hipMemcpy2D(OUT, ldo * sizeof(float), dO.p, RP * sizeof(float), r * sizeof(float), X, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (reps > 0 && avg_us) {
@@ -793,6 +804,55 @@ int nmfamd_op_inverse_f32(const float* A, long lda, int r, float offdiag, float 
 	if (launch_inverse_small<float>((float*)dA.p, RP, r, (float*)dI.p, (double*)dW.p, offdiag, diag, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (hipMemcpy2D(Ainv, ldi * sizeof(float), dI.p, RP * sizeof(float), r * sizeof(float), r, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
 	return hipDeviceSynchronize() == hipSuccess ? NMFAMD_OK : NMFAMD_HIP_ERROR;
+}
+
+// Test entry of the r x r inverses on every route they are launched by (docs/INVERSE.md).  The device image of A starts as the caller's A_after (zeros without one) with
+// the r x r block of A on top, the output as the caller's Ainv_full: what a launch leaves alone keeps the caller's sentinels.
+extern "C++" {
+template <typename T>
+static int op_inverse_ex(const T* A, long lda, int r, T offdiag, T diag, int route, T* Ainv_full, T* A_after, int* rp_out,
+                         const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT, long ldo) {
+	constexpr bool f32 = std::is_same<T, float>::value;
+	if (!A || !Ainv_full || !rp_out || r <= 0 || lda < r || route < 0 || route > 3) return NMFAMD_INVALID_ARGUMENT;
+	const bool rides = route >= 2;
+	if (rides && (!f32 || r > 64 || !A_prod || !F_prod || !OUT || X <= 0 || Y <= 0 || lda_prod < X || ldf_prod < 64 || ldo < 64)) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const int RP = padded_rank(r, sizeof(T));
+	const size_t bytes = sizeof(T) * (size_t)RP * RP;
+	DevBuf dA, dI, dW;
+	if (dA.alloc(bytes) != hipSuccess || dI.alloc(bytes) != hipSuccess || dW.alloc(sizeof(double) * 2 * (size_t)r * r) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+	if (A_after && hipMemcpy(dA.p, A_after, bytes, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (hipMemcpy2D(dA.p, RP * sizeof(T), A, lda * sizeof(T), r * sizeof(T), r, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (hipMemcpy(dI.p, Ainv_full, bytes, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (rides) {
+		if constexpr (f32) {
+			const InversePassenger passenger = {(const float*)dA.p, (float*)dI.p, offdiag, diag, r};
+			const int st = route == 2 ? op_factor_product<float>(A_prod, lda_prod, X, Y, F_prod, ldf_prod, 64, OUT, ldo, false, nullptr, &passenger)
+			                          : op_factor_product_x3(A_prod, lda_prod, X, Y, F_prod, ldf_prod, 64, OUT, ldo, 0, nullptr, false, false, &passenger);
+			if (st != NMFAMD_OK) return st;
+		}
+	} else {
+		const hipError_t e = route == 0 ? launch_inverse_small<T>((T*)dA.p, RP, r, (T*)dI.p, (double*)dW.p, offdiag, diag, nullptr)
+		                                : launch_inverse_householder<T>((T*)dA.p, RP, r, (T*)dI.p, (double*)dW.p, offdiag, diag, nullptr);
+		if (e == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
+		if (e != hipSuccess) return NMFAMD_HIP_ERROR;
+	}
+	if (hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (hipMemcpy(Ainv_full, dI.p, bytes, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (A_after && hipMemcpy(A_after, dA.p, bytes, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	*rp_out = RP;
+	return NMFAMD_OK;
+}
+}
+
+int nmfamd_op_inverse_ex_f32(const float* A, long lda, int r, float offdiag, float diag, int route, float* Ainv_full, float* A_after, int* rp_out,
+                             const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT, long ldo) {
+	return op_inverse_ex<float>(A, lda, r, offdiag, diag, route, Ainv_full, A_after, rp_out, A_prod, lda_prod, X, Y, F_prod, ldf_prod, OUT, ldo);
+}
+
+int nmfamd_op_inverse_ex_f64(const double* A, long lda, int r, double offdiag, double diag, int route, double* Ainv_full, double* A_after, int* rp_out,
+                             const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT, long ldo) {
+	return op_inverse_ex<double>(A, lda, r, offdiag, diag, route, Ainv_full, A_after, rp_out, A_prod, lda_prod, X, Y, F_prod, ldf_prod, OUT, ldo);
 }
 
 // Test / measurement entry of kernels_tri.hip (padded rank 256): the passes between a factor update and the next product.

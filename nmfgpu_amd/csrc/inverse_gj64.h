@@ -34,7 +34,8 @@ __device__ inline double readlane_f64(double v, int lane_uniform) {
 // Pivot search of one Gauss-Jordan step, wave-local: lane = row, v = the pivot column.  The (near-)largest |v|
 // among the rows not used yet wins -- one 32-bit key per lane, the float bits of |v| with the low six bits
 // replaced by 63 - lane (the first of equal maxima wins).  Publishes the multipliers f / piv, the pivot row,
-// 1 / piv (hardware estimate + two Newton steps: the matrix carries fp32 data) and the bookkeeping.
+// 1 / piv of step k (hardware estimate + two Newton steps: the matrix carries fp32 data; read once, when the result is
+// written) and the bookkeeping.
 __device__ inline void gj_search(double v, unsigned long long used, int lane, int k, int b,
                                  double (*s_f)[64], double* s_pivinv, int* s_p, int* s_rowof, int* s_pivrow) {
 	unsigned key = 0u;
@@ -46,23 +47,29 @@ __device__ inline void gj_search(double v, unsigned long long used, int lane, in
 	pivinv = pivinv * (2.0 - piv * pivinv);
 	pivinv = pivinv * (2.0 - piv * pivinv);
 	s_f[b][lane] = v * pivinv;
-	if (lane == 0) { s_p[b] = p; s_pivinv[b] = pivinv; s_rowof[p] = k; s_pivrow[k] = p; }
+	if (lane == 0) { s_p[b] = p; s_pivinv[k] = pivinv; s_rowof[p] = k; s_pivrow[k] = p; }
 }
 
 // In-place Gauss-Jordan with partial pivoting in fp64, r <= 64, one workgroup of NW waves (8, or 4 when it rides in
 // a 256-thread kernel): wave w owns columns CPW w .. CPW w + CPW - 1 (CPW = 64 / NW) of the (identity-padded)
 // 64 x 64 matrix, lane = row, so
 //   * the pivot search of step k is local to wave k / CPW (register k % CPW: static index, no LDS),
-//   * one barrier per step carries the multipliers, the pivot row index and 1 / piv to the other waves,
+//   * one barrier per step carries the multipliers and the pivot row index to the other waves,
 //   * every wave fetches its CPW pivot-row values with v_readlane (same-address ds_read_b128 is serialised)
-//     and updates CPW columns: rows i != p: M_i -= (f_i / piv) row_p; row p: row_p / piv = row_p - (1 - 1/piv) row_p,
+//     and updates CPW columns: rows i != p: M_i -= (f_i / piv) row_p; row p is left as it is,
+//   * the division of row p by its pivot is DEFERRED to the write-back: a pivot row is never searched again and from then on only a target of
+//     M_i -= (M_ik / piv) row_p', which is linear in row i -- the stored row times the pending 1 / piv (s_pivinv[step]) is the row of the textbook
+//     algorithm at every later step, the eliminated column's entry in row p is 1 (times the pending 1 / piv), and each element is scaled once, in
+//     (T)(M * (1 / piv)).  No per-step work for the pivot row (the update loop is VALU-issue bound: two selects per element cost 3.1 us of 28.5,
+//     one multiply 1.2 us; docs/INVERSE.md), and every operation commutes with a power of two.  (Not row_p - (1 - 1 / piv) row_p, the earlier form:
+//     for |piv| >> 1 the rounding of 1 - 1 / piv leaves u |row_p| in a row of magnitude |row_p / piv|, a relative error of u |piv|),
 //   * the search of step k + 1 is issued as soon as its column is final, ahead of the next barrier.
 // Physical column k ends up as the column of the inverse that belongs to pivot row p_k; physical row p_k as row k.
 // (Measured: 26 us against 55 us for the two-barrier, LDS-broadcast form this replaces: tools/probe/gj_probe.hip.)
 template <typename T, int NW = 8>
 __device__ inline void inverse_gj64_body(const T* __restrict__ A, int RP, int r, T* __restrict__ Ainv, T offdiag, T diag) {
 	__shared__ double s_f[2][64];
-	__shared__ double s_pivinv[2];
+	__shared__ double s_pivinv[64];
 	__shared__ int s_p[2];
 	__shared__ int s_rowof[64], s_pivrow[64];
 	const int tid = threadIdx.x, lane = tid & 63;
@@ -85,15 +92,15 @@ __device__ inline void inverse_gj64_body(const T* __restrict__ A, int RP, int r,
 			__syncthreads();
 			const double fm = s_f[b][lane];                  // f / piv
 			const int p = __builtin_amdgcn_readfirstlane(s_p[b]);
-			const double pivinv = s_pivinv[b];
 			used |= 1ull << p;
 			double prow[CPW];
 #pragma unroll
 			for (int q = 0; q < CPW; ++q) prow[q] = readlane_f64(M[q], p);
-			const double fadj = (lane == p) ? 1.0 - pivinv : fm;
+			const bool is_p = lane == p;
+			const double fadj = is_p ? 0.0 : fm;
 #pragma unroll
-			for (int q = 0; q < CPW; ++q) M[q] = M[q] - fadj * prow[q];
-			if (wave == kg) M[kc] = (lane == p) ? pivinv : -fm;      // the eliminated column becomes a column of the inverse
+			for (int q = 0; q < CPW; ++q) M[q] = __builtin_fma(-fadj, prow[q], M[q]);
+			if (wave == kg) M[kc] = is_p ? 1.0 : -fm;      // the eliminated column becomes a column of the inverse (row p: 1 x the pending 1 / piv)
 			if (kc < CPW - 1) { if (wave == kg) gj_search(M[kc + 1 < CPW ? kc + 1 : 0], used, lane, CPW * kg + kc + 1, b ^ 1, s_f, s_pivinv, s_p, s_rowof, s_pivrow); }
 			else if (kg < NW - 1) { if (wave == kg + 1) gj_search(M[0], used, lane, CPW * kg + CPW, b ^ 1, s_f, s_pivinv, s_p, s_rowof, s_pivrow); }
 		}
@@ -101,10 +108,11 @@ __device__ inline void inverse_gj64_body(const T* __restrict__ A, int RP, int r,
 	__syncthreads();
 	{
 		const int kk = s_rowof[lane];                            // this physical row is row kk of the inverse
+		const double rs = s_pivinv[kk];                         // ... whose division by its pivot is still pending
 #pragma unroll
 		for (int q = 0; q < CPW; ++q) {
 			const int j = s_pivrow[CPW * wave + q];
-			if (kk < r && j < r) Ainv[(long)j * RP + kk] = (T)M[q];
+			if (kk < r && j < r) Ainv[(long)j * RP + kk] = (T)(M[q] * rs);
 		}
 	}
 	// zero padding of the RP x RP output outside the r x r block

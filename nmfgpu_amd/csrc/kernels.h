@@ -338,6 +338,9 @@ hipError_t launch_copy_two(T* dst, const T* a, long na, const T* b, long nb, hip
 // (r > 64 only; that route also adds the regulariser to A in place).
 template <typename T>
 hipError_t launch_inverse_small(T* A, int RP, int r, T* Ainv, double* work, T offdiag, T diag, hipStream_t stream);
+// ... its r > 64 half (Householder QR through `work`) at any r: what the kernel tests run below 65 as well
+template <typename T>
+hipError_t launch_inverse_householder(T* A, int RP, int r, T* Ainv, double* work, T offdiag, T diag, hipStream_t stream);
 
 template <typename T>
 hipError_t launch_transpose(const T* src, long lds, int rows, int cols, T* dst, long ldd, hipStream_t stream);

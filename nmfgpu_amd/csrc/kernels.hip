@@ -1016,18 +1016,26 @@ __global__ __launch_bounds__(256) void k_inverse_small(const T* __restrict__ A, 
 	}
 }
 
+// The Householder route at any r: the regulariser is added to A IN PLACE (A + regulariser is what the launch leaves behind), then k_inverse_small.
 template <typename T>
-hipError_t launch_inverse_small(T* A, int RP, int r, T* Ainv, double* work, T offdiag, T diag, hipStream_t stream) {
-	if (r <= 64) {
-		hipLaunchKernelGGL((k_inverse_gj64<T>), dim3(1), dim3(512), 0, stream, A, RP, r, Ainv, offdiag, diag);
-		return hipGetLastError();
-	}
+hipError_t launch_inverse_householder(T* A, int RP, int r, T* Ainv, double* work, T offdiag, T diag, hipStream_t stream) {
 	if (offdiag != T(0) || diag != T(0)) {
 		hipError_t e = launch_fill_small<T>(A, RP, r, 1, offdiag, diag, stream);
 		if (e != hipSuccess) return e;
 	}
 	hipLaunchKernelGGL((k_inverse_small<T>), dim3(1), dim3(256), 0, stream, A, RP, r, Ainv, work);
 	return hipGetLastError();
+}
+template hipError_t launch_inverse_householder<float>(float*, int, int, float*, double*, float, float, hipStream_t);
+template hipError_t launch_inverse_householder<double>(double*, int, int, double*, double*, double, double, hipStream_t);
+
+template <typename T>
+hipError_t launch_inverse_small(T* A, int RP, int r, T* Ainv, double* work, T offdiag, T diag, hipStream_t stream) {
+	if (r <= 64) {
+		hipLaunchKernelGGL((k_inverse_gj64<T>), dim3(1), dim3(512), 0, stream, A, RP, r, Ainv, offdiag, diag);
+		return hipGetLastError();
+	}
+	return launch_inverse_householder<T>(A, RP, r, Ainv, work, offdiag, diag, stream);
 }
 template hipError_t launch_inverse_small<float>(float*, int, int, float*, double*, float, float, hipStream_t);
 template hipError_t launch_inverse_small<double>(double*, int, int, double*, double*, double, double, hipStream_t);

@@ -800,15 +800,58 @@ def op_gram(P: np.ndarray) -> np.ndarray:
     return G
 
 
-def op_inverse(A: np.ndarray, offdiag: float = 0.0, diag: float = 0.0) -> np.ndarray:
+def inverse_padded_rank(r: int, dtype) -> int:
+    """The padded rank RP of the r x r inverse's output (csrc/engine.h, padded_rank)."""
+    return 64 if r <= 64 else (-(-r // 64) * 64 if np.dtype(dtype) == np.float64 else -(-r // 128) * 128)
+
+
+def op_inverse(A: np.ndarray, offdiag: float = 0.0, diag: float = 0.0, route: int = 0, full=False, product=None):
+    """(A + regulariser)^-1 of a host r x r matrix (float32 or float64) by one launch, regulariser = offdiag everywhere and diag on the diagonal (docs/INVERSE.md).
+    route 0: as the engines launch it (Gauss-Jordan up to r = 64, Householder QR above); 1: Householder at any r; 2 / 3 (float32, r <= 64): as the passenger
+    workgroup of the fp32 MFMA product / the split-operand product of product = (A_prod X x Y, F_prod 64 x Y[, OUT 64 x X]).
+    full=False returns the r x r inverse.  full=True returns a dict: `inv` (the RP x RP output, NaN where the launch wrote nothing), `a_after` (the RP x RP
+    input buffer as the launch left it, its padding NaN), `rp`, and on routes 2 / 3 `out` (the product).  full may also be a dict of caller-owned arrays `inv` and
+    `a_after` (RP x RP, Fortran order), which a refused call (EngineError, status 1) leaves as they were; so it does an OUT given in `product`."""
     A = _f(A)
     r = A.shape[0]
-    out = np.zeros((r, r), dtype=np.float32, order="F")
-    st = library().nmfamd_op_inverse_f32(C.c_void_p(A.ctypes.data), C.c_long(_ld(A)), r, C.c_float(offdiag), C.c_float(diag),
-                                         C.c_void_p(out.ctypes.data), C.c_long(r))
+    dt = A.dtype
+    if dt not in (np.float32, np.float64) or A.shape[1] != r:
+        raise ValueError("op_inverse takes a square float32 or float64 matrix")
+    RP = inverse_padded_rank(r, dt)
+    given = full if isinstance(full, dict) else {}
+    inv = given.get("inv")
+    if inv is None:
+        inv = np.full((RP, RP), np.nan, dtype=dt, order="F")
+    after = given.get("a_after")
+    if after is None and full:
+        after = np.full((RP, RP), np.nan, dtype=dt, order="F")
+    for a in (inv, after):
+        if a is not None and (a.shape != (RP, RP) or a.dtype != dt or not a.flags.f_contiguous):
+            raise ValueError(f"op_inverse: the full outputs are {RP} x {RP} Fortran-ordered arrays of A's type")
+    null = C.c_void_p(None)
+    prod = [null, C.c_long(0), 0, 0, null, C.c_long(0), null, C.c_long(0)]
+    out = None
+    if product is not None:
+        Ap, Fp = _f(product[0]), _f(product[1])
+        X, Y = Ap.shape
+        if Ap.dtype != np.float32 or Fp.dtype != np.float32 or Fp.shape != (64, Y):
+            raise ValueError("op_inverse: product = (A_prod X x Y, F_prod 64 x Y) in float32")
+        out = product[2] if len(product) > 2 else np.zeros((64, X), dtype=np.float32, order="F")
+        if out.shape != (64, X) or out.dtype != np.float32 or not out.flags.f_contiguous:
+            raise ValueError("op_inverse: OUT is a 64 x X Fortran-ordered float32 array")
+        prod = [C.c_void_p(Ap.ctypes.data), C.c_long(_ld(Ap)), X, Y, C.c_void_p(Fp.ctypes.data), C.c_long(_ld(Fp)), C.c_void_p(out.ctypes.data), C.c_long(64)]
+    rp = C.c_int(0)
+    f32 = dt == np.float32
+    name = "nmfamd_op_inverse_ex_f32" if f32 else "nmfamd_op_inverse_ex_f64"
+    scalar = C.c_float if f32 else C.c_double
+    st = getattr(library(), name)(C.c_void_p(A.ctypes.data), C.c_long(_ld(A)), r, scalar(offdiag), scalar(diag), int(route), C.c_void_p(inv.ctypes.data),
+                                  C.c_void_p(after.ctypes.data) if after is not None else null, C.byref(rp), *prod)
     if st != 0:
-        raise EngineError(st, "nmfamd_op_inverse_f32")
-    return out
+        raise EngineError(st, name)
+    assert rp.value == RP, (rp.value, RP)
+    if not full:
+        return np.asfortranarray(inv[:r, :r])
+    return {"inv": inv, "a_after": after, "rp": RP, "out": out}
 
 
 def op_factor_passes(P: np.ndarray, theta: float = 0.0, colsq: Optional[np.ndarray] = None, reps: int = 0):
