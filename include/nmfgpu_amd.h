@@ -605,6 +605,28 @@ NMFAMD_API int nmfamd_op_beta_update_rows_f32(float* P, float* Aacc, float* Bacc
                                               int r, int out_pad, int out_valid, double beta, double l1, double l2, int online, double rho, int flush, float* sum_part);
 NMFAMD_API int nmfamd_op_beta_update_rows_f64(double* P, double* Aacc, double* Bacc, const double* num_part, const double* den_part, int slabs, const double* dsum, int RP,
                                               int r, int out_pad, int out_valid, double beta, double l1, double l2, int online, double rho, int flush, double* sum_part);
+/* The two launches of a half-step one at a time, for the kernel-level tests (docs/DIVERGENCE.md, "Kernel-level tests").
+ * op_beta_fused: the fused launch alone -- launch_beta_fused, launch_beta_fused_weighted with Omega (an array like X), launch_beta_fused_bf16 with mixed (f32
+ * only, no Omega) -- under the plan nmfamd_op_beta_half_step_* uses.  A, B, X, ldx and the valid counts as there; update / terms: which of the launch's outputs are
+ * asked for (at least one).  plan[5]: slabs, tiles, tiles_per_slab, bo, kt.  With all four output arrays NULL only the plan is returned and nothing is launched; the
+ * caller sizes num_part / den_part [slabs][out_pad][RP] and tf_part / td_part [slabs][out_pad] (terms) from it.  The output arrays are uploaded as the caller
+ * filled them and are not cleared before the launch: what the launch does not write (den_part at the unweighted beta = 1) comes back unchanged. */
+NMFAMD_API int nmfamd_op_beta_fused_f32(const float* A, const float* B, const float* X, const float* Omega, long ldx, int RP, int out_pad, int out_valid, int red_pad,
+                                        int red_valid, double beta, int update, int terms, int mixed, int force_slabs, float* num_part, float* den_part, float* tf_part,
+                                        float* td_part, int* plan);
+NMFAMD_API int nmfamd_op_beta_fused_f64(const double* A, const double* B, const double* X, const double* Omega, long ldx, int RP, int out_pad, int out_valid, int red_pad,
+                                        int red_valid, double beta, int update, int terms, int mixed, int force_slabs, double* num_part, double* den_part, double* tf_part,
+                                        double* td_part, int* plan);
+/* op_beta_update: launch_beta_update alone on caller-built partial panels.  P [out_pad][RP] (in place); num_part / den_part [slabs][out_pad][RP], dsum [RP] (the
+ * denominators of the unweighted beta = 1), tf_part / td_part [slabs][out_pad] with t_frob / t_div [out_pad] (all four or none); weighted: the launch the weighted
+ * engines run (den_part at every beta).  update = 0: the terms only, P untouched.  sumsq_part / sum_part [(out_pad / 128)][RP] and t_frob / t_div are uploaded as the
+ * caller filled them.  At most 16 slabs.  NMFAMD_INVALID_ARGUMENT wherever launch_beta_update refuses, nothing launched. */
+NMFAMD_API int nmfamd_op_beta_update_f32(float* P, const float* num_part, const float* den_part, int slabs, const float* dsum, int RP, int r, int out_pad, int out_valid,
+                                         double beta, double l1, double l2, int weighted, int update, const float* tf_part, const float* td_part, float* sumsq_part,
+                                         float* sum_part, float* t_frob, float* t_div);
+NMFAMD_API int nmfamd_op_beta_update_f64(double* P, const double* num_part, const double* den_part, int slabs, const double* dsum, int RP, int r, int out_pad, int out_valid,
+                                         double beta, double l1, double l2, int weighted, int update, const double* tf_part, const double* td_part, double* sumsq_part,
+                                         double* sum_part, double* t_frob, double* t_div);
 /* The launches of the sparse path (kernels_sparse.hip), one each, on caller-built host arrays, for tests.  Panels are row-major [rows][RP]; a sparse image is
  * ptr / idx / val with 0-based int32 indices ascending within a row, nnz stored entries, the indices referring to rows of the gathered panel (b_rows / p_rows of
  * them).  eps is the epsilon of the type, as in the engine's KL iteration.  Output arrays are uploaded as the caller filled them and are not cleared before the

@@ -1159,6 +1159,102 @@ int op_beta_update_rows(T* P, T* Aacc, T* Bacc, const T* num_part, const T* den_
 	return NMFAMD_OK;
 }
 
+// The fused launch of a half-step alone (launch_beta_fused<T>, launch_beta_fused_weighted<T> with Omega, launch_beta_fused_bf16 with mixed), with op_beta_half_step's
+// plan, on caller-built arrays.  plan_out: slabs, tiles, tiles_per_slab, bo, kt.  All four output arrays NULL: the plan only, nothing launched -- the caller sizes
+// num_part / den_part [slabs][out_pad][RP] and tf_part / td_part [slabs][out_pad] from it.  The outputs are uploaded as the caller filled them and are not cleared,
+// so a test sees what the launch wrote and what it left alone.
+template <typename T>
+int op_beta_fused(const T* A, const T* B, const T* X, const T* Omega, long ldx, int RP, int out_pad, int out_valid, int red_pad, int red_valid, double beta_value,
+                  int update, int terms, int mixed, int force_slabs, T* num_part, T* den_part, T* tf_part, T* td_part, int* plan_out) {
+	const double beta = (double)(T)beta_value;
+	const bool plan_only = !num_part && !den_part && !tf_part && !td_part;
+	if (!plan_out || !beta_half_step_available(RP) || !std::isfinite(beta) || out_pad < 128 || out_pad % 128 != 0 || red_pad < 128 || red_pad % 128 != 0 ||
+	    out_valid < 0 || out_valid > out_pad || red_valid < 0 || red_valid > red_pad || ldx < red_pad || ldx % 4 != 0 || force_slabs < 0 || (mixed && (Omega || sizeof(T) != 4)))
+		return NMFAMD_INVALID_ARGUMENT;
+	if (!plan_only && (!A || !B || !X || !num_part || !den_part || (terms && (!tf_part || !td_part)))) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	int dev = 0;
+	hipDeviceProp_t prop;
+	if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return NMFAMD_HIP_ERROR;
+	const BetaPlan plan = plan_beta_half_step(out_pad, red_pad, RP, sizeof(T), prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256, force_slabs);
+	plan_out[0] = plan.slabs; plan_out[1] = plan.tiles; plan_out[2] = plan.tiles_per_slab; plan_out[3] = plan.bo; plan_out[4] = plan.kt;
+	if (plan_only) return NMFAMD_OK;
+	const size_t panelA = sizeof(T) * (size_t)out_pad * RP, panelB = sizeof(T) * (size_t)red_pad * RP, image = sizeof(T) * (size_t)out_pad * (size_t)ldx;
+	const size_t parts = panelA * plan.slabs, tparts = sizeof(T) * (size_t)plan.slabs * out_pad;
+	const long part_stride = (long)out_pad * RP;
+	DevBuf dA, dB, dX, dO, dNum, dDen, dTf, dTd;
+	if (dA.alloc(panelA) != hipSuccess || dB.alloc(panelB) != hipSuccess || dX.alloc(image) != hipSuccess || (Omega && dO.alloc(image) != hipSuccess) ||
+	    dNum.alloc(parts) != hipSuccess || dDen.alloc(parts) != hipSuccess || dTf.alloc(tparts) != hipSuccess || dTd.alloc(tparts) != hipSuccess)
+		return NMFAMD_NO_DEVICE_MEMORY;
+	if (hipMemcpy(dA.p, A, panelA, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dB.p, B, panelB, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(dX.p, X, image, hipMemcpyHostToDevice) != hipSuccess || (Omega && hipMemcpy(dO.p, Omega, image, hipMemcpyHostToDevice) != hipSuccess) ||
+	    hipMemcpy(dNum.p, num_part, parts, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dDen.p, den_part, parts, hipMemcpyHostToDevice) != hipSuccess)
+		return NMFAMD_HIP_ERROR;
+	if (terms && (hipMemcpy(dTf.p, tf_part, tparts, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dTd.p, td_part, tparts, hipMemcpyHostToDevice) != hipSuccess))
+		return NMFAMD_HIP_ERROR;
+	T* tf = terms ? (T*)dTf.p : nullptr;
+	T* td = terms ? (T*)dTd.p : nullptr;
+	const T eps = std::numeric_limits<T>::epsilon();
+	hipError_t err = hipErrorInvalidValue;
+	if (mixed) {
+		if constexpr (sizeof(T) == 4)
+			err = launch_beta_fused_bf16((const T*)dX.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update != 0, terms != 0, eps, plan, (T*)dNum.p, (T*)dDen.p,
+			                             part_stride, tf, td, out_pad, out_pad, out_valid, red_valid, nullptr);
+	} else if (Omega)
+		err = launch_beta_fused_weighted<T>((const T*)dX.p, (const T*)dO.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update != 0, terms != 0, eps, plan, (T*)dNum.p,
+		                                    (T*)dDen.p, part_stride, tf, td, out_pad, out_pad, out_valid, red_valid, nullptr);
+	else
+		err = launch_beta_fused<T>((const T*)dX.p, ldx, (const T*)dA.p, (const T*)dB.p, RP, beta, update != 0, terms != 0, eps, plan, (T*)dNum.p, (T*)dDen.p, part_stride,
+		                           tf, td, out_pad, out_pad, out_valid, red_valid, nullptr);
+	if (err == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
+	if (err != hipSuccess || hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (hipMemcpy(num_part, dNum.p, parts, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(den_part, dDen.p, parts, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (terms && (hipMemcpy(tf_part, dTf.p, tparts, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(td_part, dTd.p, tparts, hipMemcpyDeviceToHost) != hipSuccess))
+		return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
+
+// launch_beta_update<T> alone on caller-built partial panels: P [out_pad][RP], num_part / den_part [slabs][out_pad][RP] (either may be NULL where the launch does not
+// take it), dsum [RP], tf_part / td_part [slabs][out_pad] (both or neither).  sumsq_part / sum_part [out_pad / 128][RP] and t_frob / t_div [out_pad] are uploaded as the
+// caller filled them.  Which combinations run is the launcher's decision: its hipErrorInvalidValue comes back as NMFAMD_INVALID_ARGUMENT, nothing launched.
+template <typename T>
+int op_beta_update(T* P, const T* num_part, const T* den_part, int slabs, const T* dsum, int RP, int r, int out_pad, int out_valid, double beta_value, double l1d,
+                   double l2d, int weighted, int update, const T* tf_part, const T* td_part, T* sumsq_part, T* sum_part, T* t_frob, T* t_div) {
+	// (the sizes every buffer below is cut from; everything else is left to launch_beta_update)
+	if (!P || RP < 1 || RP > 256 || out_pad < 128 || out_pad % 128 != 0 || out_valid < 0 || out_valid > out_pad || slabs < 1 || slabs > BETA_MAX_SLABS ||
+	    !sumsq_part || !sum_part)
+		return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const size_t panel = sizeof(T) * (size_t)out_pad * RP, sums = sizeof(T) * (size_t)(out_pad / 128) * RP, rows = sizeof(T) * (size_t)out_pad;
+	DevBuf dP, dNum, dDen, dD, dSq, dSm, dTf, dTd, dOf, dOd;
+	if (dP.alloc(panel) != hipSuccess || dNum.alloc(panel * slabs) != hipSuccess || dDen.alloc(panel * slabs) != hipSuccess || dD.alloc(sizeof(T) * (size_t)RP) != hipSuccess ||
+	    dSq.alloc(sums) != hipSuccess || dSm.alloc(sums) != hipSuccess || dTf.alloc(rows * slabs) != hipSuccess || dTd.alloc(rows * slabs) != hipSuccess ||
+	    dOf.alloc(rows) != hipSuccess || dOd.alloc(rows) != hipSuccess)
+		return NMFAMD_NO_DEVICE_MEMORY;
+	if (hipMemcpy(dP.p, P, panel, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dSq.p, sumsq_part, sums, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(dSm.p, sum_part, sums, hipMemcpyHostToDevice) != hipSuccess)
+		return NMFAMD_HIP_ERROR;
+	if (num_part && hipMemcpy(dNum.p, num_part, panel * slabs, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (den_part && hipMemcpy(dDen.p, den_part, panel * slabs, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (dsum && hipMemcpy(dD.p, dsum, sizeof(T) * (size_t)RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (tf_part && hipMemcpy(dTf.p, tf_part, rows * slabs, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (td_part && hipMemcpy(dTd.p, td_part, rows * slabs, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (t_frob && hipMemcpy(dOf.p, t_frob, rows, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (t_div && hipMemcpy(dOd.p, t_div, rows, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	const hipError_t err = launch_beta_update<T>((T*)dP.p, num_part ? (const T*)dNum.p : nullptr, den_part ? (const T*)dDen.p : nullptr, (long)out_pad * RP, slabs,
+	                                             dsum ? (const T*)dD.p : nullptr, RP, r, out_pad, out_valid, std::numeric_limits<T>::epsilon(), beta_value, (T)l1d, (T)l2d,
+	                                             update != 0, (T*)dSq.p, (T*)dSm.p, tf_part ? (const T*)dTf.p : nullptr, td_part ? (const T*)dTd.p : nullptr, out_pad,
+	                                             t_frob ? (T*)dOf.p : nullptr, t_div ? (T*)dOd.p : nullptr, nullptr, weighted != 0);
+	if (err == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
+	if (err != hipSuccess || hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (hipMemcpy(P, dP.p, panel, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(sumsq_part, dSq.p, sums, hipMemcpyDeviceToHost) != hipSuccess ||
+	    hipMemcpy(sum_part, dSm.p, sums, hipMemcpyDeviceToHost) != hipSuccess)
+		return NMFAMD_HIP_ERROR;
+	if (t_frob && hipMemcpy(t_frob, dOf.p, rows, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (t_div && hipMemcpy(t_div, dOd.p, rows, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
+
 // Test entries of kernels_sparse.hip: one launch each on caller-built arrays, eps = epsilon of T as in Engine::iterate_kl.  The arguments are checked as far as the
 // buffer sizes and the indices go (a stored index outside the gathered panel would be read on the device); which padded ranks run is the launchers' decision.
 // Output arrays are uploaded as the caller filled them and are not cleared, so a test sees what a launch wrote and what it left alone.
@@ -1305,6 +1401,28 @@ int nmfamd_op_beta_update_rows_f32(float* P, float* Aacc, float* Bacc, const flo
 int nmfamd_op_beta_update_rows_f64(double* P, double* Aacc, double* Bacc, const double* num_part, const double* den_part, int slabs, const double* dsum, int RP, int r,
                                    int out_pad, int out_valid, double beta, double l1, double l2, int online, double rho, int flush, double* sum_part) {
 	return op_beta_update_rows<double>(P, Aacc, Bacc, num_part, den_part, slabs, dsum, RP, r, out_pad, out_valid, beta, l1, l2, online, rho, flush, sum_part);
+}
+
+int nmfamd_op_beta_fused_f32(const float* A, const float* B, const float* X, const float* Omega, long ldx, int RP, int out_pad, int out_valid, int red_pad, int red_valid,
+                             double beta, int update, int terms, int mixed, int force_slabs, float* num_part, float* den_part, float* tf_part, float* td_part, int* plan) {
+	return op_beta_fused<float>(A, B, X, Omega, ldx, RP, out_pad, out_valid, red_pad, red_valid, beta, update, terms, mixed, force_slabs, num_part, den_part, tf_part, td_part, plan);
+}
+
+int nmfamd_op_beta_fused_f64(const double* A, const double* B, const double* X, const double* Omega, long ldx, int RP, int out_pad, int out_valid, int red_pad, int red_valid,
+                             double beta, int update, int terms, int mixed, int force_slabs, double* num_part, double* den_part, double* tf_part, double* td_part, int* plan) {
+	return op_beta_fused<double>(A, B, X, Omega, ldx, RP, out_pad, out_valid, red_pad, red_valid, beta, update, terms, mixed, force_slabs, num_part, den_part, tf_part, td_part, plan);
+}
+
+int nmfamd_op_beta_update_f32(float* P, const float* num_part, const float* den_part, int slabs, const float* dsum, int RP, int r, int out_pad, int out_valid, double beta,
+                              double l1, double l2, int weighted, int update, const float* tf_part, const float* td_part, float* sumsq_part, float* sum_part, float* t_frob,
+                              float* t_div) {
+	return op_beta_update<float>(P, num_part, den_part, slabs, dsum, RP, r, out_pad, out_valid, beta, l1, l2, weighted, update, tf_part, td_part, sumsq_part, sum_part, t_frob, t_div);
+}
+
+int nmfamd_op_beta_update_f64(double* P, const double* num_part, const double* den_part, int slabs, const double* dsum, int RP, int r, int out_pad, int out_valid, double beta,
+                              double l1, double l2, int weighted, int update, const double* tf_part, const double* td_part, double* sumsq_part, double* sum_part, double* t_frob,
+                              double* t_div) {
+	return op_beta_update<double>(P, num_part, den_part, slabs, dsum, RP, r, out_pad, out_valid, beta, l1, l2, weighted, update, tf_part, td_part, sumsq_part, sum_part, t_frob, t_div);
 }
 
 int nmfamd_op_beta_half_step_f32(float* A, const float* B, const float* X, long ldx, int RP, int r, int out_pad, int out_valid, int red_pad, int red_valid, int beta,

@@ -1100,6 +1100,81 @@ def op_beta_update_rows(P: np.ndarray, num_part: np.ndarray, den: np.ndarray, r:
     return {"P": P, "A": A, "B": B, "sum_part": sm}
 
 
+def op_beta_fused(A: np.ndarray, B: np.ndarray, X: np.ndarray, out_valid: int, red_valid: int, beta: float, *, update: bool = True, terms: bool = False,
+                  Omega: Optional[np.ndarray] = None, mixed: bool = False, force_slabs: int = 0, fill=np.nan):
+    """The fused launch of a half-step alone (nmfamd_op_beta_fused_*: launch_beta_fused; with Omega launch_beta_fused_weighted; with mixed, float32 only,
+    launch_beta_fused_bf16) under the plan of op_beta_half_step*: A (out_pad, RP), B (red_pad, RP), X and Omega (out_pad, ldx >= red_pad).  Every output starts
+    as `fill`, so what the launch does not write shows.  Returns a dict: `num_part`, `den_part` (slabs, out_pad, RP), `tf_part`, `td_part` ((slabs, out_pad); None
+    without terms) and the plan `slabs`, `tiles`, `tiles_per_slab`, `bo`, `kt`."""
+    dt = np.dtype(A.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("float32 or float64")
+    A = np.ascontiguousarray(A, dtype=dt); B = np.ascontiguousarray(B, dtype=dt); X = np.ascontiguousarray(X, dtype=dt)
+    out_pad, RP = A.shape
+    red_pad = B.shape[0]
+    if B.shape[1] != RP or X.shape[0] != out_pad or X.shape[1] < red_pad:
+        raise ValueError("shapes: A (out_pad, RP); B (red_pad, RP); X (out_pad, >= red_pad)")
+    if Omega is not None:
+        Omega = np.ascontiguousarray(Omega, dtype=dt)
+        if Omega.shape != X.shape:
+            raise ValueError("Omega must have the shape of X")
+    fn = library().nmfamd_op_beta_fused_f32 if dt == np.float32 else library().nmfamd_op_beta_fused_f64
+    plan = (C.c_int * 5)()
+    how = (C.c_long(X.shape[1]), RP, out_pad, int(out_valid), red_pad, int(red_valid), C.c_double(beta), int(bool(update)), int(bool(terms)), int(bool(mixed)),
+           int(force_slabs))
+    st = fn(_p(A), _p(B), _p(X), _p(Omega), *how, None, None, None, None, plan)
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_beta_fused")
+    slabs = plan[0]
+    num = np.full((slabs, out_pad, RP), fill, dt); den = np.full((slabs, out_pad, RP), fill, dt)
+    tf = np.full((slabs, out_pad), fill, dt) if terms else None
+    td = np.full((slabs, out_pad), fill, dt) if terms else None
+    st = fn(_p(A), _p(B), _p(X), _p(Omega), *how, _p(num), _p(den), _p(tf), _p(td), plan)
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_beta_fused")
+    return {"num_part": num, "den_part": den, "tf_part": tf, "td_part": td, "slabs": plan[0], "tiles": plan[1], "tiles_per_slab": plan[2], "bo": plan[3], "kt": plan[4]}
+
+
+def op_beta_update(P: np.ndarray, num_part: Optional[np.ndarray], den: Optional[np.ndarray], r: int, out_valid: int, beta: float, *, l1: float = 0.0, l2: float = 0.0,
+                   weighted: bool = False, update: bool = True, terms=None, slabs: Optional[int] = None, fill=np.nan):
+    """launch_beta_update alone (nmfamd_op_beta_update_*) on caller-built partial panels, in op_beta_update_rows's convention: P (out_pad, RP), num_part (slabs,
+    out_pad, RP), den either (slabs, out_pad, RP) partial denominators or the RP values of dsum (the unweighted beta = 1).  terms = (tf_part, td_part), each (slabs,
+    out_pad): the launch also adds them into `t_frob`, `t_div`.  update=False: the terms only.  weighted: the launch of the weighted engines.  slabs: only where
+    neither num_part nor terms gives it.  Returns a dict: `P` (a new array), `sumsq_part`, `sum_part` ((out_pad // 128, RP)), `t_frob`, `t_div` (out_pad values; None
+    without terms); what the launch does not write is `fill`."""
+    dt = np.dtype(P.dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("float32 or float64")
+    P = np.array(P, dtype=dt, order="C")
+    out_pad, RP = P.shape
+    num_part = None if num_part is None else np.ascontiguousarray(num_part, dtype=dt)
+    den = None if den is None else np.ascontiguousarray(den, dtype=dt)
+    tf = td = None
+    if terms is not None:
+        tf = np.ascontiguousarray(terms[0], dtype=dt); td = np.ascontiguousarray(terms[1], dtype=dt)
+        if tf.ndim != 2 or tf.shape[1] != out_pad or td.shape != tf.shape:
+            raise ValueError("terms: two (slabs, out_pad) arrays")
+    if slabs is None:
+        slabs = num_part.shape[0] if num_part is not None else tf.shape[0]
+    for a in (num_part, den if den is not None and den.ndim != 1 else None):
+        if a is not None and a.shape != (slabs, out_pad, RP):
+            raise ValueError("shapes: P (out_pad, RP); num_part and den (slabs, out_pad, RP)")
+    if tf is not None and tf.shape[0] != slabs:
+        raise ValueError("terms: as many slabs as num_part")
+    vec = den is not None and den.ndim == 1
+    if vec and den.shape != (RP,):
+        raise ValueError("den: (slabs, out_pad, RP) partial denominators, or the RP values of dsum")
+    sq = np.full((out_pad // 128, RP), fill, dt); sm = np.full((out_pad // 128, RP), fill, dt)
+    of = np.full(out_pad, fill, dt) if terms is not None else None
+    od = np.full(out_pad, fill, dt) if terms is not None else None
+    fn = library().nmfamd_op_beta_update_f32 if dt == np.float32 else library().nmfamd_op_beta_update_f64
+    st = fn(_p(P), _p(num_part), None if vec else _p(den), int(slabs), _p(den) if vec else None, RP, int(r), out_pad, int(out_valid), C.c_double(beta), C.c_double(l1),
+            C.c_double(l2), int(bool(weighted)), int(bool(update)), _p(tf), _p(td), _p(sq), _p(sm), _p(of), _p(od))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_beta_update")
+    return {"P": P, "sumsq_part": sq, "sum_part": sm, "t_frob": of, "t_div": od}
+
+
 def op_hals_normalize(Wt: np.ndarray, H: np.ndarray, sumsq_part: np.ndarray):
     """The HALS column normalisation (nmfamd_op_hals_normalize_*): Wt (mpad, RP) and H (npad, RP) panels, sumsq_part (parts, RP) partial
     sums of squares.  Returns a dict: `Wt`, `H` (new arrays; the inputs are not changed)."""

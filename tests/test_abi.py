@@ -51,6 +51,12 @@ def test_panel_update_test_entries_are_exported():
     assert C.sizeof(_PanelFused) == 72 and _PanelFused.off.offset == 32 and _PanelFused.smooth_out.offset == 56
 
 
+def test_beta_kernel_test_entries_are_exported():
+    lib = na.library()
+    for name in ("nmfamd_op_beta_fused_f32", "nmfamd_op_beta_fused_f64", "nmfamd_op_beta_update_f32", "nmfamd_op_beta_update_f64"):
+        assert name in _declared_c_symbols("nmfgpu_amd.h") and hasattr(lib, name), name
+
+
 def test_inverse_test_entries_are_exported():
     lib = na.library()
     for name in ("nmfamd_op_inverse_f32", "nmfamd_op_inverse_ex_f32", "nmfamd_op_inverse_ex_f64"):
