@@ -193,13 +193,28 @@ enum { NMFAMD_COLUMN_MAJOR = 0, NMFAMD_ROW_MAJOR = 1 };
  * evaluates the value rule of a dense divergence engine in the same pass; everything behind that image is the host upload's code, so the resident images, the
  * tr(V^T V) terms and every later result equal those of nmfamd_engine_upload_dense on the same values bit for bit.  Statuses and nmfamd_engine_last_error texts
  * are the host entry's: NMFAMD_INVALID_ARGUMENT for a value that breaks the rule (the engine is then without a valid V), NMFAMD_VALUE_RANGE as there.
- * Refused on an engine with sparse_compute or missing_values (its dense input becomes triplets on the host) and on a weighted engine. */
+ * Refused on an engine with sparse_compute or missing_values (nmfamd_engine_upload_dense_device_stored is the entry of those) and on a weighted engine. */
 NMFAMD_API int nmfamd_engine_upload_dense_device(nmfamd_engine* e, const void* V, long ld, int layout);
 /* Replaces nmfamd_engine_upload_dense_weighted: V and Omega (m x n each, layouts independent of each other) in device memory.  The joint value rule is evaluated
  * on the device; with more than one kind of violation the one reported is: a bad weight, then a bad entry of V, then "at least one weight has to be > 0".  The
  * resident images equal the host entry's bit for bit; the sum of the weights (rmsd's divisor) is added in double as one partial per 64 x 64 tile and then in tile
  * order -- a function of the input and the shape only, within m n 2^-53 (relative) of the host entry's sum.  Refused on an engine that is not weighted. */
 NMFAMD_API int nmfamd_engine_upload_dense_weighted_device(nmfamd_engine* e, const void* V, long ldv, int layout_v, const void* Omega, long ldo, int layout_o);
+/* Replaces nmfamd_engine_upload_sparse for arrays in device memory (format, a, b, base as there; a and b are 32-bit).  The pointer check covers nnz elements
+ * (values), nnz ints (b) and nnz (COO) or outer + 1 ints (a); a null values / b is taken where nnz = 0.  Refusals, statuses and nmfamd_engine_last_error texts are
+ * the host entry's word for word; its value rules (a dense divergence engine with beta > 0: finite and >= 0; missing_values: finite, at least one entry) are
+ * evaluated by a kernel.  sparse_compute / missing_values engines copy the arrays device-to-device into arrays the image builder owns and build the CSR and CSC
+ * images there (nmfamd_geometry.sparse_setup = 1); an input that builder hands back -- an entry outside the matrix, pointer arrays that do not ascend, a row or
+ * column longer than 8192 entries, nnz = 0 -- and NMFAMD_SPARSE_SETUP=host cost a download of the arrays and take the host entry's path (sparse_setup = 0).  Every
+ * other engine densifies the arrays where they lie.  The result equals the host entry's on the same values bit for bit (densifying engines: for unique
+ * coordinates; three or more duplicates of one coordinate are added in no fixed order, there as here). */
+NMFAMD_API int nmfamd_engine_upload_sparse_device(nmfamd_engine* e, int format, const void* values, const int* a, const int* b, long nnz, int base);
+/* Dense V (m x n, layout and ld as for nmfamd_engine_upload_dense_device) in device memory on an engine with sparse_compute or missing_values -- the engines that
+ * refuse nmfamd_engine_upload_dense_device; every other engine refuses this entry.  The stored entries are those of nmfamd_engine_upload_dense: with missing_values
+ * every entry that is not NaN, zeros included (an infinite entry, and a V without an observed entry, are refused with the host entry's texts), otherwise every
+ * entry != 0.  Both images are compacted on the device (count, scan, scatter: no limit on the length of a row or column; sparse_setup = 1) and equal the host
+ * entry's bit for bit, as does everything computed from them. */
+NMFAMD_API int nmfamd_engine_upload_dense_device_stored(nmfamd_engine* e, const void* V, long ld, int layout);
 /* Replace nmfamd_engine_set_factors / _get_factors: W (m x r) and H (r x n) in device memory, each in its own layout; a null pointer leaves that factor (its ld and
  * layout are then not looked at).  set invalidates what nmfamd_engine_set_factors invalidates and writes exact zeros into the panels' padding; get returns what
  * nmfamd_engine_get_factors returns (nsNMF: W S) and writes the m x r / r x n block only -- bytes in the gap of ld stay as they are. */

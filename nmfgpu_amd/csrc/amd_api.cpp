@@ -355,6 +355,16 @@ int nmfamd_engine_upload_dense_device(nmfamd_engine* e, const void* V, long ld, 
 	                   [&](Engine<double>& g) { return g.upload_dense_device((const double*)V, ld, layout); });
 }
 
+int nmfamd_engine_upload_sparse_device(nmfamd_engine* e, int format, const void* values, const int* a, const int* b, long nnz, int base) {
+	return dispatch(e, [&](Engine<float>& g) { return g.upload_sparse_from_device(format, (const float*)values, a, b, nnz, base); },
+	                   [&](Engine<double>& g) { return g.upload_sparse_from_device(format, (const double*)values, a, b, nnz, base); });
+}
+
+int nmfamd_engine_upload_dense_device_stored(nmfamd_engine* e, const void* V, long ld, int layout) {
+	return dispatch(e, [&](Engine<float>& g) { return g.upload_dense_device_stored((const float*)V, ld, layout); },
+	                   [&](Engine<double>& g) { return g.upload_dense_device_stored((const double*)V, ld, layout); });
+}
+
 int nmfamd_engine_upload_dense_weighted_device(nmfamd_engine* e, const void* V, long ldv, int layout_v, const void* Omega, long ldo, int layout_o) {
 	return dispatch(e, [&](Engine<float>& g) { return g.upload_dense_weighted_device((const float*)V, ldv, layout_v, (const float*)Omega, ldo, layout_o); },
 	                   [&](Engine<double>& g) { return g.upload_dense_weighted_device((const double*)V, ldv, layout_v, (const double*)Omega, ldo, layout_o); });

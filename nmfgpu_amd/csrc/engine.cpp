@@ -744,15 +744,31 @@ Status Engine<T>::check_device_matrix(const char* name, const void* p, long ld, 
 	if (layout != 0 && layout != 1) return refuse(n + ": layout has to be 0 (column-major) or 1 (row-major)");
 	const long inner = layout == 0 ? rows : cols, outer = layout == 0 ? cols : rows;
 	if (ld < inner) return refuse(n + ": leading dimension below the " + (layout == 0 ? "row count (column-major)" : "column count (row-major)"));
-	if ((uintptr_t)p % sizeof(T) != 0) return refuse(n + ": pointer not aligned to the element size");
+	const unsigned long long elems = outer > 0 ? (unsigned long long)(outer - 1) * (unsigned long long)ld + (unsigned long long)inner : 0;
+	return check_device_extent(n, p, sizeof(T), elems, "the extent (outer - 1) * ld + inner");
+}
+
+// ... of a caller's device array of `count` elements (a null pointer is taken where count is 0)
+template <typename T>
+Status Engine<T>::check_device_vector(const char* name, const void* p, size_t elem, long count) {
+	const std::string n(name);
+	if (count <= 0) return ST_OK;
+	if (p == nullptr) return refuse(n + ": null pointer");
+	return check_device_extent(n, p, elem, (unsigned long long)count, "the array of " + std::to_string(count) + " elements");
+}
+
+// What both have in common, over the element size: p (not null) is aligned to `elem`, device memory of the engine's device, and `elems` elements from p lie inside
+// its allocation
+template <typename T>
+Status Engine<T>::check_device_extent(const std::string& n, const void* p, size_t elem, unsigned long long elems, const std::string& extent) {
+	if ((uintptr_t)p % elem != 0) return refuse(n + ": pointer not aligned to the element size");
 	int kind = 0, dev = -1; unsigned long long avail = 0;
 	device_pointer_info(p, &kind, &dev, &avail);
 	if (kind == 0) return refuse(n + ": not device memory (a pointer the HIP runtime does not know: host memory goes through the host entry)");
 	if (kind == 2) return refuse(n + ": not device memory (pinned host memory goes through the host entry)");
 	if (kind != 1) return refuse(n + ": not device memory (managed or array memory is not taken)");
 	if (dev != device_) return refuse(n + ": memory of another device than the engine's");
-	const unsigned long long need = ((unsigned long long)(outer - 1) * (unsigned long long)ld + (unsigned long long)inner) * sizeof(T);
-	if (outer > 0 && need > avail) return refuse(n + ": the extent (outer - 1) * ld + inner reaches past the end of the allocation");
+	if (elems > 0 && elems * elem > avail) return refuse(n + ": " + extent + " reaches past the end of the allocation");
 	return ST_OK;
 }
 
@@ -825,44 +841,27 @@ Status Engine<T>::get_factors_device(T* W, long ldw, int layout_w, T* H, long ld
 
 template <typename T>
 Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const int* b, long nnz, int base) {
-	if (format < 1 || format > 3 || nnz < 0 || (nnz > 0 && (!values || !a || !b))) return ST_INVALID;
-	if (weighted_) { last_error_ = "weighted NMF: sparse input is refused; upload V dense together with its weights (upload_dense_weighted)"; return ST_INVALID; }
+	if (nnz > 0 && (!values || !a || !b)) return ST_INVALID;
+	if (Status st = refuse_sparse_input(format, nnz)) return st;
 	if (beta_dense_) {
-		// the stored entries are densified (launch_densify below); an unstored entry is a zero, which a divergence with beta <= 0 (Itakura-Saito) does not take
 		beta_uploaded_ = false;
-		if (beta_ <= 0) {
-			last_error_ = beta_ == 0 ? "Itakura-Saito divergence: sparse input is refused (unstored entries are zeros); upload V dense"
-			                         : "beta-divergence with beta <= 0: sparse input is refused (unstored entries are zeros); upload V dense";
-			return ST_INVALID;
-		}
 		if (nnz > 0) { if (Status st = beta_check_values(values, 1, nnz, nnz)) return st; }
 	}
 	if (sparse_ && prm_.is_masked()) {
 		// missing values: every stored entry is observed (stored zeros too, which both image builders keep); its value must be finite, and there must be one
-		if (nnz == 0) { last_error_ = "missing values: no stored entry"; return ST_INVALID; }
+		if (nnz == 0) return refuse_sparse_values(SPARSE_NO_ENTRY);
 		for (long p = 0; p < nnz; ++p)
-			if (!std::isfinite(values[p])) { last_error_ = "missing values: a stored value is not finite"; return ST_INVALID; }
+			if (!std::isfinite(values[p])) return refuse_sparse_values(IMPORT_BAD_VALUE);
 	}
 	if (sparse_) {
-		// the images are built on the device (kernels_sparse_setup.hip); what that path does not cover -- entries outside the matrix (dropped below), pointer
+		// the images are built on the device (kernels_sparse_setup.hip); what that path does not cover -- entries outside the matrix (dropped by the host path), pointer
 		// arrays that do not ascend, a row or column longer than its LDS sort takes, no entries at all -- and NMFAMD_SPARSE_SETUP=host take the host path
-		const char* where = std::getenv("NMFAMD_SPARSE_SETUP");
-		if (!(where != nullptr && std::strcmp(where, "host") == 0) && nnz > 0) {
+		if (!sparse_setup_on_host() && nnz > 0) {
 			bool fallback = false;
 			const Status st = upload_sparse_device(format, values, a, b, nnz, base, &fallback);
 			if (!fallback) return st;
 		}
-		sparse_setup_on_device_ = false;
-		// expand to 0-based (row, column, value) triplets with the caller's index base applied exactly
-		// (reference: cusparseSetMatIndexBase, Matrix.h:158-160,184-186,215-217); out-of-range entries are dropped
-		std::vector<int> rows, cols; std::vector<T> vals;
-		rows.reserve(nnz); cols.reserve(nnz); vals.reserve(nnz);
-		auto push = [&](long i, long j, T v) { if (i >= 0 && i < m_ && j >= 0 && j < n_) { rows.push_back((int)i); cols.push_back((int)j); vals.push_back(v); } };
-		if (format == 1) { for (int i = 0; i < m_; ++i) for (long p = (long)a[i] - base; p < (long)a[i + 1] - base && p < nnz; ++p) if (p >= 0) push(i, (long)b[p] - base, values[p]); }
-		else if (format == 2) { for (int j = 0; j < n_; ++j) for (long p = (long)a[j] - base; p < (long)a[j + 1] - base && p < nnz; ++p) if (p >= 0) push((long)b[p] - base, j, values[p]); }
-		else { for (long p = 0; p < nnz; ++p) push((long)a[p] - base, (long)b[p] - base, values[p]); }
-		if (prm_.is_masked() && vals.empty()) { last_error_ = "missing values: no stored entry inside the matrix"; return ST_INVALID; }
-		return upload_triplets(rows, cols, vals);
+		return upload_sparse_on_host(format, values, a, b, nnz, base);
 	}
 	DeviceBuffers scratch;      // the caller's arrays on the device: freed on every way out
 	T* d_val = nullptr; int *d_a = nullptr, *d_b = nullptr;
@@ -889,6 +888,18 @@ Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const
 // source/common/Matrix.h:145-232).  *fallback: the input needs the host path (nothing of this engine's state has been touched then, except freed images).
 template <typename T>
 Status Engine<T>::upload_sparse_device(int format, const T* values, const int* a, const int* b, long nnz, int base, bool* fallback) {
+	return build_sparse_images(format, nnz, base, fallback, [&](T* d_val, size_t nv, int* d_a, size_t na, int* d_b, size_t nb) {
+		HIPX(hipMemcpyAsync(d_val, values, nv, hipMemcpyHostToDevice, stream_));
+		HIPX(hipMemcpyAsync(d_a, a, na, hipMemcpyHostToDevice, stream_));
+		HIPX(hipMemcpyAsync(d_b, b, nb, hipMemcpyHostToDevice, stream_));
+		return ST_OK;
+	});
+}
+
+// ... behind the copies: fill(d_val, bytes, d_a, bytes, d_b, bytes) brings the caller's arrays (host memory: upload_sparse; device memory: upload_sparse_from_device)
+// into device arrays this body owns -- which is what lets it adopt them as the CSR image where the input already is one
+template <typename T> template <typename Fill>
+Status Engine<T>::build_sparse_images(int format, long nnz, int base, bool* fallback, Fill fill) {
 	*fallback = false;
 	if (nnz >= (1l << 31)) return ST_INVALID;
 	const int outer = format == 1 ? m_ : n_;
@@ -897,8 +908,6 @@ Status Engine<T>::upload_sparse_device(int format, const T* values, const int* a
 	// scratch: freed on every way out
 	T* d_val = nullptr;
 	int *d_a = nullptr, *d_b = nullptr, *row = nullptr, *col = nullptr, *items = nullptr, *rowq = nullptr, *counts = nullptr, *small = nullptr;
-	T* d_vtv = nullptr;
-	double* d_colsum = nullptr;
 	DeviceBuffers scratch;
 	auto alloc = [&](auto** p, size_t bytes) { return scratch.device(p, std::max<size_t>(bytes, 16), false, stream_); };
 	auto image = [&](auto** p, size_t bytes) { return buffers_.device(p, bytes, false, stream_); };      // (a part of the engine's CSR / CSC images)
@@ -911,9 +920,7 @@ Status Engine<T>::upload_sparse_device(int format, const T* values, const int* a
 	HIPX(alloc(&d_val, nv)); HIPX(alloc(&d_a, sizeof(int) * (size_t)na)); HIPX(alloc(&d_b, ni));
 	HIPX(alloc(&row, ni)); HIPX(alloc(&col, ni));
 	HIPX(alloc(&counts, sizeof(int) * (size_t)segs)); HIPX(alloc(&small, sizeof(int) * 4));
-	HIPX(hipMemcpyAsync(d_val, values, nv, hipMemcpyHostToDevice, stream_));
-	HIPX(hipMemcpyAsync(d_a, a, sizeof(int) * (size_t)na, hipMemcpyHostToDevice, stream_));
-	HIPX(hipMemcpyAsync(d_b, b, ni, hipMemcpyHostToDevice, stream_));
+	if (Status st = fill(d_val, nv, d_a, sizeof(int) * (size_t)na, d_b, ni)) return st;
 	HIPX(hipMemsetAsync(small, 0, sizeof(int) * 4, stream_));
 	int* flags = small;                       // [0] flags, [1] longest row, [2] longest column
 	HIPX(launch_sp_expand(format, d_a, d_b, nnz, outer, base, m_, n_, row, col, flags, stream_));
@@ -950,7 +957,17 @@ Status Engine<T>::upload_sparse_device(int format, const T* values, const int* a
 	HIPX(launch_sp_gather_csc<T>(items, rowq, csr_val_, nnz, csc_idx_, csc_val_, stream_));
 	const bool two_pass = tuning_env("NMFAMD_KL_TWO_PASS") != nullptr;      // (round 1's two-pass KL step, a measurement switch: quotient buffers + the CSR -> CSC permutation)
 	if (two_pass) { csc_from_csr_ = items; buffers_.adopt(scratch, items); HIPX(image(&q_, nv)); HIPX(image(&q2_, nv)); }
-	// tr(V^T V) terms per column (accumulated in T like the trace kernel, in the image's order) and sum(V) for the KL divergence
+	return finish_sparse_images(nnz);
+}
+
+// What every device-side builder of the sparse images ends with (build_sparse_images, upload_dense_device_stored), the images in place:
+// tr(V^T V) terms per column (accumulated in T like the trace kernel, in the image's order) and sum(V) for the KL divergence, nnz_, the blocked KL gather
+template <typename T>
+Status Engine<T>::finish_sparse_images(long nnz) {
+	DeviceBuffers scratch;      // freed on every way out
+	T* d_vtv = nullptr;
+	double* d_colsum = nullptr;
+	auto alloc = [&](auto** p, size_t bytes) { return scratch.device(p, std::max<size_t>(bytes, 16), false, stream_); };
 	HIPX(alloc(&d_vtv, sizeof(T) * (size_t)n_)); HIPX(alloc(&d_colsum, sizeof(double) * (size_t)n_));
 	HIPX(launch_sp_col_sumsq<T>(csc_ptr_, csc_val_, n_, d_vtv, d_colsum, stream_));
 	h_vtv_.assign(n_, T(0));
@@ -966,6 +983,156 @@ Status Engine<T>::upload_sparse_device(int format, const T* values, const int* a
 	if (Status st = setup_kl_blocks()) return st;
 	HIPX(hipStreamSynchronize(stream_));
 	return ST_OK;
+}
+
+// What both forms of the sparse upload refuse before they look at an array: a format other than 1 ... 3 or nnz < 0 (no text), a weighted engine, a dense divergence
+// engine with beta <= 0 (which is then without a valid V, as after any refused upload of such an engine)
+template <typename T>
+Status Engine<T>::refuse_sparse_input(int format, long nnz) {
+	if (format < 1 || format > 3 || nnz < 0) return ST_INVALID;
+	if (weighted_) { last_error_ = "weighted NMF: sparse input is refused; upload V dense together with its weights (upload_dense_weighted)"; return ST_INVALID; }
+	if (beta_dense_ && beta_ <= 0) {
+		// the stored entries are densified (launch_densify); an unstored entry is a zero, which a divergence with beta <= 0 (Itakura-Saito) does not take
+		beta_uploaded_ = false;
+		last_error_ = beta_ == 0 ? "Itakura-Saito divergence: sparse input is refused (unstored entries are zeros); upload V dense"
+		                         : "beta-divergence with beta <= 0: sparse input is refused (unstored entries are zeros); upload V dense";
+		return ST_INVALID;
+	}
+	return ST_OK;
+}
+
+// ... and the value rules of a missing-values engine, by what was found (the host loop, or the flags of kernels_compact.hip)
+template <typename T>
+Status Engine<T>::refuse_sparse_values(int found) {
+	last_error_ = (found & SPARSE_NO_ENTRY) ? "missing values: no stored entry" : "missing values: a stored value is not finite";
+	return ST_INVALID;
+}
+
+template <typename T>
+bool Engine<T>::sparse_setup_on_host() const {
+	const char* where = std::getenv("NMFAMD_SPARSE_SETUP");
+	return where != nullptr && std::strcmp(where, "host") == 0;
+}
+
+// The host path of a sparse upload on a sparse engine, from host arrays: triplets, then the host's counting sorts
+template <typename T>
+Status Engine<T>::upload_sparse_on_host(int format, const T* values, const int* a, const int* b, long nnz, int base) {
+	sparse_setup_on_device_ = false;
+	// expand to 0-based (row, column, value) triplets with the caller's index base applied exactly
+	// (reference: cusparseSetMatIndexBase, Matrix.h:158-160,184-186,215-217); out-of-range entries are dropped
+	std::vector<int> rows, cols; std::vector<T> vals;
+	rows.reserve(nnz); cols.reserve(nnz); vals.reserve(nnz);
+	auto push = [&](long i, long j, T v) { if (i >= 0 && i < m_ && j >= 0 && j < n_) { rows.push_back((int)i); cols.push_back((int)j); vals.push_back(v); } };
+	if (format == 1) { for (int i = 0; i < m_; ++i) for (long p = (long)a[i] - base; p < (long)a[i + 1] - base && p < nnz; ++p) if (p >= 0) push(i, (long)b[p] - base, values[p]); }
+	else if (format == 2) { for (int j = 0; j < n_; ++j) for (long p = (long)a[j] - base; p < (long)a[j + 1] - base && p < nnz; ++p) if (p >= 0) push((long)b[p] - base, j, values[p]); }
+	else { for (long p = 0; p < nnz; ++p) push((long)a[p] - base, (long)b[p] - base, values[p]); }
+	if (prm_.is_masked() && vals.empty()) { last_error_ = "missing values: no stored entry inside the matrix"; return ST_INVALID; }
+	return upload_triplets(rows, cols, vals);
+}
+
+// upload_sparse for arrays in DEVICE memory of the engine's device, branch by branch (docs/DEVICE_IO.md, "Sparse input")
+template <typename T>
+Status Engine<T>::upload_sparse_from_device(int format, const T* values, const int* a, const int* b, long nnz, int base) {
+	if (Status st = refuse_sparse_input(format, nnz)) return st;
+	const int outer = format == 1 ? m_ : n_;
+	const long na = format == 3 ? nnz : (long)outer + 1;
+	if (Status st = check_device_vector("values", values, sizeof(T), nnz)) return st;
+	if (Status st = check_device_vector("a", a, sizeof(int), na)) return st;
+	if (Status st = check_device_vector("b", b, sizeof(int), nnz)) return st;
+	if (beta_dense_) beta_uploaded_ = false;
+	HIPX(hipDeviceSynchronize());      // whatever stream produced the arrays has finished
+	const bool masked = sparse_ && prm_.is_masked();
+	if (masked && nnz == 0) return refuse_sparse_values(SPARSE_NO_ENTRY);
+	if ((beta_dense_ || masked) && nnz > 0) {
+		int flags = 0;
+		HIPX(hipMemsetAsync(range_flag_, 0, sizeof(int), stream_));
+		HIPX(launch_sparse_value_rule<T>(values, nnz, beta_dense_ ? 1 : 2, range_flag_, stream_));
+		HIPX(hipMemcpyAsync(&flags, range_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_));
+		HIPX(hipStreamSynchronize(stream_));
+		if (flags & IMPORT_BAD_VALUE) {
+			if (masked) return refuse_sparse_values(IMPORT_BAD_VALUE);
+			last_error_ = beta_value_fault(); return ST_INVALID;
+		}
+	}
+	if (sparse_) {
+		if (!sparse_setup_on_host() && nnz > 0) {
+			bool fallback = false;
+			const Status st = build_sparse_images(format, nnz, base, &fallback, [&](T* d_val, size_t nv, int* d_a, size_t nab, int* d_b, size_t nb) {
+				HIPX(hipMemcpyAsync(d_val, values, nv, hipMemcpyDeviceToDevice, stream_));
+				HIPX(hipMemcpyAsync(d_a, a, nab, hipMemcpyDeviceToDevice, stream_));
+				HIPX(hipMemcpyAsync(d_b, b, nb, hipMemcpyDeviceToDevice, stream_));
+				return ST_OK;
+			});
+			if (!fallback) return st;
+		}
+		// an input the device builder hands back (or NMFAMD_SPARSE_SETUP=host): the arrays come down and the host path runs as it is
+		std::vector<T> h_val((size_t)nnz);
+		std::vector<int> h_a((size_t)na), h_b((size_t)nnz);
+		if (nnz > 0) {
+			HIPX(hipMemcpyAsync(h_val.data(), values, sizeof(T) * (size_t)nnz, hipMemcpyDeviceToHost, stream_));
+			HIPX(hipMemcpyAsync(h_b.data(), b, sizeof(int) * (size_t)nnz, hipMemcpyDeviceToHost, stream_));
+		}
+		if (na > 0) HIPX(hipMemcpyAsync(h_a.data(), a, sizeof(int) * (size_t)na, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipStreamSynchronize(stream_));
+		return upload_sparse_on_host(format, h_val.data(), h_a.data(), h_b.data(), nnz, base);
+	}
+	// a densifying engine: launch_densify reads the caller's arrays where they lie (k_densify indexes values and idx below nnz and ptr below outer + 1 only -- the
+	// extents checked above -- and its stores are guarded by the matrix's bounds)
+	return upload_image(false, [&](T* Vcol) {
+		HIPX(hipMemsetAsync(Vcol, 0, sizeof(T) * (size_t)(mpad_ * npad_), stream_));
+		if (format == 3) HIPX(launch_densify<T>(3, values, nullptr, a, b, nnz, 0, base, Vcol, mpad_, m_, n_, stream_));
+		else HIPX(launch_densify<T>(format, values, a, b, nullptr, nnz, outer, base, Vcol, mpad_, m_, n_, stream_));
+		return ST_OK;
+	});
+}
+
+// Dense V in DEVICE memory on a sparse engine: the stored entries of upload_dense compacted into both images on the device (kernels_compact.hip: count, scan,
+// scatter -- no sort, so no limit on a row's or a column's length), then the tail of the sparse builder
+template <typename T>
+Status Engine<T>::upload_dense_device_stored(const T* V, long ld, int layout) {
+	if (weighted_) { last_error_ = "weighted NMF: V is uploaded together with its weights (upload_dense_weighted)"; return ST_INVALID; }
+	if (!sparse_) { last_error_ = "device upload of the stored entries: only an engine with 'sparseCompute' or 'missingValues' takes it; use nmfamd_engine_upload_dense_device"; return ST_INVALID; }
+	if (Status st = check_device_matrix("V", V, ld, layout, m_, n_)) return st;
+	HIPX(hipDeviceSynchronize());      // whatever stream produced V has finished
+	const int masked = prm_.is_masked() ? 1 : 0;
+	const long nr = compact_row_counts(m_, n_), nc = compact_col_counts(m_, n_);
+	if (nr >= (1l << 31) - 1 || nc >= (1l << 31) - 1) return ST_INVALID;
+	DeviceBuffers scratch;      // freed on every way out
+	int *rowcnt = nullptr, *colcnt = nullptr, *off_r = nullptr, *off_c = nullptr, *small = nullptr;
+	unsigned long long* total = nullptr;
+	auto alloc = [&](auto** p, size_t bytes) { return scratch.device(p, std::max<size_t>(bytes, 16), false, stream_); };
+	auto image = [&](auto** p, size_t bytes) { return buffers_.device(p, bytes, false, stream_); };
+	HIPX(alloc(&rowcnt, sizeof(int) * (size_t)nr)); HIPX(alloc(&colcnt, sizeof(int) * (size_t)nc));
+	HIPX(scratch.device(&total, sizeof(unsigned long long), true, stream_));
+	HIPX(hipMemsetAsync(range_flag_, 0, sizeof(int), stream_));
+	HIPX(launch_compact_count<T>(V, ld, layout, m_, n_, masked, rowcnt, colcnt, range_flag_, total, stream_));
+	int flags = 0;
+	unsigned long long h_total = 0;
+	HIPX(hipMemcpyAsync(&flags, range_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_));
+	HIPX(hipMemcpyAsync(&h_total, total, sizeof(h_total), hipMemcpyDeviceToHost, stream_));
+	HIPX(hipStreamSynchronize(stream_));
+	// (up to here nothing of the engine's state has changed; the texts are upload_dense's)
+	if (flags & IMPORT_BAD_VALUE) { last_error_ = "missing values: V holds an infinite value (NaN marks a missing entry)"; return ST_INVALID; }
+	if (masked && h_total == 0) { last_error_ = "missing values: V has no observed entry"; return ST_INVALID; }
+	if (h_total >= (1ull << 31)) return ST_INVALID;
+	const long nnz = (long)h_total;
+
+	buffers_.release(csr_ptr_, csr_idx_, csc_ptr_, csc_idx_, csc_from_csr_, csr_val_, csc_val_, q_, q2_);
+	nnz_ = 0;
+	HIPX(alloc(&off_r, sizeof(int) * (size_t)(nr + 1))); HIPX(alloc(&off_c, sizeof(int) * (size_t)(nc + 1))); HIPX(alloc(&small, sizeof(int) * 4));
+	HIPX(launch_sp_scan(rowcnt, (int)nr, off_r, small, stream_));
+	HIPX(launch_sp_scan(colcnt, (int)nc, off_c, small + 1, stream_));
+	const size_t ni = sizeof(int) * (size_t)std::max<long>(nnz, 1), nv = sizeof(T) * (size_t)std::max<long>(nnz, 1);
+	HIPX(image(&csr_ptr_, sizeof(int) * (size_t)(m_ + 1)));
+	HIPX(image(&csc_ptr_, sizeof(int) * (size_t)(n_ + 1)));
+	HIPX(image(&csr_idx_, ni)); HIPX(image(&csc_idx_, ni));
+	HIPX(image(&csr_val_, nv)); HIPX(image(&csc_val_, nv));
+	// (the quotient buffers and the CSR -> CSC permutation only serve round 1's two-pass KL step, a measurement switch)
+	const bool two_pass = tuning_env("NMFAMD_KL_TWO_PASS") != nullptr;
+	if (two_pass) { HIPX(image(&csc_from_csr_, ni)); HIPX(image(&q_, nv)); HIPX(image(&q2_, nv)); }
+	HIPX(launch_compact_pointers(off_r, off_c, m_, n_, csr_ptr_, csc_ptr_, stream_));
+	HIPX(launch_compact_scatter<T>(V, ld, layout, m_, n_, masked, off_r, off_c, nnz, csr_idx_, csr_val_, csc_idx_, csc_val_, csc_from_csr_, stream_));
+	return finish_sparse_images(nnz);
 }
 
 template <typename T>

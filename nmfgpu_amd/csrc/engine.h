@@ -223,6 +223,17 @@ public:
 	// for another layout; and on an engine with sparse_compute / missing_values (their dense input becomes triplets on the host).
 	Status upload_dense_device(const T* V, long ld, int layout);
 	Status upload_dense_weighted_device(const T* V, long ldv, int layout_v, const T* Omega, long ldo, int layout_o);
+	// upload_sparse with values, a and b in DEVICE memory (nmfamd_engine_upload_sparse_device), branch by branch: the host entry's refusals with its statuses and
+	// texts (the value rules evaluated by a kernel), the pointer checks and the ordering of upload_dense_device over nnz elements of T (values), nnz ints (b) and nnz
+	// (COO) or outer + 1 ints (a).  Sparse engines: the arrays are copied device-to-device into the arrays the image builder owns (build_sparse_images: the same code
+	// on the same bits as the host entry); an input the builder hands back, and NMFAMD_SPARSE_SETUP=host, cost a download and run the host path as it is.  Every
+	// other engine densifies the caller's arrays where they lie, inside the same upload_image fill.  Nothing of the caller's memory is kept or written.
+	Status upload_sparse_from_device(int format, const T* values, const int* a, const int* b, long nnz, int base);
+	// Dense V in DEVICE memory on an engine with sparse_compute / missing_values (nmfamd_engine_upload_dense_device_stored; every other engine refuses it): the
+	// stored entries of upload_dense -- missing values: not NaN, zeros included, an infinite entry refused; otherwise != 0 -- compacted into the CSR and CSC images by
+	// kernels_compact.hip (count, scan, scatter: no sort, no limit on a row's or column's length), then finish_sparse_images.  The images, the terms and every later
+	// result equal upload_dense's bit for bit (sum(V) of the KL divergence: added per column, then across columns).  Checks and ordering of upload_dense_device.
+	Status upload_dense_device_stored(const T* V, long ld, int layout);
 
 	// W: host m x r (ld), H: host r x n (ld).  Either pointer may be null (leave as is).  PanelState: factors_touched, then w_set / h_set for the factor given.
 	Status set_factors(const T* W, long ldw, const T* H, long ldh);
@@ -402,7 +413,14 @@ private:
 	Status finish_weighted_upload(double sum_w);     // ... and its tail: finish_upload(V_), Omt_, the synchronisation, sum_w_, beta_uploaded_
 	Status export_panel_w(bool want_w, const T** src);   // get_factors / get_factors_device: one-pass check, materialize_w, nsNMF's W S; *src = the panel to read W from
 	Status upload_triplets(std::vector<int>& rows, std::vector<int>& cols, std::vector<T>& vals);   // sparse mode: builds CSR + CSC on the host (the fall-back of upload_sparse_device)
-	Status upload_sparse_device(int format, const T* values, const int* a, const int* b, long nnz, int base, bool* fallback);   // ... on the device (kernels_sparse_setup.hip)
+	Status upload_sparse_device(int format, const T* values, const int* a, const int* b, long nnz, int base, bool* fallback);   // ... on the device (kernels_sparse_setup.hip), from HOST arrays: three copies, then ...
+	template <typename Fill> Status build_sparse_images(int format, long nnz, int base, bool* fallback, Fill fill);   // ... the builder on device arrays it owns; fill copies the caller's arrays into them
+	Status finish_sparse_images(long nnz);            // the tail of every device-side builder: tr(V^T V) terms, sum_v_, nnz_, sparse_setup_on_device_, setup_kl_blocks
+	Status upload_sparse_on_host(int format, const T* values, const int* a, const int* b, long nnz, int base);   // host arrays -> triplets -> upload_triplets
+	enum { SPARSE_NO_ENTRY = 8 };                     // (beside the IMPORT_* flags of kernels.h)
+	Status refuse_sparse_input(int format, long nnz); // what both forms of the sparse upload refuse before they look at an array
+	Status refuse_sparse_values(int found);           // ... and on a missing-values engine: SPARSE_NO_ENTRY, or IMPORT_BAD_VALUE for a value that is not finite
+	bool sparse_setup_on_host() const;                // NMFAMD_SPARSE_SETUP=host
 	Status setup_kl_blocks();
 	bool sparse_setup_on_device_ = false;
 	Status iterate_kl(bool compute_error);            // KL-divergence multiplicative update (sparse mode)
@@ -415,6 +433,8 @@ private:
 	const char* beta_value_fault() const;             // ... the text of a violation
 	// the check of a caller's device matrix (rows x cols, layout, ld) before any device work: ST_OK, or ST_INVALID with last_error() naming `name` and what is wrong
 	Status check_device_matrix(const char* name, const void* p, long ld, int layout, long rows, long cols);
+	Status check_device_vector(const char* name, const void* p, size_t elem, long count);   // ... of a device array of `count` elements of `elem` bytes (null taken where count is 0)
+	Status check_device_extent(const std::string& name, const void* p, size_t elem, unsigned long long elems, const std::string& extent);   // what the two share, over the element size
 	Status refuse(std::string text) { error_text_ = std::move(text); last_error_ = error_text_.c_str(); return ST_INVALID; }
 	std::string error_text_;                          // owns a composed last_error_ text
 	int device_ = -1;                                 // the HIP device the buffers live on (allocate_buffers)

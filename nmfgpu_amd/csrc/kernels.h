@@ -372,6 +372,25 @@ hipError_t launch_import_panel(const T* src, long ld, int layout, bool is_w, int
 template <typename T>
 hipError_t launch_export_panel(const T* panel, int RP, long len_pad, bool is_w, int r, int len, T* dst, long ld, int layout, hipStream_t stream);
 
+// ---- device-resident input of the sparse engines (kernels_compact.hip, docs/DEVICE_IO.md) ----
+// A dense src (rows x cols, layout and ld as above, DEVICE memory, read only) compacted into the CSR and CSC images of its stored entries -- masked: every entry that
+// is not NaN (an infinite one sets IMPORT_BAD_VALUE in *flags), otherwise every entry != 0.  Count: rowcnt[i][tile column] (compact_row_counts ints) and
+// colcnt[j][tile row] (compact_col_counts ints), tiles of 64 x 64, every count written once; *total (zeroed by the caller) += the number of stored entries.
+long compact_row_counts(int rows, int cols);
+long compact_col_counts(int rows, int cols);
+template <typename T>
+hipError_t launch_compact_count(const T* src, long ld, int layout, int rows, int cols, int masked, int* rowcnt, int* colcnt, int* flags, unsigned long long* total, hipStream_t stream);
+// off_r / off_c: the exclusive scans of rowcnt / colcnt with the total behind the last element (launch_sp_scan).  csr_ptr[i] = off_r[i][0], csr_ptr[rows] = the total ...
+hipError_t launch_compact_pointers(const int* off_r, const int* off_c, int rows, int cols, int* csr_ptr, int* csc_ptr, hipStream_t stream);
+// ... and the entries: CSR rows ascending in their columns, CSC columns ascending in their rows; from_csr (or null): the CSR position of every CSC entry.  nnz: the
+// total of the count; no position outside [0, nnz) is written.
+template <typename T>
+hipError_t launch_compact_scatter(const T* src, long ld, int layout, int rows, int cols, int masked, const int* off_r, const int* off_c, long nnz, int* csr_idx, T* csr_val,
+                                  int* csc_idx, T* csc_val, int* from_csr, hipStream_t stream);
+// The value rules of a sparse upload over values[0 .. nnz) in DEVICE memory: rule 1 every value finite and >= 0, rule 2 finite; a violation sets IMPORT_BAD_VALUE.
+template <typename T>
+hipError_t launch_sparse_value_rule(const T* values, long nnz, int rule, int* flags, hipStream_t stream);
+
 // format: 1 CSR (ptr = rowPtr, idx = column indices), 2 CSC (ptr = columnPtr, idx = row indices),
 // 3 COO (idx = row indices, idx2 = column indices); outer = rows (CSR) / columns (CSC).
 template <typename T>
@@ -636,6 +655,9 @@ hipError_t launch_beta_online_reset(const T* P, T* Aacc, T* Bacc, long count, hi
 hipError_t launch_sp_expand(int format, const int* a, const int* b, long nnz, int outer, int base, int m, int n, int* row, int* col, int* flags, hipStream_t stream);
 // ptr[0 .. segments] = exclusive scan of the histogram of key[0 .. count) (counts: `segments` ints of scratch), maxlen[0] = the longest segment
 hipError_t launch_sp_histogram_scan(const int* key, long count, int segments, int* counts, int* ptr, int* maxlen, hipStream_t stream);
+// the scan alone, over counts somebody else wrote (kernels_compact.hip): ptr[0 .. count] = exclusive scan of counts[0 .. count), maxlen[0] = the largest count;
+// ptr and counts are different arrays
+hipError_t launch_sp_scan(const int* counts, int count, int* ptr, int* maxlen, hipStream_t stream);
 long sp_segment_sort_capacity();
 // items <- the positions 0 .. count - 1 grouped by key (segment s at [ptr[s], ptr[s + 1])), every segment ascending by (minor[item], item) -- by item alone
 // when minor == nullptr.  fill: `segments` ints of scratch; maxlen: the longest segment (<= sp_segment_sort_capacity())

@@ -186,7 +186,12 @@ hipError_t launch_sp_histogram_scan(const int* key, long count, int segments, in
 	return hipGetLastError();
 }
 
-long sp_segment_sort_capacity() { return 8192; }      // keys of 8 bytes in 64 KiB of LDS
+hipError_t launch_sp_scan(const int* counts, int count, int* ptr, int* maxlen, hipStream_t stream) {
+	hipLaunchKernelGGL(k_sp_scan, dim3(1), dim3(1024), 0, stream, counts, count, ptr, maxlen);
+	return hipGetLastError();
+}
+
+long sp_segment_sort_capacity() { return 8192; }     // keys of 8 bytes in 64 KiB of LDS
 
 hipError_t launch_sp_scatter_sort(const int* key, long count, int segments, const int* ptr, int* fill, int* items, const int* minor, int maxlen, hipStream_t stream) {
 	if (maxlen > sp_segment_sort_capacity()) return hipErrorInvalidValue;

@@ -121,6 +121,37 @@ def device_matrix(obj, shape, dtype, writable: bool = False):
     raise ValueError(f"strides {tuple(strides)} (bytes) of a {shape} array: exactly one of them has to be the item size and the other one at least the inner extent")
 
 
+def device_vector(obj, dtype, count: Optional[int] = None):
+    """(ptr, count) of a 1-D device array for the sparse device entry of Engine (docs/DEVICE_IO.md), the sibling of device_matrix: obj is anything with
+    __cuda_array_interface__ (nothing is imported, no library is called) that is contiguous -- no strides, or a stride equal to the item size -- or a raw
+    (ptr, count) pair, which the library checks.  TypeError for an object without the interface and for another dtype (an int64 index array -- torch's CSR default
+    -- has to be converted to int32); ValueError for another rank, a non-unit stride and a count other than `count`."""
+    dt = np.dtype(dtype)
+    if isinstance(obj, tuple) and len(obj) == 2:
+        ptr, have = int(obj[0] or 0), int(obj[1])
+    else:
+        iface = getattr(obj, "__cuda_array_interface__", None)
+        if not isinstance(iface, dict):
+            raise TypeError(f"a device array with __cuda_array_interface__ is needed, got {type(obj).__name__}")
+        try:
+            got = np.dtype(iface["typestr"])
+        except TypeError:
+            got = None
+        if got != dt:
+            hint = " (convert the index array to int32: tensor.to(torch.int32))" if got == np.dtype(np.int64) and dt == np.dtype(np.int32) else ""
+            raise TypeError(f"the device array must be {dt}, got {iface.get('typestr')!r}{hint}")
+        shape = tuple(iface["shape"])
+        if len(shape) != 1:
+            raise ValueError(f"a 1-D device array is needed, got shape {shape}")
+        strides = iface.get("strides")
+        if strides is not None and shape[0] > 1 and tuple(strides) != (dt.itemsize,):
+            raise ValueError(f"the device array must be contiguous (stride {dt.itemsize} bytes), got strides {tuple(strides)}")
+        ptr, have = int(iface["data"][0] or 0), int(shape[0])
+    if count is not None and have != int(count):
+        raise ValueError(f"the device array must have {int(count)} elements, got {have}")
+    return ptr, have
+
+
 def device_pointer_info(ptr: int) -> dict:
     """What the pointer check of the device entries sees (nmfamd_device_pointer_info; no kernel, no engine): {"kind": "unknown" | "device" | "pinned" | "other",
     "device": index or -1, "bytes_from_p": bytes from ptr to the end of its allocation (0 unless "device")}."""
@@ -339,7 +370,7 @@ class Engine:
         dtype and shape (m, n) with __cuda_array_interface__ -- torch tensors, row-major or column-major, views with a leading dimension included (device_matrix) --
         or raw (ptr, ld, layout) triples.  They are read where they lie, never written, and everything that follows equals upload() of the same values bit for
         bit (rmsd of a weighted engine: within m n 2^-53).  Work enqueued on any stream of the device is waited for first.  Engines with sparse_compute or
-        missing_values refuse it."""
+        missing_values refuse it: upload_device_stored is their entry."""
         vp, vld, vlay = self._dev(V, (self.m, self.n))
         if weights is not None:
             wp, wld, wlay = self._dev(weights, (self.m, self.n))
@@ -347,6 +378,25 @@ class Engine:
                         "upload_dense_weighted_device")
             return
         self._upload(lambda: self._lib.nmfamd_engine_upload_dense_device(self._h, C.c_void_p(vp), C.c_long(vld), vlay), "upload_dense_device")
+
+    def upload_device_stored(self, V):
+        """upload() of a dense V that lies in the memory of the engine's GPU, for the engines upload_device refuses: sparse_compute (the entries != 0 are stored) and
+        missing_values (every entry that is not NaN is observed, zeros included).  V as for upload_device.  The CSR and CSC images are compacted on the device
+        (docs/DEVICE_IO.md, "Dense input on the sparse engines") and equal those of upload() of the same values bit for bit; any other engine refuses the call."""
+        vp, vld, vlay = self._dev(V, (self.m, self.n))
+        self._upload(lambda: self._lib.nmfamd_engine_upload_dense_device_stored(self._h, C.c_void_p(vp), C.c_long(vld), vlay), "upload_dense_device_stored")
+
+    def upload_sparse_device(self, fmt: int, values, a, b, base: int = 0):
+        """upload_sparse() for arrays that lie in the memory of the engine's GPU (docs/DEVICE_IO.md, "Sparse input"): values of the engine's dtype, a and b int32
+        (torch's CSR tensors hold int64 indices: convert them), each a contiguous 1-D device array with __cuda_array_interface__ (device_vector) or a raw
+        (ptr, count) pair.  fmt 1 CSR (a: m + 1 row pointers, b: column indices), 2 CSC (a: n + 1 column pointers, b: row indices), 3 COO (a: rows, b: columns).
+        The arrays are read where they lie, never written and not kept; everything that follows equals upload_sparse() of the same values."""
+        vp, nnz = device_vector(values, self.dtype)
+        na = {1: self.m + 1, 2: self.n + 1, 3: nnz}.get(fmt)      # (another format: the library refuses it, as it refuses upload_sparse's)
+        ap, _ = device_vector(a, np.int32, na)
+        bp, _ = device_vector(b, np.int32, nnz)
+        self._upload(lambda: self._lib.nmfamd_engine_upload_sparse_device(self._h, int(fmt), C.c_void_p(vp), C.c_void_p(ap), C.c_void_p(bp), C.c_long(nnz), int(base)),
+                     "upload_sparse_device")
 
     def set_factors_device(self, W, H):
         """set_factors() from device arrays (W: (m, r), H: (r, n), either layout, see upload_device); None leaves that factor."""
