@@ -140,6 +140,25 @@ typedef struct nmfamd_params_v6 {
 	                           refused at creation */
 } nmfamd_params_v6;
 
+/* nmfamd_params_v6 followed by what has been added since (v2 to v6 keep their sizes).  nmfamd_engine_create_v2 and nmfamd_plan_geometry read
+ * min(params_size, sizeof(nmfamd_params_v7)) bytes and take the rest as 0: a v6-sized struct gives the engine it always gave. */
+typedef struct nmfamd_params_v7 {
+	nmfamd_params_v6 v6;
+	double missing_divergence; /* with base.missing_values = 1: the divergence of the masked update (docs/MISSING.md, "Beta-divergence").  0 = the Frobenius objective
+	                              (kernels_masked.hip, as ever); 1 = generalised KL; 2 = Itakura-Saito; 3 = the beta-divergence at missing_beta.  The iteration is the
+	                              weighted update of docs/DIVERGENCE.md at 0 / 1 weights with both sums over the stored entries only -- O(nnz r) at every beta
+	                              (kernels_masked_beta.hip).  beta <= 0: every stored value finite and > 0 (a stored zero is refused); beta > 0: finite and >= 0 (a stored
+	                              zero is an observation); an upload that breaks the rule returns NMFAMD_INVALID_ARGUMENT with nmfamd_engine_last_error set.
+	                              nmfamd_engine_set_hals_penalties is accepted (none: normalisation as the weighted update; any: none); constant_w is available;
+	                              nmfamd_engine_divergence reports sum_p d_beta(v_p | (W H)_p + eps) over the stored entries, frobenius / rmsd the residual over them.
+	                              base.divergence stays refused beside missing_values.  Refused at creation with nmfamd_engine_last_error: a value outside
+	                              {0, 1, 2, 3}; != 0 without missing_values = 1, with base.divergence != 0, with another algorithm than Multiplicative, r > 256,
+	                              weighted, mixed_precision, batch_size or row blocks.  The three-phase and sharded calls are refused as on every masked engine */
+	double missing_beta;       /* with missing_divergence = 3: the beta, any finite value, taken in the engine's precision; 0 and 1 run the kernels of
+	                              missing_divergence = 2 and 1, bit for bit.  A non-zero value with another missing_divergence, and a value that is not finite or
+	                              lies outside the range of the engine's precision, are refused at creation */
+} nmfamd_params_v7;
+
 typedef struct nmfamd_engine nmfamd_engine;  /* opaque; owns every device buffer of one factorisation */
 
 /* Number of visible HIP devices (0 when there is none), and the library's build description. */
@@ -154,7 +173,7 @@ NMFAMD_API const char* nmfamd_engine_last_error(const nmfamd_engine* e);
  * every kernel and copy of this engine is issued on it. */
 NMFAMD_API int nmfamd_engine_create(int m, int n, int r, int algorithm, const nmfamd_params* params,
                                     int elem_bytes, void* stream, nmfamd_engine** out);
-/* The same with the sized, extended parameter struct (nmfamd_params_v2 ... _v6; params_size = sizeof of the caller's struct, at least
+/* The same with the sized, extended parameter struct (nmfamd_params_v2 ... _v7; params_size = sizeof of the caller's struct, at least
  * sizeof(nmfamd_params) unless params is NULL) and the row blocks of nmfamd_engine_create_blocks (1: none). */
 NMFAMD_API int nmfamd_engine_create_v2(int m, int n, int r, int algorithm, const void* params, unsigned long params_size,
                                        int elem_bytes, void* stream, int row_blocks, nmfamd_engine** out);
@@ -240,6 +259,7 @@ NMFAMD_API int nmfamd_engine_synchronize(nmfamd_engine* e);
  *   1/2 ||V - W H||^2 + l1W ||W||_1 + l1H ||H||_1 + 1/2 l2W ||W||^2 + 1/2 l2H ||H||^2     (docs/HALS.md has the mapping from alpha_W, alpha_H, l1_ratio).
  * Dense divergence engines (divergence 2, 3, or 1 with dense_compute): the same four terms added to the divergence, by scikit-learn's solver="mu" -- each
  * half-step's denominator carries + l1 + l2 A before the power (docs/DIVERGENCE.md); nmfamd_engine_divergence keeps reporting the divergence alone.
+ * Masked divergence engines (missing_values = 1 with nmfamd_params_v7.missing_divergence != 0; docs/MISSING.md): likewise, over the stored entries.
  * Valid any time between iterations (a regularisation path on one resident V); takes effect at the next nmfamd_engine_iterate.  While any of the four is
  * non-zero the column normalisation of W is skipped; all zeros restores the unpenalised iteration.  nmfamd_engine_frobenius / _rmsd keep reporting
  * ||V - W H||, not the penalised objective.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error) for a negative or non-finite value, and for a
@@ -656,6 +676,18 @@ NMFAMD_API int nmfamd_op_kl_fused_f32(const int* ptr, const int* idx, const floa
                                       int rows_pad, int blocks, const float* a_scale, float* out, float* t_vwh, float* t_kl);
 NMFAMD_API int nmfamd_op_kl_fused_f64(const int* ptr, const int* idx, const double* val, long nnz, const double* A, const double* B, long b_rows, int RP, int rows,
                                       int rows_pad, int blocks, const double* a_scale, double* out, double* t_vwh, double* t_kl);
+/* masked_beta_half_step: one launch of the masked beta-divergence half-step (kernels_masked_beta.hip, docs/MISSING.md "Beta-divergence") of any instantiation.
+ * A [a_rows][RP] (a_rows >= rows; in place: rows < `rows` are updated unless update = 0, the others come back as they were), B [b_rows][RP], RP 64, 128 or 256;
+ * ptr / idx / val as above with rows + 1 offsets.  divergence / beta as nmfamd_params_v7.missing_divergence / missing_beta (1, 2, or 3 with beta); l1, l2 the
+ * penalties of the half-step.  t_frob / t_div (both or neither, `rows` values) and sumsq_part (optional, update only; sumsq_parts = nmfamd_masked_norm_parts(rows)
+ * vectors of RP values) are uploaded as the caller filled them, so what the launch does not write comes back unchanged. */
+NMFAMD_API int nmfamd_masked_norm_parts(int rows);
+NMFAMD_API int nmfamd_op_masked_beta_half_step_f32(const int* ptr, const int* idx, const float* val, long nnz, float* A, long a_rows, const float* B, long b_rows, int RP,
+                                                   int rows, int divergence, double beta, double l1, double l2, int update, float* t_frob, float* t_div,
+                                                   float* sumsq_part, int sumsq_parts);
+NMFAMD_API int nmfamd_op_masked_beta_half_step_f64(const int* ptr, const int* idx, const double* val, long nnz, double* A, long a_rows, const double* B, long b_rows, int RP,
+                                                   int rows, int divergence, double beta, double l1, double l2, int update, double* t_frob, double* t_div,
+                                                   double* sumsq_part, int sumsq_parts);
 /* kl_update: P(y, c) <- (P(y, c) * scale(c)) * (sum over the parts of num) / (den(c) + eps) on P [len_pad][RP] (scale NULL: ones); num holds `parts` panels
  * part_stride values apart (a multiple of 4, >= len_pad * RP when parts > 1; what lies between two panels is not read).  sumsq_part / sum_part (each optional,
  * [len_pad / 128][RP]): per 128 rows the sums of squares / the sums of the new values.  len_pad a multiple of 128. */

@@ -275,8 +275,27 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 		}
 	}
 	{
+		// "missingDivergence" = 1 / 2 / 3 beside "missingValues" = 1 (docs/MISSING.md, "Beta-divergence"): the masked update under generalised KL, Itakura-Saito or the
+		// beta-divergence at "missingBeta".  Read here, ahead of the penalties it allows; "missingValues" itself keeps its block further down (its value is only
+		// looked at here: anything but exactly 1 leaves a "missingDivergence" without its switch, which the engine's own rule refuses)
+		int idx = parameter_index(d.parameters, d.numParameters, "missingDivergence");
+		if (idx >= 0) prm.missing_divergence = d.parameters[idx].value;
+		idx = parameter_index(d.parameters, d.numParameters, "missingBeta");
+		if (idx >= 0) prm.missing_beta = d.parameters[idx].value;
+		idx = parameter_index(d.parameters, d.numParameters, "missingValues");
+		if (idx >= 0 && d.parameters[idx].value == 1.0) prm.missing_values = 1;
+		if (const char* why = nmfamd::masked_beta_fault(prm, d.algorithm == NmfAlgorithm::Multiplicative, (int)d.features)) {
+			log_error((std::string("[ERROR] ") + why).c_str());
+			return ResultType::ErrorInvalidArgument;
+		}
+		if (prm.is_masked_beta() && !std::isfinite((double)(T)prm.masked_beta())) {
+			log_error("[ERROR] missing-value divergence: 'missingBeta' out of the range of the engine's precision");
+			return ResultType::ErrorInvalidArgument;
+		}
+	}
+	{
 		// "l1W", "l1H", "l2W", "l2H": the penalties of scikit-learn's coordinate descent on the HALS sweeps (docs/HALS.md) and of its multiplicative update on the
-		// dense divergence updates (docs/DIVERGENCE.md: "divergence" 2, 3, and 1 with "denseCompute"); absent = 0
+		// dense divergence updates (docs/DIVERGENCE.md: "divergence" 2, 3, and 1 with "denseCompute") and on the masked divergence update ("missingDivergence"); absent = 0
 		struct { const char* name; double* slot; } pen[] = {{"l1W", &prm.l1W}, {"l1H", &prm.l1H}, {"l2W", &prm.l2W}, {"l2H", &prm.l2H}};
 		for (auto& p : pen) {
 			const int idx = parameter_index(d.parameters, d.numParameters, p.name);

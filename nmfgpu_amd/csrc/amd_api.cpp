@@ -48,9 +48,10 @@ thread_local std::string g_create_error;
 bool sized_params(const void* params_sized, unsigned long params_size, AlgorithmParams* out) {
 	if (params_sized == nullptr) return true;
 	if (params_size < sizeof(nmfamd_params)) return false;
-	nmfamd_params_v6 v6;
-	std::memset(&v6, 0, sizeof(v6));
-	std::memcpy(&v6, params_sized, params_size < sizeof(v6) ? (size_t)params_size : sizeof(v6));
+	nmfamd_params_v7 v7;
+	std::memset(&v7, 0, sizeof(v7));
+	std::memcpy(&v7, params_sized, params_size < sizeof(v7) ? (size_t)params_size : sizeof(v7));
+	const nmfamd_params_v6& v6 = v7.v6;
 	const nmfamd_params_v5& v5 = v6.v5;
 	const nmfamd_params_v4& v4 = v5.v4;
 	const nmfamd_params_v3& v3 = v4.v3;
@@ -58,6 +59,7 @@ bool sized_params(const void* params_sized, unsigned long params_size, Algorithm
 	const nmfamd_params& b = v2.base;
 	AlgorithmParams& p = *out;
 	p.lambda = b.lambda; p.lambdaW = b.lambdaW; p.lambdaH = b.lambdaH; p.alphaW = b.alphaW; p.alphaH = b.alphaH; p.theta = b.theta; p.divergence = b.divergence; p.sparse_compute = b.sparse_compute; p.precision = b.precision; p.missing_values = b.missing_values; p.dense_compute = v2.dense_compute; p.beta_value = v3.beta; p.weighted = v4.weighted; p.mixed_precision = v5.mixed_precision; p.batch_size = v6.batch_size; p.forget_factor = v6.forget_factor;
+	p.missing_divergence = v7.missing_divergence; p.missing_beta = v7.missing_beta;
 	return true;
 }
 
@@ -1315,6 +1317,34 @@ int op_kl_fused(const int* ptr, const int* idx, const T* val, long nnz, const T*
 	return NMFAMD_OK;
 }
 
+// One launch of the masked beta-divergence half-step (kernels_masked_beta.hip) on a caller-built image and caller-built padded panels.  divergence / beta select the
+// map as nmfamd_params_v7 does (1 KL, 2 Itakura-Saito, 3 beta -- where 0 and 1 run the maps of 2 and 1).  A [a_rows][RP] comes back as the launch left it; t_frob /
+// t_div [rows] and sumsq_part [masked_norm_parts(rows)][RP] are uploaded as the caller filled them.
+template <typename T>
+int op_masked_beta_half_step(const int* ptr, const int* idx, const T* val, long nnz, T* A, long a_rows, const T* B, long b_rows, int RP, int rows, int divergence, double beta,
+                             double l1, double l2, int update, T* t_frob, T* t_div, T* sumsq_part, int sumsq_parts) {
+	if (!ptr || !idx || !val || !A || !B || nnz < 0 || nnz > 0x7fffffffl || b_rows < 1 || rows < 1 || a_rows < rows || (RP != 64 && RP != 128 && RP != 256) ||
+	    divergence < 1 || divergence > 3 || (divergence != 3 && beta != 0) || (t_frob == nullptr) != (t_div == nullptr) ||
+	    (sumsq_part != nullptr && sumsq_parts != masked_norm_parts(rows)) || !sparse_image_ok(ptr, idx, nnz, rows, 1, b_rows))
+		return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const double b = divergence == 2 ? 0.0 : divergence == 3 ? beta : 1.0;
+	const size_t panel = (size_t)a_rows * RP, ns = (size_t)(sumsq_part ? sumsq_parts : 0) * RP;
+	DevBuf dPtr, dIdx, dVal, dA, dB, dTf, dTd, dSq;
+	if (upload(dPtr, ptr, (size_t)rows + 1) != hipSuccess || upload(dIdx, idx, (size_t)nnz) != hipSuccess || upload(dVal, val, (size_t)nnz) != hipSuccess ||
+	    upload(dA, A, panel) != hipSuccess || upload(dB, B, (size_t)b_rows * RP) != hipSuccess ||
+	    (t_frob && (upload(dTf, t_frob, (size_t)rows) != hipSuccess || upload(dTd, t_div, (size_t)rows) != hipSuccess)) || (sumsq_part && upload(dSq, sumsq_part, ns) != hipSuccess))
+		return NMFAMD_NO_DEVICE_MEMORY;
+	const int st = op_status(launch_masked_beta_half_step<T>((const int*)dPtr.p, (const int*)dIdx.p, (const T*)dVal.p, (T*)dA.p, (const T*)dB.p, RP, std::numeric_limits<T>::epsilon(),
+	                                                         b, (T)l1, (T)l2, update != 0, (T*)dTf.p, (T*)dTd.p, (T*)dSq.p, rows, nullptr));
+	if (st != NMFAMD_OK) return st;
+	if (hipMemcpy(A, dA.p, sizeof(T) * panel, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (t_frob && (hipMemcpy(t_frob, dTf.p, sizeof(T) * rows, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(t_div, dTd.p, sizeof(T) * rows, hipMemcpyDeviceToHost) != hipSuccess))
+		return NMFAMD_HIP_ERROR;
+	if (sumsq_part && hipMemcpy(sumsq_part, dSq.p, sizeof(T) * ns, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
+
 template <typename T>
 int op_kl_update(T* P, const T* num, int parts, long part_stride, const T* den, const T* scale, int RP, int len_pad, T* sumsq_part, T* sum_part) {
 	// num: `parts` panels of len_pad * RP values, part_stride values apart (what lies between them is uploaded too, and must not be read)
@@ -1548,6 +1578,18 @@ int nmfamd_op_hals_normalize_f32(float* Wt, int RP, int mpad, float* H, int npad
 
 int nmfamd_op_hals_normalize_f64(double* Wt, int RP, int mpad, double* H, int npad, const double* sumsq_part, int parts) {
 	return op_hals_normalize<double>(Wt, RP, mpad, H, npad, sumsq_part, parts);
+}
+
+int nmfamd_masked_norm_parts(int rows) { return rows > 0 ? masked_norm_parts(rows) : 0; }
+
+int nmfamd_op_masked_beta_half_step_f32(const int* ptr, const int* idx, const float* val, long nnz, float* A, long a_rows, const float* B, long b_rows, int RP, int rows,
+                                        int divergence, double beta, double l1, double l2, int update, float* t_frob, float* t_div, float* sumsq_part, int sumsq_parts) {
+	return op_masked_beta_half_step<float>(ptr, idx, val, nnz, A, a_rows, B, b_rows, RP, rows, divergence, beta, l1, l2, update, t_frob, t_div, sumsq_part, sumsq_parts);
+}
+
+int nmfamd_op_masked_beta_half_step_f64(const int* ptr, const int* idx, const double* val, long nnz, double* A, long a_rows, const double* B, long b_rows, int RP, int rows,
+                                        int divergence, double beta, double l1, double l2, int update, double* t_frob, double* t_div, double* sumsq_part, int sumsq_parts) {
+	return op_masked_beta_half_step<double>(ptr, idx, val, nnz, A, a_rows, B, b_rows, RP, rows, divergence, beta, l1, l2, update, t_frob, t_div, sumsq_part, sumsq_parts);
 }
 
 int nmfamd_op_kl_fused_f32(const int* ptr, const int* idx, const float* val, long nnz, const float* A, const float* B, long b_rows, int RP, int rows, int rows_pad, int blocks,

@@ -178,8 +178,15 @@ Status Engine<T>::check_parameters() {
 	if (const char* why = hals_sweep_tolerance_fault(prm_.sweep_tolerance, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = nenmf_step_tolerance_fault(prm_.steps_tolerance, prm_.steps_tolerance != 0, alg_ == ALG_NENMF)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = beta_dense_fault(prm_, alg_ == ALG_MU, r_, row_blocks_)) { last_error_ = why; return ST_INVALID; }
+	if (const char* why = masked_beta_fault(prm_, alg_ == ALG_MU, r_, row_blocks_)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = weighted_fault(prm_)) { last_error_ = why; return ST_INVALID; }
 	beta_dense_ = prm_.is_beta_dense();
+	masked_beta_ = prm_.is_masked_beta();
+	if (masked_beta_) {
+		// beta in the engine's precision, as the dense engines take theirs: a value that rounds to 0 or 1 there IS the Itakura-Saito or the KL map
+		mbeta_ = (double)(T)prm_.masked_beta();
+		if (!std::isfinite(mbeta_)) { last_error_ = "missing-value divergence: 'missingBeta' out of the range of the engine's precision"; return ST_INVALID; }
+	}
 	if (const char* why = mixed_precision_fault(prm_, sizeof(T) == 4)) { last_error_ = why; return ST_INVALID; }
 	if (const char* why = minibatch_fault(prm_)) { last_error_ = why; return ST_INVALID; }
 	weighted_ = prm_.weighted != 0;
@@ -614,6 +621,7 @@ Status Engine<T>::upload_dense(const T* V, long ld) {
 				const T v = V[(size_t)j * ld + i];
 				if (std::isnan(v)) continue;
 				if (!std::isfinite(v)) { last_error_ = "missing values: V holds an infinite value (NaN marks a missing entry)"; return ST_INVALID; }
+				if (masked_beta_ && (v < T(0) || (mbeta_ <= 0 && v == T(0)))) { last_error_ = masked_value_fault(); return ST_INVALID; }
 				rows.push_back(i); cols.push_back(j); vals.push_back(v);
 			}
 		if (vals.empty()) { last_error_ = "missing values: V has no observed entry"; return ST_INVALID; }
@@ -851,7 +859,7 @@ Status Engine<T>::upload_sparse(int format, const T* values, const int* a, const
 		// missing values: every stored entry is observed (stored zeros too, which both image builders keep); its value must be finite, and there must be one
 		if (nnz == 0) return refuse_sparse_values(SPARSE_NO_ENTRY);
 		for (long p = 0; p < nnz; ++p)
-			if (!std::isfinite(values[p])) return refuse_sparse_values(IMPORT_BAD_VALUE);
+			if (!std::isfinite(values[p]) || (masked_beta_ && (values[p] < T(0) || (mbeta_ <= 0 && values[p] == T(0))))) return refuse_sparse_values(IMPORT_BAD_VALUE);
 	}
 	if (sparse_) {
 		// the images are built on the device (kernels_sparse_setup.hip); what that path does not cover -- entries outside the matrix (dropped by the host path), pointer
@@ -1004,8 +1012,16 @@ Status Engine<T>::refuse_sparse_input(int format, long nnz) {
 // ... and the value rules of a missing-values engine, by what was found (the host loop, or the flags of kernels_compact.hip)
 template <typename T>
 Status Engine<T>::refuse_sparse_values(int found) {
-	last_error_ = (found & SPARSE_NO_ENTRY) ? "missing values: no stored entry" : "missing values: a stored value is not finite";
+	last_error_ = (found & SPARSE_NO_ENTRY) ? "missing values: no stored entry" : masked_beta_ ? masked_value_fault() : "missing values: a stored value is not finite";
 	return ST_INVALID;
+}
+
+// The demand of a masked divergence engine on the stored values: finite, and > 0 at beta <= 0 (such a divergence is undefined at 0: a stored zero is refused) or >= 0
+// at beta > 0 (a stored zero is an observation)
+template <typename T>
+const char* Engine<T>::masked_value_fault() const {
+	return mbeta_ <= 0 ? "missing values with beta <= 0: every stored value has to be finite and > 0"
+	                   : "missing values with beta > 0: every stored value has to be finite and >= 0";
 }
 
 template <typename T>
@@ -1046,7 +1062,7 @@ Status Engine<T>::upload_sparse_from_device(int format, const T* values, const i
 	if ((beta_dense_ || masked) && nnz > 0) {
 		int flags = 0;
 		HIPX(hipMemsetAsync(range_flag_, 0, sizeof(int), stream_));
-		HIPX(launch_sparse_value_rule<T>(values, nnz, beta_dense_ ? 1 : 2, range_flag_, stream_));
+		HIPX(launch_sparse_value_rule<T>(values, nnz, beta_dense_ ? 1 : !masked_beta_ ? 2 : mbeta_ <= 0 ? 3 : 1, range_flag_, stream_));
 		HIPX(hipMemcpyAsync(&flags, range_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_));
 		HIPX(hipStreamSynchronize(stream_));
 		if (flags & IMPORT_BAD_VALUE) {
@@ -1132,6 +1148,15 @@ Status Engine<T>::upload_dense_device_stored(const T* V, long ld, int layout) {
 	if (two_pass) { HIPX(image(&csc_from_csr_, ni)); HIPX(image(&q_, nv)); HIPX(image(&q2_, nv)); }
 	HIPX(launch_compact_pointers(off_r, off_c, m_, n_, csr_ptr_, csc_ptr_, stream_));
 	HIPX(launch_compact_scatter<T>(V, ld, layout, m_, n_, masked, off_r, off_c, nnz, csr_idx_, csr_val_, csc_idx_, csc_val_, csc_from_csr_, stream_));
+	if (masked_beta_) {
+		// the value rule of the engine's beta over the compacted values (the count pass knows finite from not finite only); a violation leaves the engine without
+		// an image (nnz_ = 0: iterate refuses)
+		HIPX(hipMemsetAsync(range_flag_, 0, sizeof(int), stream_));
+		HIPX(launch_sparse_value_rule<T>(csr_val_, nnz, mbeta_ <= 0 ? 3 : 1, range_flag_, stream_));
+		HIPX(hipMemcpyAsync(&flags, range_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_));
+		HIPX(hipStreamSynchronize(stream_));
+		if (flags & IMPORT_BAD_VALUE) return refuse_sparse_values(IMPORT_BAD_VALUE);
+	}
 	return finish_sparse_images(nnz);
 }
 
@@ -1526,7 +1551,8 @@ void Engine<T>::finalize_error(bool resolve) {
 		for (int i = 0; i < m_; ++i) { s += (double)h_psN_[i]; d += (double)h_klrow_[i]; }
 		frob2_ = s;
 		frob_ = std::sqrt(s);
-		rmsd_ = frob_ / std::sqrt(weighted_ ? sum_w_ : (double)m_ * (double)n_);      // (weighted: sum of the weights -- the observed count at 0 / 1 weights)
+		// (weighted: sum of the weights -- the observed count at 0 / 1 weights; a masked divergence engine: the stored entries)
+		rmsd_ = frob_ / std::sqrt(weighted_ ? sum_w_ : masked_beta_ ? (double)nnz_ : (double)m_ * (double)n_);
 		kl_ = d;
 		beta_unresolved_ = false;
 	}
@@ -2484,7 +2510,7 @@ template <typename T>
 Status Engine<T>::iterate(bool compute_error, bool constant_w) {
 	const T eps = std::numeric_limits<T>::epsilon();
 	timing_now_ = timing_ && (timing_iter_++ % timing_stride_ == 0);
-	if (prm_.is_masked()) return iterate_masked(compute_error, constant_w);      // (before the KL test: a masked engine never has divergence != 0, allocate())
+	if (prm_.is_masked()) return masked_beta_ ? iterate_masked_beta(compute_error, constant_w) : iterate_masked(compute_error, constant_w);      // (before the KL test: a masked engine never has divergence != 0, allocate())
 	if (beta_dense_ && minibatch_) {
 		if (constant_w) { last_error_ = "minibatch update: no constant-W form (with W fixed a batch step is the full H step: use the engine without 'batchSize')"; return ST_INVALID; }
 		return iterate_beta_minibatch(compute_error);
@@ -2866,6 +2892,45 @@ Status Engine<T>::iterate_masked(bool compute_error, bool constant_w) {
 		masked_pending_ = true;
 	}
 	if (!constant_w) HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, msq_part_, masked_norm_parts(m_), stream_));
+	return ST_OK;
+}
+
+// Missing-value NMF under the beta-divergence (docs/MISSING.md, "Beta-divergence"): the weighted update of docs/DIVERGENCE.md at 0 / 1 weights with both sums over the
+// stored entries, in iterate_masked's skeleton -- one fused launch per half-step (kernels_masked_beta.hip) that maps every stored entry's p = wh_p + eps, accumulates
+// numerator and denominator and applies the quotient, the penalties and gamma to its own row in place:
+//   H step over the CSC image (l1H, l2H), W step with the new H over the CSR image (l1W, l2W), + the two per-row error terms of (W_{k-1}, H_k) on error iterations
+//   normalisation as the weighted update: none with a penalty; beta = 1 the columns of W only (launch_normalize_panel); any other beta the compensated form
+//   (launch_hals_normalize: W D^-1, D H), both from the W launch's per-workgroup sums of squares
+// Under constant W the H step runs alone and an error iteration takes its terms from the terms-only form of the W-side launch.  The terms travel to pinned memory
+// like the dense divergence engines' and are summed in double by finalize_error().  Nothing derived from a factor outlives a launch, so PanelState has no flag of
+// this iteration: an upload or a factor from outside goes through its transitions as on every engine and finds nothing of ours to clear.
+template <typename T>
+Status Engine<T>::iterate_masked_beta(bool compute_error, bool constant_w) {
+	if (!sparse_ || nnz_ <= 0) { last_error_ = "missing values: no stored entry has been uploaded"; return ST_INVALID; }
+	const T eps = std::numeric_limits<T>::epsilon();
+	const bool penalised = prm_.hals_penalised();
+	const T l1W = (T)prm_.l1W, l1H = (T)prm_.l1H, l2W = (T)prm_.l2W, l2H = (T)prm_.l2H;
+	record_begin();
+	HIPX(launch_masked_beta_half_step<T>(csc_ptr_, csc_idx_, csc_val_, H_, Wt_, RP_, eps, mbeta_, l1H, l2H, true, (T*)nullptr, (T*)nullptr, (T*)nullptr, n_, stream_));
+	record_end();
+	if (!constant_w || compute_error) {
+		T* tf = compute_error ? t_vwh_ : (T*)nullptr;
+		T* td = compute_error ? t_kl_ : (T*)nullptr;
+		record_begin(1);
+		HIPX(launch_masked_beta_half_step<T>(csr_ptr_, csr_idx_, csr_val_, Wt_, H_, RP_, eps, mbeta_, l1W, l2W, !constant_w, tf, td,
+		                                     constant_w || penalised ? (T*)nullptr : msq_part_, m_, stream_));
+		record_end();
+	}
+	if (compute_error) {
+		finalize_error(false);      // (the pinned buffer is about to be reused; an older copy is long complete)
+		HIPX(hipMemcpyAsync(pin_kl_, t_vwh_, sizeof(T) * m_, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipMemcpyAsync(pin_kl_ + m_, t_kl_, sizeof(T) * m_, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipEventRecord(err_event_, stream_));
+		beta_pending_ = true;
+	}
+	if (constant_w || penalised) return ST_OK;
+	if (mbeta_ == 1) HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, msq_part_, masked_norm_parts(m_), stream_));
+	else HIPX(launch_hals_normalize<T>(Wt_, RP_, (int)mpad_, H_, (int)npad_, msq_part_, masked_norm_parts(m_), stream_));
 	return ST_OK;
 }
 

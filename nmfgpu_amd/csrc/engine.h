@@ -66,12 +66,17 @@ struct AlgorithmParams {
 	double mixed_precision = 0; // 1 on a dense divergence fp32 engine: the operands of the fused half-step's products rounded to bf16 (kernels_beta_bf16.hip, docs/DIVERGENCE.md)
 	double batch_size = 0;      // > 0 on a dense divergence engine: the minibatch (online) update over blocks of batch_size columns of V (kernels_beta_online.hip, docs/DIVERGENCE.md)
 	double forget_factor = 0;   // ... its forgetting factor in [0, 1]: rho = forget_factor^(min(batch_size, n) / n) scales the accumulated numerator and denominator of W
+	// missing_values = 1: the divergence of the masked update -- 0 Frobenius (kernels_masked.hip), 1 generalised KL, 2 Itakura-Saito, 3 the beta-divergence at
+	// missing_beta (kernels_masked_beta.hip, docs/MISSING.md "Beta-divergence"); fields of their own, as 'weighted' has: 'divergence' stays refused beside missing_values
+	double missing_divergence = 0, missing_beta = 0;
 	bool is_masked() const { return missing_values != 0; }
+	bool is_masked_beta() const { return missing_values != 0 && missing_divergence != 0; }
+	double masked_beta() const { return missing_divergence == 2 ? 0.0 : missing_divergence == 3 ? missing_beta : 1.0; }
 	bool is_minibatch() const { return batch_size != 0; }
 	// the dense beta-divergence update: Itakura-Saito (beta = 0) and the general form always, generalised KL (beta = 1) with dense_compute
 	bool is_beta_dense() const { return divergence == 2 || divergence == 3 || (divergence == 1 && dense_compute != 0); }
 	double beta() const { return divergence == 2 ? 0.0 : divergence == 3 ? beta_value : 1.0; }
-	bool takes_penalties(bool is_hals) const { return is_hals || is_beta_dense(); }
+	bool takes_penalties(bool is_hals) const { return is_hals || is_beta_dense() || is_masked_beta(); }
 	bool hals_penalised() const { return l1W != 0 || l1H != 0 || l2W != 0 || l2H != 0; }
 };
 
@@ -137,6 +142,23 @@ inline const char* beta_dense_fault(const AlgorithmParams& p, bool is_mu, int r,
 	if (p.precision > 0) return "dense divergence update: no bf16 operands";
 	if (r > 256) return "dense divergence update: rank <= 256";
 	if (row_blocks > 1) return "dense divergence update: single GPU only (no row blocks)";
+	return nullptr;
+}
+
+// What 'missing_divergence' and 'missing_beta' (nmfamd_params_v7) must satisfy, after beta_dense_fault: nullptr, or why not.  (A 'missing_beta' outside the range of
+// the engine's precision is Engine::check_parameters' to refuse.)
+inline const char* masked_beta_fault(const AlgorithmParams& p, bool is_mu, int r, int row_blocks = 1) {
+	const double d = p.missing_divergence;
+	if (!(d == 0 || d == 1 || d == 2 || d == 3)) return "missing-value divergence: 'missingDivergence' has to be 0 (Frobenius), 1 (KL), 2 (Itakura-Saito) or 3 (beta)";
+	if (!(p.missing_beta - p.missing_beta == 0)) return "missing-value divergence: 'missingBeta' has to be finite";
+	if (p.missing_beta != 0 && d != 3) return "missing-value divergence: 'missingBeta' needs 'missingDivergence' = 3 (the general beta-divergence)";
+	if (d == 0) return nullptr;
+	if (p.missing_values != 1) return "missing-value divergence: 'missingDivergence' needs 'missingValues' = 1";
+	if (p.divergence != 0) return "missing-value divergence: does not combine with 'divergence' (that one selects the unmasked updates)";
+	if (!is_mu) return "missing-value divergence: the Multiplicative algorithm only";
+	if (r > 256) return "missing-value divergence: rank <= 256";
+	if (p.weighted != 0 || p.mixed_precision != 0 || p.batch_size != 0) return "missing-value divergence: does not combine with 'weighted', 'mixedPrecision' or 'batchSize' (those are the dense engines')";
+	if (row_blocks > 1) return "missing-value divergence: single GPU only (no row blocks)";
 	return nullptr;
 }
 
@@ -294,6 +316,8 @@ public:
 	long exchange_count() const { return prm_.is_masked() || beta_dense_ ? 0 : (long)RP_ * mpad_ + (long)RP_ * RP_ + (prm_.divergence != 0 ? (long)RP_ + 2 * mpad_ : 0); }
 	bool is_kl() const { return prm_.divergence != 0; }
 	bool is_masked() const { return prm_.is_masked(); }
+	bool is_masked_beta() const { return masked_beta_; }
+	double masked_beta() const { return mbeta_; }      // the beta of a masked divergence engine, in the precision of T
 	bool is_beta_dense() const { return beta_dense_; }
 	// sharded runs: the error terms refer to the whole matrix (sorted tr(V^T V) terms of ALL columns, sum of ALL entries, total column count)
 	void set_error_globals(const std::vector<T>& vtv_sorted_all, double sum_v_all, long total_columns) { h_vtv_ = vtv_sorted_all; sum_v_ = sum_v_all; err_total_columns_ = total_columns; }
@@ -425,7 +449,9 @@ private:
 	bool sparse_setup_on_device_ = false;
 	Status iterate_kl(bool compute_error);            // KL-divergence multiplicative update (sparse mode)
 	Status iterate_masked(bool compute_error, bool constant_w);   // multiplicative update over the stored entries only (kernels_masked.hip)
+	Status iterate_masked_beta(bool compute_error, bool constant_w);   // ... under the beta-divergence (kernels_masked_beta.hip)
 	Status masked_refuses(const char* what);          // ST_INVALID with last_error_ set: no three-phase / sharded form of the masked update
+	const char* masked_value_fault() const;           // the text of a stored value that breaks the rule of a masked divergence engine's beta
 	Status iterate_beta_minibatch(bool compute_error);            // ... its minibatch (online) form: one pass over the batches (kernels_beta_online.hip)
 	Status iterate_beta(bool compute_error, bool constant_w);     // dense beta-divergence multiplicative update (kernels_beta.hip, docs/DIVERGENCE.md)
 	Status beta_refuses(const char* what);            // ... nor of the dense beta-divergence update
@@ -521,6 +547,10 @@ private:
 	// masked update: per-workgroup sums of squares of the new W rows ([MASKED_NORM_PARTS + 16][RP]); the per-row residual terms travel through pin_kl_ (first m)
 	T* msq_part_ = nullptr;
 	bool masked_pending_ = false, masked_unresolved_ = false;
+	// ... under the beta-divergence (prm_.is_masked_beta()): mbeta_ = prm_.masked_beta() rounded to T, what the launches take; the two per-row terms travel like the
+	// dense divergence engines' (t_vwh_ / t_kl_ -> pin_kl_, beta_pending_), rmsd over the stored entries
+	bool masked_beta_ = false;
+	double mbeta_ = 1;
 	// dense beta-divergence update: V_ is the column-major image (the H step's), Vt_ its transpose (the W step's); slabs_ holds the slabs' partial numerators,
 	// beta_den_ their partial denominators (beta = 0), beta_tpart_ the slabs' parts of the two per-row error terms ([2][BETA_MAX_SLABS][mpad])
 	bool beta_dense_ = false, beta_uploaded_ = false;

@@ -387,7 +387,7 @@ hipError_t launch_compact_pointers(const int* off_r, const int* off_c, int rows,
 template <typename T>
 hipError_t launch_compact_scatter(const T* src, long ld, int layout, int rows, int cols, int masked, const int* off_r, const int* off_c, long nnz, int* csr_idx, T* csr_val,
                                   int* csc_idx, T* csc_val, int* from_csr, hipStream_t stream);
-// The value rules of a sparse upload over values[0 .. nnz) in DEVICE memory: rule 1 every value finite and >= 0, rule 2 finite; a violation sets IMPORT_BAD_VALUE.
+// The value rules of a sparse upload over values[0 .. nnz) in DEVICE memory: rule 1 every value finite and >= 0, rule 2 finite, rule 3 finite and > 0; a violation sets IMPORT_BAD_VALUE.
 template <typename T>
 hipError_t launch_sparse_value_rule(const T* values, long nnz, int rule, int* flags, hipStream_t stream);
 
@@ -596,6 +596,15 @@ int masked_norm_parts(int rows);
 template <typename T>
 hipError_t launch_masked_half_step(const int* ptr, const int* idx, const T* val, T* A, const T* B, int RP, T eps, bool update,
                                    T* t_res, T* sumsq_part, int rows, hipStream_t stream);
+// ... under the beta-divergence (kernels_masked_beta.hip, docs/MISSING.md "Beta-divergence"): the same launch shape and order of sums with p = wh_p + eps mapped per
+// entry, in place
+//     A(row, :) <- A(row, :) .* (sum_p val[p] p^(beta - 2) B(idx[p], :) ./ (sum_p p^(beta - 1) B(idx[p], :) + eps + l1 + l2 A(row, :)))^gamma
+// beta is taken in the precision of T (0: the Itakura-Saito map, 1: the KL map, else the general one); gamma as launch_beta_update.  t_frob / t_div (both or
+// neither): t_frob[row] = sum_p (val[p] - p)^2 and t_div[row] = sum_p d_beta(val[p] | p) with the old row.  update = false: the terms only, A untouched.  sumsq_part
+// as above.  hipErrorInvalidValue for another RP, a beta or penalty that is not finite, a negative penalty, and a launch with nothing to write.
+template <typename T>
+hipError_t launch_masked_beta_half_step(const int* ptr, const int* idx, const T* val, T* A, const T* B, int RP, T eps, double beta, T l1, T l2, bool update,
+                                        T* t_frob, T* t_div, T* sumsq_part, int rows, hipStream_t stream);
 
 // ---- dense beta-divergence NMF: generalised KL (beta = 1), Itakura-Saito (beta = 0) and the general form (any other finite beta), with optional L1 / L2 penalties, on
 // ---- a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) ---------------------------------------------------------------------------------------------------

@@ -132,12 +132,12 @@ __global__ __launch_bounds__(256) void k_compact_pointers(const int* __restrict_
 	if (s <= segments) ptr[s] = off[s * per];
 }
 
-// rule 1: finite and >= 0, rule 2: finite
+// rule 1: finite and >= 0, rule 2: finite, rule 3: finite and > 0
 template <typename T>
 __global__ __launch_bounds__(256) void k_sparse_value_rule(const T* __restrict__ values, long nnz, int rule, int* __restrict__ flags) {
 	const long p = (long)blockIdx.x * 256 + threadIdx.x;
 	bool bad = false;
-	if (p < nnz) { const T v = values[p]; bad = !io_finite(v) || (rule == 1 && v < T(0)); }
+	if (p < nnz) { const T v = values[p]; bad = !io_finite(v) || (rule == 1 && v < T(0)) || (rule == 3 && !(v > T(0))); }
 	if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flags, IMPORT_BAD_VALUE);
 }
 
@@ -187,7 +187,7 @@ template hipError_t launch_compact_scatter<double>(const double*, long, int, int
 
 template <typename T>
 hipError_t launch_sparse_value_rule(const T* values, long nnz, int rule, int* flags, hipStream_t stream) {
-	if (rule != 1 && rule != 2) return hipErrorInvalidValue;
+	if (rule < 1 || rule > 3) return hipErrorInvalidValue;
 	if (nnz <= 0) return hipSuccess;
 	hipLaunchKernelGGL((k_sparse_value_rule<T>), dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, stream, values, nnz, rule, flags);
 	return hipGetLastError();

@@ -49,6 +49,11 @@ class _ParamsV6(C.Structure):
     _fields_ = [("v5", _ParamsV5), ("batch_size", C.c_double), ("forget_factor", C.c_double)]
 
 
+class _ParamsV7(C.Structure):
+    """nmfamd_params_v7: nmfamd_params_v6 (which keeps its size) followed by the fields added since."""
+    _fields_ = [("v6", _ParamsV6), ("missing_divergence", C.c_double), ("missing_beta", C.c_double)]
+
+
 class _Geometry(C.Structure):
     _fields_ = [("m", C.c_int), ("n", C.c_int), ("r", C.c_int), ("padded_rank", C.c_int),
                 ("padded_m", C.c_long), ("padded_n", C.c_long), ("slabs_h", C.c_int), ("slabs_w", C.c_int),
@@ -171,8 +176,13 @@ def _count(v) -> int:
 
 
 def _param_values(lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0, theta=0.0, divergence="frobenius", sparse_compute=False, precision="native",
-                  missing_values=False, dense_compute=False, beta=None, weighted=False, mixed_precision=False, batch_size=None, forget_factor=0.7) -> list:
-    """The sixteen doubles of nmfamd_params_v6, in its order, from the keyword arguments of Engine (and of plan_geometry)."""
+                  missing_values=False, dense_compute=False, beta=None, weighted=False, mixed_precision=False, batch_size=None, forget_factor=0.7,
+                  missing_divergence="frobenius", missing_beta=None) -> list:
+    """The eighteen doubles of nmfamd_params_v7, in its order, from the keyword arguments of Engine (and of plan_geometry)."""
+    if missing_beta is not None and missing_divergence != "beta":
+        raise ValueError('missing_beta needs missing_divergence="beta"')
+    if missing_divergence == "beta" and missing_beta is None:
+        raise ValueError('missing_divergence="beta" needs a missing_beta')
     if not batch_size:
         batch_size, forget_factor = 0.0, 0.0
     if beta is not None and divergence != "beta":
@@ -181,11 +191,14 @@ def _param_values(lam=0.0, lambda_w=0.0, lambda_h=0.0, alpha_w=0.0, alpha_h=0.0,
         raise ValueError('divergence="beta" needs a beta')
     return [lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, {"frobenius": 0.0, "kl": 1.0, "is": 2.0, "beta": 3.0}[divergence],
             float(sparse_compute or missing_values), {"native": 0.0, "bf16": 1.0, "fp32_mfma": -1.0}[precision],
-            float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted), float(mixed_precision), float(batch_size), float(forget_factor)]
+            float(missing_values), float(dense_compute), float(beta or 0.0), float(weighted), float(mixed_precision), float(batch_size), float(forget_factor),
+            {"frobenius": 0.0, "kl": 1.0, "is": 2.0, "beta": 3.0}[missing_divergence], float(missing_beta or 0.0)]
 
 
-def _params_struct(v: list) -> _ParamsV6:
-    return _ParamsV6(_ParamsV5(_ParamsV4(_ParamsV3(_ParamsV2(_Params(*v[:10]), v[10]), v[11]), v[12]), v[13]), v[14], v[15])
+def _params_struct(v: list) -> _ParamsV7:
+    """v: the values of _param_values; a list of sixteen (nmfamd_params_v6) leaves the two fields added since at 0."""
+    v = list(v) + [0.0] * (18 - len(v))
+    return _ParamsV7(_ParamsV6(_ParamsV5(_ParamsV4(_ParamsV3(_ParamsV2(_Params(*v[:10]), v[10]), v[11]), v[12]), v[13]), v[14], v[15]), v[16], v[17])
 
 
 def plan_geometry(m: int, n: int, r: int, algorithm: str = "mu", dtype=np.float32, *, num_cus: int, memory_side_cache_bytes: int, free_bytes: int,
@@ -212,14 +225,19 @@ class Engine:
                  sparse_compute: bool = False, precision: str = "native", row_blocks: int = 1, missing_values: bool = False,
                  l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None, weighted: bool = False, mixed_precision: bool = False,
                  batch_size=None, forget_factor=0.7, sweeps_h: int = 1, sweeps_w: int = 1, sweep_tolerance: float = 0.0,
-                 steps_h: Optional[int] = None, steps_w: Optional[int] = None, step_tolerance: Optional[float] = None):
+                 steps_h: Optional[int] = None, steps_w: Optional[int] = None, step_tolerance: Optional[float] = None,
+                 missing_divergence: str = "frobenius", missing_beta=None):
         """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V),
         "is" (Itakura-Saito, always dense: every entry of V > 0) or "beta" (the beta-divergence at `beta`, any finite value, always dense: scikit-learn's
         solver="mu" with beta_loss=beta; beta=0.0 and beta=1.0 are the "is" and the dense "kl" engines; beta <= 0 needs every entry of V > 0) --
         docs/DIVERGENCE.md.  The dense divergence engines are "mu" only, rank <= 256, single GPU; divergence_value reports their objective.
 
         missing_values=True: fit the observed entries only (docs/MISSING.md) -- the stored entries of upload_sparse, the non-NaN entries of
-        upload (zeros included).  Multiplicative update ("mu") with the Frobenius objective only; implies sparse_compute.
+        upload (zeros included).  Multiplicative update ("mu") only; implies sparse_compute.  missing_divergence: the objective over the observed entries --
+        "frobenius" (the default), "kl", "is" or "beta" at missing_beta (any finite value; 0.0 and 1.0 are "is" and "kl"), docs/MISSING.md "Beta-divergence": the
+        weighted update at 0 / 1 weights in O(nnz r) per iteration.  beta <= 0 needs every stored value > 0, beta > 0 takes stored zeros as observations; such an
+        engine takes l1_w ... l2_h (set_penalties) and constant_w, and divergence_value reports its objective.  `divergence` itself stays refused beside
+        missing_values.
 
         l1_w, l1_h, l2_w, l2_h: the L1 / L2 penalties on W and H of scikit-learn's coordinate descent ("hals", docs/HALS.md) and of its multiplicative update
         (the dense divergence engines, docs/DIVERGENCE.md); see set_penalties.  sparse_compute=True is available for "mu" and "hals" (rank <= 256).
@@ -252,7 +270,7 @@ class Engine:
         self._bind(m, n, r, dtype)
         self._ctor = dict(algorithm=algorithm, stream=stream, row_blocks=row_blocks,
                           params=_param_values(lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, divergence, sparse_compute, precision, missing_values, dense_compute, beta,
-                                               weighted, mixed_precision, batch_size, forget_factor),
+                                               weighted, mixed_precision, batch_size, forget_factor, missing_divergence, missing_beta),
                           penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)], sweeps=[_count(sweeps_h), _count(sweeps_w)],
                           sweep_tolerance=float(sweep_tolerance), step_tolerance=None if step_tolerance is None else float(step_tolerance),
                           steps=None if steps_h is None and steps_w is None else [_count(8 if steps_h is None else steps_h), _count(8 if steps_w is None else steps_w)])
@@ -288,7 +306,7 @@ class Engine:
         # row_blocks > 1: the padded row count is a multiple of 128 * row_blocks (row-block form of the sharded W step)
         if not hasattr(self._lib, "nmfamd_engine_create_v2"):
             # (NMFAMD_LIBRARY names a build from before the sized entry -- tools/time_beta.py times such a build: it reads the frozen struct only)
-            st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p.v5.v4.v3.v2.base), self.dtype.itemsize,
+            st = self._lib.nmfamd_engine_create_blocks(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p.v6.v5.v4.v3.v2.base), self.dtype.itemsize,
                                                        C.c_void_p(c["stream"]), int(c["row_blocks"]), C.byref(h))
         else:
             st = self._lib.nmfamd_engine_create_v2(self.m, self.n, self.r, ALGORITHMS[c["algorithm"]], C.byref(p), C.c_ulong(C.sizeof(p)), self.dtype.itemsize,
@@ -451,7 +469,8 @@ class Engine:
     def set_penalties(self, l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0):
         """HALS: the iterations that follow minimise 1/2 ||V - W H||^2 + l1_w ||W||_1 + l1_h ||H||_1 + 1/2 l2_w ||W||^2 + 1/2 l2_h ||H||^2
         (nmfamd_engine_set_hals_penalties; docs/HALS.md has the mapping from scikit-learn's alpha_W, alpha_H, l1_ratio).  Dense divergence engines: the
-        same four terms added to the divergence (scikit-learn's multiplicative update, docs/DIVERGENCE.md).  Valid between iterations; all zeros restores
+        same four terms added to the divergence (scikit-learn's multiplicative update, docs/DIVERGENCE.md); masked divergence engines (missing_divergence): likewise, over
+        the observed entries (docs/MISSING.md).  Valid between iterations; all zeros restores
         the unpenalised iteration, normalisation included.  frobenius / rmsd / divergence_value keep reporting the unpenalised figures."""
         vals = [float(l1_w), float(l1_h), float(l2_w), float(l2_h)]
         self._check(self._lib.nmfamd_engine_set_hals_penalties(self._h, *(C.c_double(v) for v in vals)), "set_hals_penalties")
@@ -1294,6 +1313,40 @@ def op_kl_fused(ptr: np.ndarray, idx: np.ndarray, val: np.ndarray, A: np.ndarray
     if st != 0:
         raise EngineError(st, "nmfamd_op_kl_fused")
     return {"out": out, "t_vwh": tv, "t_kl": tk}
+
+
+def masked_norm_parts(rows: int) -> int:
+    """The number of per-workgroup partial vectors a masked half-step over `rows` rows leaves with sums of squares (nmfamd_masked_norm_parts)."""
+    return int(library().nmfamd_masked_norm_parts(int(rows)))
+
+
+def op_masked_beta_half_step(ptr: np.ndarray, idx: np.ndarray, val: np.ndarray, A: np.ndarray, B: np.ndarray, rows: int, divergence: str = "kl", beta: Optional[float] = None,
+                             l1: float = 0.0, l2: float = 0.0, update: bool = True, terms: bool = False, sumsq: bool = False, *, fill=np.nan):
+    """One launch of the masked beta-divergence half-step (launch_masked_beta_half_step, docs/MISSING.md "Beta-divergence"): A (>= rows, RP) the output rows' own
+    factor rows, B (b_rows, RP) the gathered panel, ptr / idx / val the image (rows + 1 offsets); divergence "kl", "is" or "beta" with beta, as Engine's
+    missing_divergence / missing_beta.  Returns a dict: `A` (a new array: rows >= `rows` and, with update=False, every row as given), `t_frob`, `t_div` (rows
+    values, with terms) and `sumsq_part` ((masked_norm_parts(rows), RP), with sumsq) -- pre-filled with `fill`, else None."""
+    dt = _sparse_dtype(val)
+    ptr, idx, val = _sparse_image(ptr, idx, val, dt)
+    A = np.array(A, dtype=dt, order="C"); B = np.ascontiguousarray(B, dtype=dt)
+    rows = int(rows)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1] or A.shape[0] < rows:
+        raise ValueError("shapes: A (>= rows, RP); B (b_rows, RP)")
+    if ptr.shape != (rows + 1,):
+        raise ValueError("ptr: rows + 1 offsets")
+    if (beta is not None) != (divergence == "beta"):
+        raise ValueError('beta goes with divergence="beta"')
+    RP = A.shape[1]
+    tf = np.full(rows, fill, dt) if terms else None
+    td = np.full(rows, fill, dt) if terms else None
+    parts = masked_norm_parts(rows) if sumsq else 0
+    sq = np.full((parts, RP), fill, dt) if sumsq else None
+    st = _sparse_fn("masked_beta_half_step", dt)(_p(ptr), _p(idx), _p(val), C.c_long(len(val)), _p(A), C.c_long(A.shape[0]), _p(B), C.c_long(B.shape[0]), RP, rows,
+                                                 {"kl": 1, "is": 2, "beta": 3}[divergence], C.c_double(float(beta or 0.0)), C.c_double(float(l1)), C.c_double(float(l2)),
+                                                 int(bool(update)), _p(tf), _p(td), _p(sq), parts)
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_masked_beta_half_step")
+    return {"A": A, "t_frob": tf, "t_div": td, "sumsq_part": sq}
 
 
 def op_kl_update(P: np.ndarray, num_parts: np.ndarray, den: np.ndarray, scale: Optional[np.ndarray] = None, want_sumsq: bool = False, want_sum: bool = True,
