@@ -526,6 +526,33 @@ NMFAMD_API int nmfamd_op_inverse_ex_f32(const float* A, long lda, int r, float o
                                         const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT, long ldo);
 NMFAMD_API int nmfamd_op_inverse_ex_f64(const double* A, long lda, int r, double offdiag, double diag, int route, double* Ainv_full, double* A_after, int* rp_out,
                                         const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT, long ldo);
+/* Test entry of the rank-64 Gram matrix from the split image of a panel (docs/GRAM.md): one launch at a time, every input caller-built, every output buffer uploaded as
+ * the caller filled it and copied back whole.  P: [len][64] panel rows (NULL: no image, which the launcher refuses); colsq_part: [colsq_parts][64] partial sums of squares
+ * or NULL; normalize, ksplit, spread: GramReduceArgs' fields as given; finish: the spread form with spread_out and the counter word.  ride 0: launch_gram_image_args;
+ * 1 / 2: as passenger workgroups of the x-tiled / y-tiled split-operand product of A_prod (X x Y, column-major) and F_prod (64 x Y) over the 16-row image, whose result
+ * goes to OUT_ride (64 x X) and, from a launch without passengers, to OUT_plain.  3: of the x-tiled product over 128-row tiles with FactorProductPlan::col_split = 2
+ * (128 x 32 workgroups, one slab: a narrow column shard's V H^T).  `launches` (1 ... 4) launches in a row share G, scale and the counter; launch i finishes
+ * into spread_out + 4096 i.  G: g_elems floats (4096 per slice or piece).  counter[0]: the counter word before the first launch; counter[1 + i]: after launch i.
+ * plan[6]: matrices the form writes into G, passenger workgroups, pairs of K-steps, K-steps of the image, x-tiles and K slices of the product.
+ * NMFAMD_INVALID_ARGUMENT wherever a launcher refuses. */
+NMFAMD_API int nmfamd_op_gram_image_f32(const float* P, int len, const float* colsq_part, int colsq_parts, int normalize, int ksplit, int spread, int finish, int ride,
+                                        int launches, float* G, long g_elems, float* scale, float* spread_out, unsigned* counter, int* plan,
+                                        const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT_plain, float* OUT_ride, long ldo);
+/* Test entry of the rank-64 Gram matrix from partial 64 x 64 matrices (docs/GRAM.md).  route 0: launch_mu64_gram_partials (P [len_pad][64] -> partials, one matrix per
+ * 64 panel rows, parts = len_pad / 64); 1: launch_mu64_gram_reduce; 2: the same reduction as the passenger workgroups of the split-operand product of A_prod and F_prod
+ * (as nmfamd_op_gram_image_f32, ride 1), 6: the same on the col_split product launch (ride 3); 3: launch_gram64_from_partials (scale NULL: the sum alone); 4: launch_gram64_normalize_all; 5: launch_gram64_reduce_scale_all
+ * (sumsq_part: [sq_parts][64]).  Routes 4 and 5 scale the panel P in place and write x3_ks K-steps of its split image into x3 (the image of len_pad / 16 + 1 K-steps).
+ * Buffers a route does not use may be NULL. */
+NMFAMD_API int nmfamd_op_gram64_partials_f32(int route, float* P, int len_pad, float* partials, int parts, int normalize, const float* sumsq_part, int sq_parts,
+                                             float* Graw, float* G, float* scale, void* x3, int x3_ks,
+                                             const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT_plain, float* OUT_ride, long ldo);
+/* Test entry of the fp32 Gram matrix at padded ranks 128 ... 512 (docs/GRAM.md).  route 0: launch_gram_wide_f32; 1: launch_gram_wide_fused_f32; 2: launch_gram_reduce_x3
+ * alone on the caller's slices; 3: the slices as passenger workgroups of the x-tiled split-operand product of A_prod (X x Y) and F_prod (r_prod x Y) over the 16-row image,
+ * for the slice count of route 1.  P: [len][RP] panel rows; partial: part_elems floats ([slices][RP][RP]); G: [RP][RP]; qx3: the split image of G (RP / 16 + 1 K-steps);
+ * sumsq_part: [sq_parts][RP] or NULL; scale_out: [RP].  plan[0]: the slice count the launcher settled on. */
+NMFAMD_API int nmfamd_op_gram_wide_f32(int route, const float* P, int RP, int len, int parts, float* partial, long part_elems, float* G, void* qx3, const float* sumsq_part,
+                                       int sq_parts, float* scale_out, int* plan,
+                                       const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, int r_prod, float* OUT_plain, float* OUT_ride, long ldo);
 /* The passes between the update of a factor panel and the next product at padded rank 256 with bf16 product operands (129 <= r <= 256):
  * optional column normalisation (colsq: r sums of squares or NULL), nsNMF smoothing by theta, bf16 rounding; the Gram matrix of the panel and of
  * the smoothed panel.  P, P_out, pack_out: [len][ldp / r] rows of r values; G_raw, G_smooth: [r][r].  Outputs may be NULL. */

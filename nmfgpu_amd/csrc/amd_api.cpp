@@ -668,7 +668,10 @@ int nmfamd_op_factor_product_bf16(const float* A, long lda, int X, int Y, const 
 
 // x16: the x-tiled image in 16-row tiles (the engine's ONE resident image, read along its output index)
 static int op_factor_product_x3(const float* A, long lda, int X, int Y, const float* F, long ldf, int r, float* OUT, long ldo, int reps, double* avg_us, bool y_tiled, bool x16 = false,
-                                const InversePassenger* passenger = nullptr) {
+                                const InversePassenger* passenger = nullptr, const GramReduceArgs* ride = nullptr, int* out_plan = nullptr, int col_split = 0) {
+	// ride: passenger workgroups of any other kind, every field as given (the Gram test entries); out_plan: {x-tiles, K slices} of the product launch
+	// col_split 2 (r <= 64, the x-tiled form on 128-row tiles): 128 x 32 workgroups and one slab, as Engine::plan sets a narrow column shard's V H^T up
+	if (col_split != 0 && (col_split != 2 || y_tiled || x16 || r > 64)) return NMFAMD_INVALID_ARGUMENT;
 	if (!A || !F || !OUT || X <= 0 || Y <= 0 || r <= 0 || lda < X || ldf < r || ldo < r) return NMFAMD_INVALID_ARGUMENT;
 	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
 	int dev = 0; hipDeviceProp_t prop;
@@ -678,6 +681,7 @@ static int op_factor_product_x3(const float* A, long lda, int X, int Y, const fl
 	const int KS = (Y + 15) / 16;
 	FactorProductPlan plan; plan.th = 128; plan.xtiles = (int)(Xp / 128); plan.steps_total = KS; plan.nb = 2; plan.chunks = 1;
 	plan.splits = plan_splits_x3(plan.xtiles, KS, prop.multiProcessorCount);
+	if (col_split == 2) { plan.splits = 1; plan.col_split = 2; }
 	DevBuf dA, dT, dF, dFb, dS, dO;
 	const long slab_stride = (long)RP * Xp;
 	if (dA.alloc(sizeof(float) * Xp * Yp) != hipSuccess || dT.alloc(sizeof(float) * Xp * Yp) != hipSuccess || dF.alloc(sizeof(float) * RP * Yp) != hipSuccess ||
@@ -696,8 +700,10 @@ static int op_factor_product_x3(const float* A, long lda, int X, int Y, const fl
 	if (launch_pack_panel_x3((const float*)dF.p, RP, Y, dFb.p, KS, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
 	GramReduceArgs rg = {nullptr, 0, nullptr, nullptr, 0};
 	if (passenger) { rg.inv_a = passenger->a; rg.inv_out = passenger->out; rg.inv_offdiag = passenger->offdiag; rg.inv_diag = passenger->diag; rg.inv_r = passenger->r; }
-	if (hipError_t e = launch_factor_product_x3(plan, (const float*)dT.p, tstride, dFb.p, RP, (float*)dS.p, slab_stride, nullptr, passenger ? &rg : nullptr, nullptr, y_tiled, ith); e != hipSuccess)
-		return passenger && e == hipErrorInvalidValue ? NMFAMD_INVALID_ARGUMENT : NMFAMD_HIP_ERROR;
+	if (ride) rg = *ride;
+	if (out_plan) { out_plan[0] = plan.xtiles; out_plan[1] = plan.splits; }
+	if (hipError_t e = launch_factor_product_x3(plan, (const float*)dT.p, tstride, dFb.p, RP, (float*)dS.p, slab_stride, nullptr, (passenger || ride) ? &rg : nullptr, nullptr, y_tiled, ith); e != hipSuccess)
+		return (passenger || ride) && e == hipErrorInvalidValue ? NMFAMD_INVALID_ARGUMENT : NMFAMD_HIP_ERROR;
 	if (launch_reduce_slabs<float>((const float*)dS.p, plan.splits, slab_stride, (float*)dO.p, slab_stride, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (hipMemcpy2D(OUT, ldo * sizeof(float), dO.p, RP * sizeof(float), r * sizeof(float), X, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
 	if (reps > 0 && avg_us) {
@@ -865,6 +871,175 @@ int nmfamd_op_inverse_ex_f32(const float* A, long lda, int r, float offdiag, flo
 int nmfamd_op_inverse_ex_f64(const double* A, long lda, int r, double offdiag, double diag, int route, double* Ainv_full, double* A_after, int* rp_out,
                              const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT, long ldo) {
 	return op_inverse_ex<double>(A, lda, r, offdiag, diag, route, Ainv_full, A_after, rp_out, A_prod, lda_prod, X, Y, F_prod, ldf_prod, OUT, ldo);
+}
+
+// Test entry of the rank-64 Gram matrix from the split image (gram_image.h, docs/GRAM.md): one launch at a time (`launches` of them in a row into the same buffers), every
+// input caller-built, every output buffer uploaded as the caller filled it.  ride 0: launch_gram_image_args; 1 / 2: the same request as passenger workgroups of the x-tiled /
+// y-tiled split-operand product over the 16-row image of A_prod, F_prod (the engine's two forms), whose result goes to OUT_ride and, from a launch without passengers, to OUT_plain.
+int nmfamd_op_gram_image_f32(const float* P, int len, const float* colsq_part, int colsq_parts, int normalize, int ksplit, int spread, int finish, int ride, int launches,
+                             float* G, long g_elems, float* scale, float* spread_out, unsigned* counter, int* plan,
+                             const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT_plain, float* OUT_ride, long ldo) {
+	if (!G || !plan || !counter || len <= 0 || launches < 1 || launches > 4 || ride < 0 || ride > 3 || (colsq_part && colsq_parts < 1) || (finish && !spread_out)) return NMFAMD_INVALID_ARGUMENT;
+	if (ride != 0 && (!A_prod || !F_prod || !OUT_plain || !OUT_ride || X <= 0 || Y <= 0 || lda_prod < X || ldf_prod < 64 || ldo < 64)) return NMFAMD_INVALID_ARGUMENT;
+	// (a request the launcher must refuse still gets there: the buffer only has to hold what an accepted one writes)
+	const int slices = spread > 0 ? GRAM_SPREAD_SLICES : (ksplit > 1 ? std::min(ksplit, GRAM_KSPLIT_MAX) : 1);
+	if (g_elems < 4096L * slices) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const int KS = (len + 15) / 16;
+	DevBuf dP, dX, dC, dG, dS, dO, dN;
+	if (dP.alloc(sizeof(float) * 64 * (size_t)(16 * KS)) != hipSuccess || dX.alloc(3 * 16 * (size_t)(KS + 1) * 2 * 64) != hipSuccess ||
+	    dC.alloc(sizeof(float) * 64 * (size_t)std::max(colsq_parts, 1)) != hipSuccess || dG.alloc(sizeof(float) * g_elems) != hipSuccess || dS.alloc(sizeof(float) * 64) != hipSuccess ||
+	    dO.alloc(sizeof(float) * 4096 * (size_t)launches) != hipSuccess || dN.alloc(sizeof(unsigned)) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+	if (P) {
+		if (hipMemcpy(dP.p, P, sizeof(float) * 64 * (size_t)len, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+		if (launch_pack_panel_x3((const float*)dP.p, 64, len, dX.p, KS, nullptr) != hipSuccess) return NMFAMD_HIP_ERROR;
+	}
+	if (colsq_part && hipMemcpy(dC.p, colsq_part, sizeof(float) * 64 * (size_t)colsq_parts, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (hipMemcpy(dG.p, G, sizeof(float) * g_elems, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (scale && hipMemcpy(dS.p, scale, sizeof(float) * 64, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (spread_out && hipMemcpy(dO.p, spread_out, sizeof(float) * 4096 * (size_t)launches, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (hipMemcpy(dN.p, counter, sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	GramReduceArgs rg = {nullptr, 0, (float*)dG.p, scale ? (float*)dS.p : nullptr, normalize};
+	rg.image = P ? dX.p : nullptr; rg.image_ks = KS;
+	rg.colsq_part = colsq_part ? (const float*)dC.p : nullptr; rg.colsq_parts = colsq_part ? colsq_parts : 0;
+	rg.ksplit = ksplit; rg.spread = spread;
+	if (finish) rg.spread_counter = (unsigned*)dN.p;
+	int pplan[2] = {0, 0};
+	if (ride != 0) {
+		// the product alone first: what it writes must not depend on who rides
+		if (int st = op_factor_product_x3(A_prod, lda_prod, X, Y, F_prod, ldf_prod, 64, OUT_plain, ldo, 0, nullptr, ride == 2, ride == 1, nullptr, nullptr, nullptr, ride == 3 ? 2 : 0); st != NMFAMD_OK) return st;
+	}
+	for (int i = 0; i < launches; ++i) {
+		if (finish) rg.spread_out = (float*)dO.p + 4096L * i;
+		if (ride != 0) {
+			if (int st = op_factor_product_x3(A_prod, lda_prod, X, Y, F_prod, ldf_prod, 64, OUT_ride, ldo, 0, nullptr, ride == 2, ride == 1, nullptr, &rg, pplan, ride == 3 ? 2 : 0); st != NMFAMD_OK) return st;
+		} else {
+			const hipError_t e = launch_gram_image_args(rg, nullptr);
+			if (e == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
+			if (e != hipSuccess) return NMFAMD_HIP_ERROR;
+		}
+		if (hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
+		if (hipMemcpy(counter + 1 + i, dN.p, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	}
+	if (hipMemcpy(G, dG.p, sizeof(float) * g_elems, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (scale && hipMemcpy(scale, dS.p, sizeof(float) * 64, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (spread_out && hipMemcpy(spread_out, dO.p, sizeof(float) * 4096 * (size_t)launches, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	plan[0] = slices; plan[1] = gram_image_workgroups(rg); plan[2] = (KS + 2) / 2; plan[3] = KS;        // (the launchers' own count, kernels.h)
+	plan[4] = pplan[0]; plan[5] = pplan[1];
+	return NMFAMD_OK;
+}
+
+// Test entry of the rank-64 Gram matrix from partial matrices (kernels_mu64.hip, docs/GRAM.md), one launcher per route:
+//   0 launch_mu64_gram_partials   1 launch_mu64_gram_reduce   2 gram_reduce_block_x3, the passengers of the split-operand product (x-tiled over the 16-row image)
+//   6 the same passengers on the col_split product launch (x-tiled over 128-row tiles, 128 x 32 workgroups)
+//   3 launch_gram64_from_partials (scale NULL: the sum alone)   4 launch_gram64_normalize_all   5 launch_gram64_reduce_scale_all
+// Every buffer is uploaded as the caller filled it and copied back whole.
+int nmfamd_op_gram64_partials_f32(int route, float* P, int len_pad, float* partials, int parts, int normalize, const float* sumsq_part, int sq_parts,
+                                  float* Graw, float* G, float* scale, void* x3, int x3_ks,
+                                  const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, float* OUT_plain, float* OUT_ride, long ldo) {
+	if (route < 0 || route > 6) return NMFAMD_INVALID_ARGUMENT;
+	const bool cs_ride = route == 6;          // route 2 on the 128 x 32 workgroups of a col_split product launch
+	if (cs_ride) route = 2;
+	const bool panel = route == 0 || route == 4 || route == 5;
+	if (panel && (!P || len_pad < 64 || len_pad % 64 != 0)) return NMFAMD_INVALID_ARGUMENT;
+	if (route == 0 ? (!partials || parts != len_pad / 64) : (!partials || !G || parts < 0)) return NMFAMD_INVALID_ARGUMENT;
+	if ((route == 4 || route == 5) && (!scale || !x3 || x3_ks < 0 || x3_ks > len_pad / 16)) return NMFAMD_INVALID_ARGUMENT;
+	if (route == 4 && !Graw) return NMFAMD_INVALID_ARGUMENT;
+	if (route >= 1 && route <= 4 && parts < 1) return NMFAMD_INVALID_ARGUMENT;
+	if (route == 5 && (!sumsq_part || sq_parts < 0)) return NMFAMD_INVALID_ARGUMENT;
+	if (route == 2 && (!A_prod || !F_prod || !OUT_plain || !OUT_ride || X <= 0 || Y <= 0 || lda_prod < X || ldf_prod < 64 || ldo < 64)) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const size_t pb = panel ? sizeof(float) * 64 * (size_t)len_pad : 0, qb = sizeof(float) * 4096 * (size_t)std::max(parts, 1), gb = sizeof(float) * 4096;
+	const size_t xb = panel && x3 ? 3 * 16 * (size_t)(len_pad / 16 + 1) * 2 * 64 : 0, sb = sizeof(float) * 64 * (size_t)std::max(sq_parts, 1);
+	DevBuf dP, dQ, dR, dG, dS, dX, dV;
+	if (dP.alloc(pb) != hipSuccess || dQ.alloc(qb) != hipSuccess || dR.alloc(gb) != hipSuccess || dG.alloc(gb) != hipSuccess || dS.alloc(256) != hipSuccess ||
+	    dX.alloc(xb) != hipSuccess || dV.alloc(sb) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+	if (pb && hipMemcpy(dP.p, P, pb, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (parts > 0 && hipMemcpy(dQ.p, partials, sizeof(float) * 4096 * (size_t)parts, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (Graw && hipMemcpy(dR.p, Graw, gb, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (G && hipMemcpy(dG.p, G, gb, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (scale && hipMemcpy(dS.p, scale, 256, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (xb && hipMemcpy(dX.p, x3, xb, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (sumsq_part && sq_parts > 0 && hipMemcpy(dV.p, sumsq_part, sizeof(float) * 64 * (size_t)sq_parts, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	GramReduceArgs rg = {(const float*)dQ.p, parts, (float*)dG.p, scale ? (float*)dS.p : nullptr, normalize};
+	hipError_t e = hipSuccess;
+	switch (route) {
+		case 0: e = launch_mu64_gram_partials((const float*)dP.p, len_pad, (float*)dQ.p, nullptr); break;
+		case 1: e = launch_mu64_gram_reduce(rg, nullptr); break;
+		case 2: {
+			if (int st = op_factor_product_x3(A_prod, lda_prod, X, Y, F_prod, ldf_prod, 64, OUT_plain, ldo, 0, nullptr, false, !cs_ride, nullptr, nullptr, nullptr, cs_ride ? 2 : 0); st != NMFAMD_OK) return st;
+			if (int st = op_factor_product_x3(A_prod, lda_prod, X, Y, F_prod, ldf_prod, 64, OUT_ride, ldo, 0, nullptr, false, !cs_ride, nullptr, &rg, nullptr, cs_ride ? 2 : 0); st != NMFAMD_OK) return st;
+			break;
+		}
+		case 3: e = launch_gram64_from_partials((const float*)dQ.p, parts, (float*)dG.p, scale ? (float*)dS.p : nullptr, nullptr); break;
+		case 4: e = launch_gram64_normalize_all((const float*)dQ.p, parts, (float*)dR.p, (float*)dG.p, (float*)dS.p, (float*)dP.p, len_pad, dX.p, x3_ks, nullptr); break;
+		default: e = launch_gram64_reduce_scale_all((const float*)dQ.p, parts, (const float*)dV.p, sq_parts, (float*)dG.p, (float*)dS.p, (float*)dP.p, len_pad, dX.p, x3_ks, nullptr); break;
+	}
+	if (e == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
+	if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (pb && hipMemcpy(P, dP.p, pb, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (route == 0 && hipMemcpy(partials, dQ.p, sizeof(float) * 4096 * (size_t)parts, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (Graw && hipMemcpy(Graw, dR.p, gb, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (G && hipMemcpy(G, dG.p, gb, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (scale && hipMemcpy(scale, dS.p, 256, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (xb && hipMemcpy(x3, dX.p, xb, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
+
+// Test entry of the Gram matrix at padded ranks 128 ... 512 in fp32 (kernels_wide.hip, gram_wide.h, docs/GRAM.md):
+//   0 launch_gram_wide_f32 (mirrored slices, launch_reduce_partials)   1 launch_gram_wide_fused_f32 (k_gram_wide_x3<2, false>, k_gram_reduce_x3)
+//   2 launch_gram_reduce_x3 alone on the caller's slices   3 the slices as passenger workgroups (GramReduceArgs::wide_P) of the x-tiled split-operand product of
+//   A_prod (X x Y) and F_prod (r_prod x Y) over the 16-row image, for the slice count of route 1
+// P: [len][RP]; partial: part_elems floats; every output buffer is uploaded as the caller filled it and copied back whole.  plan[0]: the slice count the launcher settled on.
+int nmfamd_op_gram_wide_f32(int route, const float* P, int RP, int len, int parts, float* partial, long part_elems, float* G, void* qx3, const float* sumsq_part, int sq_parts,
+                            float* scale_out, int* plan,
+                            const float* A_prod, long lda_prod, int X, int Y, const float* F_prod, long ldf_prod, int r_prod, float* OUT_plain, float* OUT_ride, long ldo) {
+	if (route < 0 || route > 3 || !partial || !plan || RP < 64 || RP % 64 != 0 || RP > 512 || part_elems < 0) return NMFAMD_INVALID_ARGUMENT;
+	if (route != 2 && (!P || len <= 0)) return NMFAMD_INVALID_ARGUMENT;
+	if (route != 3 && !G) return NMFAMD_INVALID_ARGUMENT;
+	if (sumsq_part && (!scale_out || sq_parts < 1)) return NMFAMD_INVALID_ARGUMENT;
+	if (route == 3 && (!A_prod || !F_prod || !OUT_plain || !OUT_ride || X <= 0 || Y <= 0 || r_prod <= 0 || lda_prod < X || ldf_prod < r_prod || ldo < r_prod)) return NMFAMD_INVALID_ARGUMENT;
+	// (the passengers read the panel with the PRODUCT's padded rank: the two must agree, or the product be the rank-64 form that refuses them)
+	if (route == 3 && padded_rank(r_prod) != RP && padded_rank(r_prod) != 64) return NMFAMD_INVALID_ARGUMENT;
+	const bool wide = RP % 128 == 0;
+	// the slice count each launcher settles on, from the launchers' own functions (kernels_wide.hip); a request a launcher must refuse still gets there, and writes nothing
+	int settled = parts;
+	if (wide && route == 0) settled = gram_wide_parts(RP, len, parts);
+	if (wide && (route == 1 || route == 3)) settled = gram_wide_fused_parts(RP, len, parts);
+	const size_t mat = (size_t)RP * RP;
+	if (wide && settled >= 1 && (size_t)part_elems < mat * (size_t)settled) return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const long lp = pad128(std::max(len, 1));
+	const size_t xb = 3 * 16 * (size_t)(RP / 16 + 1) * (RP / 32) * 64;
+	DevBuf dP, dQ, dG, dX, dV, dS;
+	if (dP.alloc(sizeof(float) * RP * (size_t)lp) != hipSuccess || dQ.alloc(sizeof(float) * (size_t)part_elems) != hipSuccess || dG.alloc(sizeof(float) * mat) != hipSuccess ||
+	    dX.alloc(xb) != hipSuccess || dV.alloc(sizeof(float) * RP * (size_t)std::max(sq_parts, 1)) != hipSuccess || dS.alloc(sizeof(float) * RP) != hipSuccess) return NMFAMD_NO_DEVICE_MEMORY;
+	if (P && hipMemcpy(dP.p, P, sizeof(float) * RP * (size_t)len, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (part_elems > 0 && hipMemcpy(dQ.p, partial, sizeof(float) * (size_t)part_elems, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (G && hipMemcpy(dG.p, G, sizeof(float) * mat, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (qx3 && hipMemcpy(dX.p, qx3, xb, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (sumsq_part && hipMemcpy(dV.p, sumsq_part, sizeof(float) * RP * (size_t)sq_parts, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (scale_out && hipMemcpy(dS.p, scale_out, sizeof(float) * RP, hipMemcpyHostToDevice) != hipSuccess) return NMFAMD_HIP_ERROR;
+	const float* sq = sumsq_part ? (const float*)dV.p : nullptr;
+	hipError_t e = hipSuccess;
+	if (route == 0) e = launch_gram_wide_f32((const float*)dP.p, RP, len, parts, (float*)dQ.p, (float*)dG.p, nullptr);
+	else if (route == 1) e = launch_gram_wide_fused_f32((const float*)dP.p, RP, len, parts, (float*)dQ.p, (float*)dG.p, qx3 ? dX.p : nullptr, sq, sq_parts, (float*)dS.p, nullptr);
+	else if (route == 2) e = (parts >= 1 && (size_t)part_elems < mat * (size_t)parts) ? hipErrorInvalidValue
+	                       : launch_gram_reduce_x3((const float*)dQ.p, parts, RP, (float*)dG.p, qx3 ? dX.p : nullptr, sq, sq_parts, (float*)dS.p, nullptr);
+	else {
+		GramReduceArgs rg = {nullptr, 0, nullptr, nullptr, 0};
+		rg.wide_P = (const float*)dP.p; rg.wide_len = len; rg.wide_parts = settled; rg.wide_partial = (float*)dQ.p;
+		if (int st = op_factor_product_x3(A_prod, lda_prod, X, Y, F_prod, ldf_prod, r_prod, OUT_plain, ldo, 0, nullptr, false, true); st != NMFAMD_OK) return st;
+		if (int st = op_factor_product_x3(A_prod, lda_prod, X, Y, F_prod, ldf_prod, r_prod, OUT_ride, ldo, 0, nullptr, false, true, nullptr, &rg); st != NMFAMD_OK) return st;
+	}
+	if (e == hipErrorInvalidValue) return NMFAMD_INVALID_ARGUMENT;
+	if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (part_elems > 0 && hipMemcpy(partial, dQ.p, sizeof(float) * (size_t)part_elems, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (G && hipMemcpy(G, dG.p, sizeof(float) * mat, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (qx3 && hipMemcpy(qx3, dX.p, xb, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (scale_out && hipMemcpy(scale_out, dS.p, sizeof(float) * RP, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	plan[0] = settled;
+	return NMFAMD_OK;
 }
 
 // Test / measurement entry of kernels_tri.hip (padded rank 256): the passes between a factor update and the next product.

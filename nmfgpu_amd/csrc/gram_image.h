@@ -17,9 +17,11 @@
 namespace nmfamd {
 
 // One workgroup of 256 threads = one 16 x 16 tile (ti, tj), ti <= tj, of the upper triangle (blocks with ti > tj return at
-// once); the mirrored tile is written from the same values, so G is exactly symmetric.  The four waves split the K-steps;
+// once); the mirrored tile is written from the same values, so the unscaled matrix (and every slice and piece) is exactly symmetric.  The four waves split the K-steps;
 // partial tiles are added in wave order.  With rg.normalize the tile is scaled on both sides by 1 / sqrt(sum of squares of
 // the column) (1 where that is 0: kernel::normalizeColumns' `sum > 0` guard, KernelNormalizeColumns.cu:37-58).
+// (A scaled element is (v * s[c]) * s[r], two roundings: INSIDE a diagonal tile (r, c) and (c, r) are scaled one by one and may differ in the last bit, as they
+// may everywhere in spread_out and in the consumer's sum of the slices -- docs/GRAM.md, "Findings"; every consumer reads both triangles.)
 // Where the sums of squares come from:
 //   rg.colsq_part != nullptr (round 4): the update kernel that wrote the panel left one vector of 64 partial sums per workgroup
 //     (k_mu64_update32<true>); every block adds the `colsq_parts` vectors of its 32 columns in a fixed order -- fp32 sums of the

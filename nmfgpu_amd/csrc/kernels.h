@@ -93,6 +93,14 @@ constexpr int TRI_PASSENGERS = 32;                 // tri_gram_tile.h: 16 K slic
 constexpr int GRAM_IMAGE_TILES = 10;               // gram_image.h: upper triangle of the 4 x 4 grid of 16 x 16 tiles
 constexpr int GRAM_SPREAD_SLICES = 3;              // ... pieces a tile arrives in when ten tiles are dealt to sixteen workgroups (gram_image.h, spread form)
 constexpr int GRAM_KSPLIT_MAX = 8;                 // ... and the most K slices its K-split form is cut into
+// What the Gram-from-image forms can serve (launch_gram_image_args, and the same request riding in launch_factor_product_x3).  A K-split or spread launch adds
+// pieces of the K range, so no piece's diagonal is the column's sum of squares: with normalize the scales of these two forms must come from colsq_part.
+// ... and the passenger workgroups such a request takes: what launch_gram_image_args launches and what launch_factor_product_x3 appends to the product's grid
+inline int gram_image_workgroups(const GramReduceArgs& rg) { return rg.ksplit > 1 ? GRAM_IMAGE_TILES * rg.ksplit : GRAM_REDUCE_BLOCKS; }
+inline bool gram_image_args_valid(const GramReduceArgs& rg) {
+	const bool in_pieces = rg.ksplit > 1 || rg.spread > 0;
+	return rg.image != nullptr && rg.ksplit <= GRAM_KSPLIT_MAX && !(in_pieces && rg.normalize != 0 && rg.colsq_part == nullptr);
+}
 
 // X: valid output length (the plan picks the tile height; panels must be allocated for xtiles * th rows).
 // A is x-TILED: A(x, y) at A[(x/th) * tile_stride + y*th + x%th] (launch_tile / launch_tile_transposed).
@@ -226,6 +234,8 @@ bool panel_update_long_available(int RP, int len_pad);
 hipError_t launch_panel_update_long_mu(const float* P_in, float* P_out, const float* slabs, int S, long slab_stride, const void* q_split, int RP, int len_pad,
                                        float eps, float* ps, int len_valid, float* sumsq_part, hipStream_t stream, const PanelTriExtras* tri = nullptr);
 bool gram_wide_available(int RP);
+// the slice count launch_gram_wide_f32 settles on (at most `parts`)
+int gram_wide_parts(int RP, int len, int parts);
 // len: valid panel rows (the padding rows behind them are zero); partial: parts * RP * RP elements
 hipError_t launch_gram_wide_f32(const float* P, int RP, int len, int parts, float* partial, float* G, hipStream_t stream);
 // q_split (optional): 3 * 16 * (RP / 16 + 1) * (RP / 32) * 64 bytes of scratch; when given, the r x r product runs on the bf16

@@ -525,8 +525,8 @@ __global__ __launch_bounds__(256) void k_gram_image(GramReduceArgs rg) {
 
 // every field of rg as given (the K-split form included: 10 * ksplit blocks)
 hipError_t launch_gram_image_args(const GramReduceArgs& rg, hipStream_t stream) {
-	if (rg.image == nullptr || rg.ksplit > GRAM_KSPLIT_MAX || (rg.ksplit > 1 && rg.normalize != 0 && rg.colsq_part == nullptr)) return hipErrorInvalidValue;
-	hipLaunchKernelGGL(k_gram_image, dim3(rg.ksplit > 1 ? GRAM_IMAGE_TILES * rg.ksplit : GRAM_REDUCE_BLOCKS), dim3(256), 0, stream, rg);
+	if (!gram_image_args_valid(rg)) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(k_gram_image, dim3(gram_image_workgroups(rg)), dim3(256), 0, stream, rg);
 	return hipGetLastError();
 }
 
@@ -567,7 +567,9 @@ hipError_t launch_mu64_gram_partials(const float* P, int len_pad, float* partial
 }
 
 // Stand-alone Gram reduction with the same arithmetic (and summation order) as the passenger
-// workgroups of the factor-product launch.
+// workgroups of the fp32 factor-product launch (kernels.hip: 512 threads, two groups of parts).  The passengers of the split-operand
+// product (gram_reduce_block_x3, 256 threads) add FOUR groups: the same bits up to two parts and on exact data, the last bit may
+// differ beyond (docs/GRAM.md, "Findings").
 __global__ __launch_bounds__(512) void k_mu64_gram_reduce(GramReduceArgs rg) {
 	__shared__ float lds[64 + 512];
 	const int tid = threadIdx.x, blk = blockIdx.x;

@@ -566,15 +566,20 @@ __global__ __launch_bounds__(256, 2) void k_gram_wide_x3(const float* __restrict
 
 bool gram_wide_available(int RP) { return RP >= 128 && RP % 128 == 0; }
 
+int gram_wide_parts(int RP, int len, int parts) {
+	const int nb = RP / 128, nsuper = nb * (nb + 1) / 2;
+	// two workgroups per CU are enough; fewer, longer slices keep the partial traffic down
+	static const int wgs = [] { const char* e = tuning_env("NMFAMD_GRAM_WGS"); return e ? std::atoi(e) : 0; }();
+	const int target = wgs > 0 ? wgs : 512;
+	return std::max(1, std::min(std::min(parts, std::max(16, target / nsuper)), std::max(1, len / 64)));      // and at least 32 K-steps per slice
+}
+
 // len: valid panel rows (an odd len reads one zero row of the padding); partial: parts * RP * RP elements of scratch
 hipError_t launch_gram_wide_f32(const float* P, int RP, int len, int parts, float* partial, float* G, hipStream_t stream) {
 	if (!gram_wide_available(RP)) return hipErrorInvalidValue;
 	const int nb = RP / 128, nsuper = nb * (nb + 1) / 2;
-	// two workgroups per CU are enough; fewer, longer slices keep the partial traffic down
 	static const bool native = tuning_env("NMFAMD_WIDE_FP32_MFMA") != nullptr;       // A/B switch: fp32 MFMA instructions
-	static const int wgs = [] { const char* e = tuning_env("NMFAMD_GRAM_WGS"); return e ? std::atoi(e) : 0; }();
-	const int target = wgs > 0 ? wgs : 512;
-	parts = std::max(1, std::min(std::min(parts, std::max(16, target / nsuper)), std::max(1, len / 64)));      // and at least 32 K-steps per slice
+	parts = gram_wide_parts(RP, len, parts);
 	if (native) hipLaunchKernelGGL((k_gram_wide_f32<8>), dim3(parts, nsuper), dim3(256), 0, stream, P, RP, len, parts, partial);
 	else hipLaunchKernelGGL((k_gram_wide_x3<2>), dim3(parts, nsuper), dim3(256), 0, stream, P, RP, len, parts, partial);
 	hipError_t e = hipGetLastError();

@@ -525,8 +525,9 @@ static hipError_t launch_fp_x3(const FactorProductPlan& p, const float* A, long 
 	//  while the product runs -- Engine::passengers_ride)
 	const bool with_reduce = (wanted && RP == 64) || wide;
 	if (wanted && !with_reduce) return hipErrorInvalidValue;
+	if (wanted && rg->inv_a == nullptr && rg->image != nullptr && !gram_image_args_valid(*rg)) return hipErrorInvalidValue;
 	const int passengers = !with_reduce ? 0 : wide ? rg->wide_parts * ((RP / 128) * (RP / 128 + 1) / 2)
-	                                    : (rg->inv_a != nullptr ? 1 : (rg->image != nullptr && rg->ksplit > 1) ? GRAM_IMAGE_TILES * rg->ksplit : GRAM_REDUCE_BLOCKS);
+	                                    : (rg->inv_a != nullptr ? 1 : rg->image != nullptr ? gram_image_workgroups(*rg) : GRAM_REDUCE_BLOCKS);
 	if (NBW == 1 && RP != 64) return hipErrorInvalidValue;
 	// odd pieces: at least three K-steps each (x3_odd_pieces) -- the kernel's loop of whole turns is entered unconditionally
 	if (ODD && (long)p.steps_total < 3L * WAVES * p.splits) return hipErrorInvalidValue;

@@ -869,6 +869,132 @@ def op_gram(P: np.ndarray) -> np.ndarray:
     return G
 
 
+GRAM_SPREAD_SLICES, GRAM_KSPLIT_MAX, GRAM_REDUCE_BLOCKS, GRAM_IMAGE_TILES = 3, 8, 16, 10        # csrc/kernels.h
+
+
+def _ride_args(product, rows: int):
+    """(A_prod X x Y, F_prod rows x Y) in float32, Fortran order -> the trailing arguments of a riding test entry, OUT_plain, OUT_ride."""
+    if product is None:
+        return [None, C.c_long(0), 0, 0, None, C.c_long(0)], None, None
+    Ap, Fp = _f(product[0]), _f(product[1])
+    X, Y = Ap.shape
+    if Ap.dtype != np.float32 or Fp.dtype != np.float32 or Fp.shape != (rows, Y):
+        raise ValueError(f"product = (A_prod X x Y, F_prod {rows} x Y) in float32, Fortran order")
+    plain = np.full((rows, X), np.nan, dtype=np.float32, order="F")
+    ride = np.full((rows, X), np.nan, dtype=np.float32, order="F")
+    return [_p(Ap), C.c_long(_ld(Ap)), X, Y, _p(Fp), C.c_long(_ld(Fp))], plain, ride
+
+
+def split_image_bytes(ks: int, RP: int) -> int:
+    """Bytes of the split (3 x bf16) image of ks K-steps of an RP-column panel plus the all-zero step that closes it (k_pack_panel_x3)."""
+    return 3 * 16 * (ks + 1) * (RP // 32) * 64
+
+
+def op_gram_image(P: Optional[np.ndarray], *, colsq_part: Optional[np.ndarray] = None, normalize: int = 0, ksplit: int = 0, spread: int = 0, finish: bool = False,
+                  ride: int = 0, launches: int = 1, product=None, with_scale: bool = True, counter: int = 0, length: int = 16, fill=np.nan, guard_slices: int = 1):
+    """The rank-64 Gram matrix from the split image of the panel P ((len, 64) float32, C order; None: no image) by one launch, or `launches` in a row into the same
+    buffers (nmfamd_op_gram_image_f32, docs/GRAM.md).  ride 0: launch_gram_image_args; 1 / 2: as passengers of the x-tiled / y-tiled split-operand product of
+    product = (A_prod X x Y, F_prod 64 x Y) over the 16-row image; 3: of the col_split product (128 x 32 workgroups over 128-row tiles, one slab).  Every output starts as `fill` -- except the pieces of the spread form, which start as the zeros of the one clear its
+    contract asks for -- plus `guard_slices` matrices of `fill` behind the last one the form may write.  Returns a dict: `G` ((slices + guard_slices, 64, 64)),
+    `scale` (64, or None), `spread_out` ((launches, 64, 64)), `counter` (the word after each launch), `slices`, `workgroups`, `pairs`, `image_ks`, and riding `out_plain`,
+    `out_ride`, `xtiles`, `splits`."""
+    if P is not None:
+        P = np.ascontiguousarray(P, dtype=np.float32)
+        if P.ndim != 2 or P.shape[1] != 64:
+            raise ValueError("P: (len, 64) panel rows")
+        length = P.shape[0]
+    cs = None
+    if colsq_part is not None:
+        cs = np.ascontiguousarray(colsq_part, dtype=np.float32)
+        if cs.ndim != 2 or cs.shape[1] != 64:
+            raise ValueError("colsq_part: (parts, 64)")
+    slices = GRAM_SPREAD_SLICES if spread > 0 else (min(ksplit, GRAM_KSPLIT_MAX) if ksplit > 1 else 1)
+    G = np.full((slices + guard_slices, 64, 64), fill, np.float32)
+    if spread > 0:
+        G[:slices] = 0.0
+    scale = np.full(64, fill, np.float32) if with_scale else None
+    out = np.full((launches, 64, 64), fill, np.float32)
+    cnt = (C.c_uint * (1 + launches))(int(counter))
+    plan = (C.c_int * 6)()
+    prod, plain, rode = _ride_args(product if ride else None, 64)
+    st = library().nmfamd_op_gram_image_f32(_p(P), int(length), _p(cs), 0 if cs is None else int(cs.shape[0]), int(normalize), int(ksplit), int(spread), int(bool(finish)),
+                                            int(ride), int(launches), _p(G), C.c_long(G.size), _p(scale), _p(out), cnt, plan, *prod, _p(plain), _p(rode), C.c_long(64))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_gram_image_f32")
+    return {"G": G, "scale": scale, "spread_out": out, "counter": [int(cnt[1 + i]) for i in range(launches)], "slices": plan[0], "workgroups": plan[1], "pairs": plan[2],
+            "image_ks": plan[3], "xtiles": plan[4], "splits": plan[5], "out_plain": plain, "out_ride": rode}
+
+
+def op_gram64_partials(route: int, *, P: Optional[np.ndarray] = None, partials: Optional[np.ndarray] = None, normalize: int = 0, sumsq_part: Optional[np.ndarray] = None,
+                       with_scale: bool = True, x3_ks: Optional[int] = None, product=None, fill=np.nan):
+    """The rank-64 Gram matrix from partial 64 x 64 matrices, one launcher per route (nmfamd_op_gram64_partials_f32, docs/GRAM.md): 0 launch_mu64_gram_partials of the
+    panel P ((len_pad, 64), len_pad a multiple of 64); 1 launch_mu64_gram_reduce; 2 its riding twin on the split-operand product of product = (A_prod, F_prod 64 x Y),
+    6 the same on the col_split product launch;
+    3 launch_gram64_from_partials; 4 launch_gram64_normalize_all; 5 launch_gram64_reduce_scale_all.  partials: (parts, 64, 64).  Outputs start as `fill`.
+    Returns a dict: `partials`, `G`, `Graw`, `scale`, `P` (the panel after the launch), `x3` (the image's bytes as uint16: bf16 bit patterns), `out_plain`, `out_ride`."""
+    len_pad, parts = 0, 0
+    if P is not None:
+        P = np.array(P, dtype=np.float32, order="C")
+        if P.ndim != 2 or P.shape[1] != 64:
+            raise ValueError("P: (len_pad, 64)")
+        len_pad = P.shape[0]
+    if route == 0:
+        parts = len_pad // 64
+        partials = np.full((max(parts, 1), 64, 64), fill, np.float32)
+    else:
+        partials = np.ascontiguousarray(partials, dtype=np.float32)
+        if partials.ndim != 3 or partials.shape[1:] != (64, 64):
+            raise ValueError("partials: (parts, 64, 64)")
+        parts = partials.shape[0]
+    sq = None if sumsq_part is None else np.ascontiguousarray(sumsq_part, dtype=np.float32)
+    if sq is not None and (sq.ndim != 2 or sq.shape[1] != 64):
+        raise ValueError("sumsq_part: (sq_parts, 64)")
+    G = None if route == 0 else np.full((64, 64), fill, np.float32)
+    Graw = np.full((64, 64), fill, np.float32) if route == 4 else None
+    scale = np.full(64, fill, np.float32) if (route in (4, 5) or (route != 0 and with_scale)) else None
+    x3 = np.full(split_image_bytes(len_pad // 16, 64) // 2, 0x7FC0, np.uint16) if route in (4, 5) else None          # (bf16 NaN)
+    ks = len_pad // 16 if x3_ks is None else int(x3_ks)
+    prod, plain, rode = _ride_args(product if route in (2, 6) else None, 64)
+    st = library().nmfamd_op_gram64_partials_f32(int(route), _p(P), int(len_pad), _p(partials), int(parts), int(normalize), _p(sq), 0 if sq is None else int(sq.shape[0]),
+                                                 _p(Graw), _p(G), _p(scale), _p(x3), ks, *prod, _p(plain), _p(rode), C.c_long(64))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_gram64_partials_f32")
+    return {"partials": partials, "G": G, "Graw": Graw, "scale": scale, "P": P, "x3": x3, "out_plain": plain, "out_ride": rode}
+
+
+def op_gram_wide(route: int, RP: int, *, P: Optional[np.ndarray] = None, parts: int = 16, partial: Optional[np.ndarray] = None, slices_alloc: Optional[int] = None,
+                 sumsq_part: Optional[np.ndarray] = None, with_qx3: bool = True, product=None, fill=np.nan):
+    """The fp32 Gram matrix at padded ranks 128 ... 512, one launcher per route (nmfamd_op_gram_wide_f32, docs/GRAM.md): 0 launch_gram_wide_f32; 1
+    launch_gram_wide_fused_f32; 2 launch_gram_reduce_x3 alone on the caller's `partial` ((slices, RP, RP), `parts` of them read); 3 the slices as passengers of the
+    split-operand product of product = (A_prod X x Y, F_prod r_prod x Y).  P: (len, RP) float32.  The slice buffer starts as `fill` with room for slices_alloc
+    matrices (default: parts + 1, so one matrix behind the last slice shows what is left alone).  Returns a dict: `partial`, `G`, `qx3` (uint16 bf16 bit patterns),
+    `scale` (RP values, or None without sumsq_part), `parts` (the slice count the launcher settled on), `out_plain`, `out_ride`."""
+    length = 0
+    if P is not None:
+        P = np.ascontiguousarray(P, dtype=np.float32)
+        if P.ndim != 2 or P.shape[1] != RP:
+            raise ValueError("P: (len, RP)")
+        length = P.shape[0]
+    if partial is None:
+        partial = np.full((max(parts, 0) + 1 if slices_alloc is None else slices_alloc, RP, RP), fill, np.float32)
+    else:
+        partial = np.array(partial, dtype=np.float32, order="C")
+    sq = None if sumsq_part is None else np.ascontiguousarray(sumsq_part, dtype=np.float32)
+    if sq is not None and (sq.ndim != 2 or sq.shape[1] != RP):
+        raise ValueError("sumsq_part: (sq_parts, RP)")
+    G = None if route == 3 else np.full((RP, RP), fill, np.float32)
+    qx3 = np.full(split_image_bytes(RP // 16, RP) // 2, 0x7FC0, np.uint16) if (with_qx3 and route in (1, 2)) else None
+    scale = np.full(RP, fill, np.float32) if sq is not None else None
+    plan = (C.c_int * 1)()
+    r_prod = product[1].shape[0] if (route == 3 and product is not None) else 0
+    prod, plain, rode = _ride_args(product if route == 3 else None, r_prod)
+    st = library().nmfamd_op_gram_wide_f32(int(route), _p(P), int(RP), int(length), int(parts), _p(partial), C.c_long(partial.size), _p(G), _p(qx3), _p(sq),
+                                           0 if sq is None else int(sq.shape[0]), _p(scale), plan, *prod, int(r_prod), _p(plain), _p(rode), C.c_long(max(r_prod, 1)))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_gram_wide_f32")
+    return {"partial": partial, "G": G, "qx3": qx3, "scale": scale, "parts": plan[0], "out_plain": plain, "out_ride": rode}
+
+
 def inverse_padded_rank(r: int, dtype) -> int:
     """The padded rank RP of the r x r inverse's output (csrc/engine.h, padded_rank)."""
     return 64 if r <= 64 else (-(-r // 64) * 64 if np.dtype(dtype) == np.float64 else -(-r // 128) * 128)

@@ -63,6 +63,20 @@ def test_inverse_test_entries_are_exported():
         assert name in _declared_c_symbols("nmfgpu_amd.h") and hasattr(lib, name), name
 
 
+def test_gram_test_entries_are_exported():
+    lib = na.library()
+    for name in ("nmfamd_op_gram_image_f32", "nmfamd_op_gram64_partials_f32", "nmfamd_op_gram_wide_f32"):
+        assert name in _declared_c_symbols("nmfgpu_amd.h") and hasattr(lib, name), name
+    from nmfgpu_amd import engine
+    from tests import gram_reference as gr
+    assert (engine.GRAM_SPREAD_SLICES, engine.GRAM_KSPLIT_MAX, engine.GRAM_REDUCE_BLOCKS, engine.GRAM_IMAGE_TILES) == \
+        (gr.SPREAD_SLICES, gr.KSPLIT_MAX, gr.REDUCE_BLOCKS, gr.IMAGE_TILES)
+    # ... and these are the constants of csrc/kernels.h
+    text = open(os.path.join(os.path.dirname(engine.__file__), "csrc", "kernels.h")).read()
+    for cname, value in (("GRAM_SPREAD_SLICES", 3), ("GRAM_KSPLIT_MAX", 8), ("GRAM_REDUCE_BLOCKS", 16), ("GRAM_IMAGE_TILES", 10)):
+        assert re.search(rf"constexpr int {cname} = {value};", text), cname
+
+
 def test_struct_layout_matches_reference_table():
     # SURVEY.md section 8b, measured on the reference header with offsetof
     assert C.sizeof(na.MatrixDescription) == 44

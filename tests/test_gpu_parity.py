@@ -106,7 +106,9 @@ def test_factor_product_fp64_identity_layout_check():
     assert np.array_equal(out, want)
 
 
-@pytest.mark.parametrize("r,length", [(8, 500), (64, 1000), (100, 333), (128, 777), (200, 1001), (256, 5000), (300, 640), (500, 333)])
+# (the short panels: one K-step, one slice; tests/test_gpu_gram_*.py hold every route and form element by element, docs/GRAM.md)
+@pytest.mark.parametrize("r,length", [(8, 500), (64, 1000), (100, 333), (128, 777), (200, 1001), (256, 5000), (300, 640), (500, 333),
+                                      (64, 3), (64, 17), (128, 1), (128, 65), (256, 129)])
 def test_gram(r, length):
     rng = np.random.default_rng(r)
     P = F(rng.random((r, length)).astype(np.float32))
