@@ -244,6 +244,29 @@ NMFAMD_API int nmfamd_engine_get_factors_device(nmfamd_engine* e, void* W, long 
  * kind = 1; an allocator that carves tensors out of larger blocks reports the block's end).  NMFAMD_NO_DEVICE without a HIP device. */
 NMFAMD_API int nmfamd_device_pointer_info(const void* p, int* kind, int* device, unsigned long long* bytes_from_p);
 
+/* ---- predict and score entries of W H (docs/PREDICT.md) ----------------------------------------
+ * rows / cols: nnz >= 1 coordinates (i_p, j_p), 32-bit, index base 0 or 1, unsorted, duplicates counted once per copy.  W and H are what
+ * nmfamd_engine_get_factors would return at this moment (nsNMF: W S; pending scales folded in), and the effects on the engine are exactly that call's: the factors
+ * after iterate, predict, iterate equal those after iterate, get_factors, iterate bit for bit, and the error of the last error iteration stays as it was.
+ *   predict: out[p] = sum_{k < r} W(i_p, k) H(k, j_p) in the engine's precision, no eps.
+ *   score:   values v_p in the engine's precision; out may be NULL.  sums[0] = sum (v_p - out[p])^2, sums[1] = sum d_beta(v_p | out[p] + eps) (eps the machine
+ *            epsilon of the precision; v^beta = 0 at v = 0; the KL form at beta = 1, Itakura-Saito at beta = 0, the general form elsewhere, beta = 2 included),
+ *            sums[2] = the sum of the absolute values of the summands of d_beta (the scale of sums[1]'s rounding), sums[3] = sqrt(sums[0] / nnz).  beta <= 0 needs
+ *            every value finite and > 0, beta > 0 finite and >= 0; beta = NaN: no divergence wanted -- any finite value, sums[1] = sums[2] = NaN.
+ * Per-entry terms are formed in the engine's precision and added in double in a fixed order (16-lane group, workgroup, host): a repeated call is bit-identical,
+ * and the host and the device form give the same bits.
+ * NMFAMD_INVALID_ARGUMENT with nmfamd_engine_last_error, before any result is written: a coordinate outside [base, base + m) x [base, base + n) (the text names the
+ * first such p; host arrays are checked on the host before any device work, device arrays by a validation launch that reads the index arrays only -- the gather is
+ * not launched unless it found every coordinate inside), a value that breaks the rule, an engine created with row blocks > 1 or driven through the three-phase /
+ * sharded entries (it holds a column shard), an engine whose factors were never set, nnz < 1, another base.
+ * _device: every array in device memory, with the pointer check and the ordering of the entries above (sums stays a host array). */
+NMFAMD_API int nmfamd_engine_predict(nmfamd_engine* e, const int* rows, const int* cols, long nnz, int base, void* out);
+NMFAMD_API int nmfamd_engine_score(nmfamd_engine* e, const int* rows, const int* cols, const void* values, long nnz, int base, double beta, void* out_or_NULL,
+                                   double sums[4]);
+NMFAMD_API int nmfamd_engine_predict_device(nmfamd_engine* e, const int* rows, const int* cols, long nnz, int base, void* out);
+NMFAMD_API int nmfamd_engine_score_device(nmfamd_engine* e, const int* rows, const int* cols, const void* values, long nnz, int base, double beta, void* out_or_NULL,
+                                          double sums[4]);
+
 /* Uniform (0,1] fill, the same seed for both factors (source/init/RandomValueStrategy.cpp:29-70). */
 NMFAMD_API int nmfamd_engine_randomize(nmfamd_engine* e, unsigned seed, int w, int h);
 
@@ -715,6 +738,16 @@ NMFAMD_API int nmfamd_op_masked_beta_half_step_f32(const int* ptr, const int* id
 NMFAMD_API int nmfamd_op_masked_beta_half_step_f64(const int* ptr, const int* idx, const double* val, long nnz, double* A, long a_rows, const double* B, long b_rows, int RP,
                                                    int rows, int divergence, double beta, double l1, double l2, int update, double* t_frob, double* t_div,
                                                    double* sumsq_part, int sumsq_parts);
+/* predict_entries: one launch of the gather of kernels_predict.hip (docs/PREDICT.md) on caller-built padded panels Wt [w_rows][RP] and H [h_rows][RP] (fp32: RP 64,
+ * 128, 256, 384, 512; fp64: 64 ... 512 in steps of 64), r in 1 ... RP the coordinates that count.  rows / cols: nnz >= 1 coordinates of index base 0 or 1, each
+ * inside the panels (checked here, on the host: NMFAMD_INVALID_ARGUMENT).  vals (or NULL) and beta as nmfamd_engine_score, without its value rule.  out (or NULL
+ * with vals; out_len >= nnz values) and part (with vals: parts = nmfamd_predict_entry_parts(nnz) triples of doubles -- a workgroup's sums of the squared errors, of
+ * d_beta and of its absolute summands, to be added in index order) are uploaded as the caller filled them, so what the launch does not write comes back unchanged. */
+NMFAMD_API int nmfamd_predict_entry_parts(long nnz);
+NMFAMD_API int nmfamd_op_predict_entries_f32(const int* rows, const int* cols, const float* vals, long nnz, int base, const float* Wt, long w_rows, const float* H,
+                                             long h_rows, int RP, int r, double beta, float* out, long out_len, double* part, int parts);
+NMFAMD_API int nmfamd_op_predict_entries_f64(const int* rows, const int* cols, const double* vals, long nnz, int base, const double* Wt, long w_rows, const double* H,
+                                             long h_rows, int RP, int r, double beta, double* out, long out_len, double* part, int parts);
 /* kl_update: P(y, c) <- (P(y, c) * scale(c)) * (sum over the parts of num) / (den(c) + eps) on P [len_pad][RP] (scale NULL: ones); num holds `parts` panels
  * part_stride values apart (a multiple of 4, >= len_pad * RP when parts > 1; what lies between two panels is not read).  sumsq_part / sum_part (each optional,
  * [len_pad / 128][RP]): per 128 rows the sums of squares / the sums of the new values.  len_pad a multiple of 128. */

@@ -382,6 +382,30 @@ int nmfamd_engine_get_factors_device(nmfamd_engine* e, void* W, long ldw, int la
 	                   [&](Engine<double>& g) { return g.get_factors_device((double*)W, ldw, layout_w, (double*)H, ldh, layout_h); });
 }
 
+int nmfamd_engine_predict(nmfamd_engine* e, const int* rows, const int* cols, long nnz, int base, void* out) {
+	if (!out) return NMFAMD_INVALID_ARGUMENT;
+	return dispatch(e, [&](Engine<float>& g) { return g.predict_entries(rows, cols, nullptr, nnz, base, 0.0, (float*)out, nullptr, false); },
+	                   [&](Engine<double>& g) { return g.predict_entries(rows, cols, nullptr, nnz, base, 0.0, (double*)out, nullptr, false); });
+}
+
+int nmfamd_engine_score(nmfamd_engine* e, const int* rows, const int* cols, const void* values, long nnz, int base, double beta, void* out, double sums[4]) {
+	if (!values || !sums) return NMFAMD_INVALID_ARGUMENT;
+	return dispatch(e, [&](Engine<float>& g) { return g.predict_entries(rows, cols, (const float*)values, nnz, base, beta, (float*)out, sums, false); },
+	                   [&](Engine<double>& g) { return g.predict_entries(rows, cols, (const double*)values, nnz, base, beta, (double*)out, sums, false); });
+}
+
+int nmfamd_engine_predict_device(nmfamd_engine* e, const int* rows, const int* cols, long nnz, int base, void* out) {
+	if (!out) return NMFAMD_INVALID_ARGUMENT;
+	return dispatch(e, [&](Engine<float>& g) { return g.predict_entries(rows, cols, nullptr, nnz, base, 0.0, (float*)out, nullptr, true); },
+	                   [&](Engine<double>& g) { return g.predict_entries(rows, cols, nullptr, nnz, base, 0.0, (double*)out, nullptr, true); });
+}
+
+int nmfamd_engine_score_device(nmfamd_engine* e, const int* rows, const int* cols, const void* values, long nnz, int base, double beta, void* out, double sums[4]) {
+	if (!values || !sums) return NMFAMD_INVALID_ARGUMENT;
+	return dispatch(e, [&](Engine<float>& g) { return g.predict_entries(rows, cols, (const float*)values, nnz, base, beta, (float*)out, sums, true); },
+	                   [&](Engine<double>& g) { return g.predict_entries(rows, cols, (const double*)values, nnz, base, beta, (double*)out, sums, true); });
+}
+
 int nmfamd_device_pointer_info(const void* p, int* kind, int* device, unsigned long long* bytes_from_p) {
 	if (!kind || !device || !bytes_from_p) return NMFAMD_INVALID_ARGUMENT;
 	if (nmfamd_device_count() <= 0) { *kind = 0; *device = -1; *bytes_from_p = 0; return NMFAMD_NO_DEVICE; }
@@ -1520,6 +1544,33 @@ int op_masked_beta_half_step(const int* ptr, const int* idx, const T* val, long 
 	return NMFAMD_OK;
 }
 
+// One launch of the gather of kernels_predict.hip on caller-built padded panels (docs/PREDICT.md).  Every coordinate is checked here, on the host: the kernel
+// checks none.  out and part are uploaded as the caller filled them.
+template <typename T>
+int op_predict_entries(const int* rows, const int* cols, const T* vals, long nnz, int base, const T* Wt, long w_rows, const T* H, long h_rows, int RP, int r, double beta,
+                       T* out, long out_len, double* part, int parts) {
+	if (!rows || !cols || !Wt || !H || nnz < 1 || nnz > PREDICT_MAX_ENTRIES || (base != 0 && base != 1) || w_rows < 1 || h_rows < 1 ||
+	    !predict_rank_instantiated(RP, sizeof(T)) || r < 1 || r > RP || (!vals && !out) || (out && out_len < nnz) || (vals != nullptr) != (part != nullptr) ||
+	    (part && parts != predict_entry_parts(nnz)) || (vals && std::isinf((double)(T)beta)))
+		return NMFAMD_INVALID_ARGUMENT;
+	for (long p = 0; p < nnz; ++p) {
+		const long i = (long)rows[p] - base, j = (long)cols[p] - base;
+		if (i < 0 || i >= w_rows || j < 0 || j >= h_rows) return NMFAMD_INVALID_ARGUMENT;
+	}
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	DevBuf dR, dC, dV, dW, dH, dO, dP;
+	if (upload(dR, rows, (size_t)nnz) != hipSuccess || upload(dC, cols, (size_t)nnz) != hipSuccess || (vals && upload(dV, vals, (size_t)nnz) != hipSuccess) ||
+	    upload(dW, Wt, (size_t)w_rows * RP) != hipSuccess || upload(dH, H, (size_t)h_rows * RP) != hipSuccess || (out && upload(dO, out, (size_t)out_len) != hipSuccess) ||
+	    (part && upload(dP, part, (size_t)parts * 3) != hipSuccess))
+		return NMFAMD_NO_DEVICE_MEMORY;
+	const int st = op_status(launch_predict_entries<T>((const int*)dR.p, (const int*)dC.p, (const T*)dV.p, nnz, base, (const T*)dW.p, (const T*)dH.p, RP, r,
+	                                                   std::numeric_limits<T>::epsilon(), beta, (T*)dO.p, (double*)dP.p, nullptr));
+	if (st != NMFAMD_OK) return st;
+	if (out && hipMemcpy(out, dO.p, sizeof(T) * (size_t)out_len, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (part && hipMemcpy(part, dP.p, sizeof(double) * (size_t)parts * 3, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
+
 template <typename T>
 int op_kl_update(T* P, const T* num, int parts, long part_stride, const T* den, const T* scale, int RP, int len_pad, T* sumsq_part, T* sum_part) {
 	// num: `parts` panels of len_pad * RP values, part_stride values apart (what lies between them is uploaded too, and must not be read)
@@ -1756,6 +1807,18 @@ int nmfamd_op_hals_normalize_f64(double* Wt, int RP, int mpad, double* H, int np
 }
 
 int nmfamd_masked_norm_parts(int rows) { return rows > 0 ? masked_norm_parts(rows) : 0; }
+
+int nmfamd_predict_entry_parts(long nnz) { return nnz > 0 ? predict_entry_parts(nnz) : 0; }
+
+int nmfamd_op_predict_entries_f32(const int* rows, const int* cols, const float* vals, long nnz, int base, const float* Wt, long w_rows, const float* H, long h_rows, int RP,
+                                  int r, double beta, float* out, long out_len, double* part, int parts) {
+	return op_predict_entries<float>(rows, cols, vals, nnz, base, Wt, w_rows, H, h_rows, RP, r, beta, out, out_len, part, parts);
+}
+
+int nmfamd_op_predict_entries_f64(const int* rows, const int* cols, const double* vals, long nnz, int base, const double* Wt, long w_rows, const double* H, long h_rows, int RP,
+                                  int r, double beta, double* out, long out_len, double* part, int parts) {
+	return op_predict_entries<double>(rows, cols, vals, nnz, base, Wt, w_rows, H, h_rows, RP, r, beta, out, out_len, part, parts);
+}
 
 int nmfamd_op_masked_beta_half_step_f32(const int* ptr, const int* idx, const float* val, long nnz, float* A, long a_rows, const float* B, long b_rows, int RP, int rows,
                                         int divergence, double beta, double l1, double l2, int update, float* t_frob, float* t_div, float* sumsq_part, int sumsq_parts) {

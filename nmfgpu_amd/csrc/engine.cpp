@@ -828,8 +828,8 @@ Status Engine<T>::set_factors_device(const T* W, long ldw, int layout_w, const T
 	if (H) { if (Status st = check_device_matrix("H", H, ldh, layout_h, r_, n_)) return st; }
 	state_.factors_touched();
 	HIPX(hipDeviceSynchronize());
-	if (W) { state_.w_set(); HIPX(launch_import_panel<T>(W, ldw, layout_w, true, r_, m_, Wt_, RP_, mpad_, stream_)); }
-	if (H) { state_.h_set(); HIPX(launch_import_panel<T>(H, ldh, layout_h, false, r_, n_, H_, RP_, npad_, stream_)); }
+	if (W) { state_.w_set(); have_w_ = true; HIPX(launch_import_panel<T>(W, ldw, layout_w, true, r_, m_, Wt_, RP_, mpad_, stream_)); }
+	if (H) { state_.h_set(); have_h_ = true; HIPX(launch_import_panel<T>(H, ldh, layout_h, false, r_, n_, H_, RP_, npad_, stream_)); }
 	HIPX(hipStreamSynchronize(stream_));
 	return ST_OK;
 }
@@ -1165,7 +1165,7 @@ Status Engine<T>::set_factors(const T* W, long ldw, const T* H, long ldh) {
 	state_.factors_touched();
 	if (W) {
 		if (ldw < m_) return ST_INVALID;
-		state_.w_set();
+		state_.w_set(); have_w_ = true;
 		// host m x r (column-major) -> staging m x r (ld mpad) -> Wt panel (element (c, i) at [i * RP + c])
 		HIPX(hipMemcpy2DAsync(stage_, mpad_ * sizeof(T), W, ldw * sizeof(T), m_ * sizeof(T), r_, hipMemcpyHostToDevice, stream_));
 		HIPX(hipMemsetAsync(Wt_, 0, sizeof(T) * (size_t)RP_ * mpad_, stream_));
@@ -1173,7 +1173,7 @@ Status Engine<T>::set_factors(const T* W, long ldw, const T* H, long ldh) {
 	}
 	if (H) {
 		if (ldh < r_) return ST_INVALID;
-		state_.h_set();
+		state_.h_set(); have_h_ = true;
 		HIPX(hipMemsetAsync(H_, 0, sizeof(T) * (size_t)RP_ * npad_, stream_));
 		HIPX(hipMemcpy2DAsync(H_, RP_ * sizeof(T), H, ldh * sizeof(T), r_ * sizeof(T), n_, hipMemcpyHostToDevice, stream_));
 	}
@@ -1208,12 +1208,111 @@ Status Engine<T>::get_factors(T* W, long ldw, T* H, long ldh) {
 	return ST_OK;
 }
 
+// Predict and score entries of W H (docs/PREDICT.md; kernels_predict.hip).  One body for host and device arrays: the refusals that need no array, the pointer checks
+// (device) or the host check of every coordinate and value (host: before any device work), the staging of host arrays, the validation launch (device: no gather
+// runs unless it found every coordinate inside), export_panel_w -- get_factors' effects -- and the gather; the per-workgroup sums land in pinned memory and are
+// added in workgroup order.
+template <typename T>
+Status Engine<T>::predict_entries(const int* rows, const int* cols, const T* values, long nnz, int base, double beta, T* out, double* sums, bool device) {
+	if (row_blocks_ > 1) return refuse("predict: an engine with row blocks holds a column shard of a sharded run (its export is a collective); predict on a single engine");
+	if (column_shard_ || w_gather_hook_) return refuse("predict: the engine is bound to a sharded run and holds a column shard; predict on a single engine");
+	if (!have_w_ || !have_h_) return refuse("predict: the engine has no factors yet (set_factors or randomize first)");
+	if (nnz < 1 || nnz > PREDICT_MAX_ENTRIES) return refuse("predict: nnz has to be 1 ... 2^31 - 1 entries");
+	if (base != 0 && base != 1) return refuse("predict: the index base has to be 0 or 1");
+	if (rows == nullptr || cols == nullptr) return refuse("predict: null coordinate array");
+	if (values == nullptr && out == nullptr) return refuse("predict: nothing to compute (neither values nor an output array)");
+	if (values != nullptr && sums == nullptr) return refuse("score: null sums");
+	if (!predict_rank_instantiated(RP_, sizeof(T))) return refuse("predict: no kernel for padded rank " + std::to_string(RP_));
+	// the value rule of the masked beta engines, in the precision of T: 0 none, 1 finite and >= 0, 2 finite, 3 finite and > 0
+	const double b = (double)(T)beta;
+	if (values != nullptr && std::isinf(b)) return refuse("score: beta has to be finite (NaN: no divergence), within the range of the engine's precision");
+	const int rule = values == nullptr ? 0 : b != b ? 2 : b <= 0 ? 3 : 1;
+	auto bad_coordinate = [&](unsigned long p) {
+		return refuse("predict: entry " + std::to_string(p) + " has a coordinate outside the matrix ([base, base + m) x [base, base + n))" +
+		              (device ? "; found by the validation launch, the gather was not launched" : "; found on the host, before any device work"));
+	};
+	auto bad_value = [&](unsigned long p) {
+		return refuse("score: value " + std::to_string(p) + (rule == 2 ? " is not finite" : rule == 3 ? " breaks the rule of beta <= 0: every value finite and > 0" : " breaks the rule of beta > 0: every value finite and >= 0"));
+	};
+	const int* d_rows = rows; const int* d_cols = cols; const T* d_vals = values; T* d_out = out;
+	if (device) {
+		if (Status st = check_device_vector("rows", rows, sizeof(int), nnz)) return st;
+		if (Status st = check_device_vector("cols", cols, sizeof(int), nnz)) return st;
+		if (values) { if (Status st = check_device_vector("values", values, sizeof(T), nnz)) return st; }
+		if (out) { if (Status st = check_device_vector("out", out, sizeof(T), nnz)) return st; }
+		HIPX(hipDeviceSynchronize());      // whatever stream produced the arrays has finished
+	} else {
+		for (long p = 0; p < nnz; ++p) {
+			const long i = (long)rows[p] - base, j = (long)cols[p] - base;
+			if (i < 0 || i >= m_ || j < 0 || j >= n_) return bad_coordinate((unsigned long)p);
+		}
+		for (long p = 0; rule != 0 && p < nnz; ++p) {
+			const T v = values[p];
+			if (!std::isfinite(v) || (rule == 1 && v < T(0)) || (rule == 3 && !(v > T(0)))) return bad_value((unsigned long)p);
+		}
+	}
+	// the engine's own buffers
+	if (pe_part_ == nullptr) {
+		HIPX(buffers_.device(&pe_part_, sizeof(double) * 3 * PREDICT_MAX_PARTS, false, stream_));
+		HIPX(buffers_.device(&pe_flags_, sizeof(unsigned) * 2, false, stream_));
+		HIPX(buffers_.pinned(&pe_pin_, sizeof(double) * (3 * PREDICT_MAX_PARTS + 1)));
+	}
+	if (!device) {
+		if (nnz > pe_cap_) {
+			buffers_.release(pe_rows_, pe_cols_, pe_vals_, pe_out_);
+			pe_cap_ = 0;
+			const long cap = std::max(nnz, 1024l);
+			HIPX(buffers_.device(&pe_rows_, sizeof(int) * (size_t)cap, false, stream_));
+			HIPX(buffers_.device(&pe_cols_, sizeof(int) * (size_t)cap, false, stream_));
+			HIPX(buffers_.device(&pe_vals_, sizeof(T) * (size_t)cap, false, stream_));
+			HIPX(buffers_.device(&pe_out_, sizeof(T) * (size_t)cap, false, stream_));
+			pe_cap_ = cap;
+		}
+		if (out != nullptr && nnz > pe_pin_cap_) {
+			buffers_.release(pe_pin_out_);
+			pe_pin_cap_ = 0;
+			const long cap = std::max(nnz, 1024l);
+			HIPX(buffers_.pinned(&pe_pin_out_, sizeof(T) * (size_t)cap));
+			pe_pin_cap_ = cap;
+		}
+		HIPX(hipMemcpyAsync(pe_rows_, rows, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, stream_));
+		HIPX(hipMemcpyAsync(pe_cols_, cols, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, stream_));
+		if (values) HIPX(hipMemcpyAsync(pe_vals_, values, sizeof(T) * (size_t)nnz, hipMemcpyHostToDevice, stream_));
+		d_rows = pe_rows_; d_cols = pe_cols_; d_vals = values ? pe_vals_ : nullptr; d_out = out ? pe_out_ : nullptr;
+	} else {
+		// no index of a device array has been looked at yet: the validation launch reads the index arrays (and the values) only, inside the extents checked above
+		unsigned* flags = reinterpret_cast<unsigned*>(pe_pin_ + 3 * PREDICT_MAX_PARTS);
+		HIPX(hipMemsetAsync(pe_flags_, 0xff, sizeof(unsigned) * 2, stream_));
+		HIPX(launch_predict_validate<T>(d_rows, d_cols, d_vals, nnz, base, m_, n_, rule, pe_flags_, stream_));
+		HIPX(hipMemcpyAsync(flags, pe_flags_, sizeof(unsigned) * 2, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipStreamSynchronize(stream_));
+		if (flags[0] != 0xffffffffu) return bad_coordinate(flags[0]);      // (no gather was launched)
+		if (flags[1] != 0xffffffffu) return bad_value(flags[1]);
+	}
+	const T* src = nullptr;
+	if (Status s = export_panel_w(true, &src)) return s;
+	const int parts = predict_entry_parts(nnz);
+	HIPX(launch_predict_entries<T>(d_rows, d_cols, d_vals, nnz, base, src, H_, RP_, r_, std::numeric_limits<T>::epsilon(), beta, d_out, pe_part_, stream_));
+	if (d_vals) HIPX(hipMemcpyAsync(pe_pin_, pe_part_, sizeof(double) * 3 * (size_t)parts, hipMemcpyDeviceToHost, stream_));
+	if (!device && out) HIPX(hipMemcpyAsync(pe_pin_out_, pe_out_, sizeof(T) * (size_t)nnz, hipMemcpyDeviceToHost, stream_));
+	HIPX(hipStreamSynchronize(stream_));
+	if (!device && out) std::memcpy(out, pe_pin_out_, sizeof(T) * (size_t)nnz);
+	if (d_vals) {
+		double s[3] = {0, 0, 0};
+		for (int w = 0; w < parts; ++w)      // in workgroup order
+			for (int k = 0; k < 3; ++k) s[k] += pe_pin_[3 * w + k];
+		const double nan = std::numeric_limits<double>::quiet_NaN();
+		sums[0] = s[0]; sums[1] = b != b ? nan : s[1]; sums[2] = b != b ? nan : s[2]; sums[3] = std::sqrt(s[0] / (double)nnz);
+	}
+	return ST_OK;
+}
+
 template <typename T>
 Status Engine<T>::randomize_factors(unsigned seed, bool w, bool h, long h_first_column) {
 	// The reference seeds W's and H's generators identically (RandomValueStrategy.cpp:53-69).
 	state_.factors_touched();
-	if (w) { state_.w_set(); HIPX(launch_fill_uniform<T>(Wt_, RP_, r_, m_, mpad_, seed, stream_)); }
-	if (h) { state_.h_set(); HIPX(launch_fill_uniform<T>(H_, RP_, r_, n_, npad_, seed, stream_, h_first_column)); }
+	if (w) { state_.w_set(); have_w_ = true; HIPX(launch_fill_uniform<T>(Wt_, RP_, r_, m_, mpad_, seed, stream_)); }
+	if (h) { state_.h_set(); have_h_ = true; HIPX(launch_fill_uniform<T>(H_, RP_, r_, n_, npad_, seed, stream_, h_first_column)); }
 	return ST_OK;
 }
 
@@ -1598,6 +1697,7 @@ void Engine<T>::resolve_error(const std::vector<T>& vtv_sorted, std::vector<T> h
 
 template <typename T>
 Status Engine<T>::h_step(bool compute_error) {
+	column_shard_ = true;
 	// first call of an iteration in the sharded form: decides whether this iteration's products are timed
 	timing_now_ = timing_ && (timing_iter_++ % timing_stride_ == 0);
 	if (prm_.is_masked()) return masked_refuses("h_step");
@@ -1721,6 +1821,7 @@ Status Engine<T>::h_step_impl(bool compute_error) {
 
 template <typename T>
 Status Engine<T>::w_products(T* exchange) {
+	column_shard_ = true;
 	if (prm_.is_masked()) return masked_refuses("w_products");
 	if (beta_dense_) return beta_refuses("w_products");
 	if (prm_.divergence != 0) return kl_w_products(exchange, kl_err_iter_);      // (sparse Frobenius compute shards through the code below: its two products are SpMMs over the shard's images)
@@ -1769,6 +1870,7 @@ Status Engine<T>::w_products(T* exchange) {
 
 template <typename T>
 Status Engine<T>::w_finish(const T* exchange, bool compute_error) {
+	column_shard_ = true;
 	if (prm_.is_masked()) return masked_refuses("w_finish");
 	if (beta_dense_) return beta_refuses("w_finish");
 	if (prm_.divergence != 0) return kl_w_finish(exchange, compute_error);
@@ -1846,6 +1948,7 @@ Status Engine<T>::w_finish(const T* exchange, bool compute_error) {
 // (one small launch; nothing to do for a team of one).  Rank-64 multiplicative update on the split-operand path only (direct_w_finish()).
 template <typename T>
 Status Engine<T>::w_finish_peers(const T* const* exchanges, int count, bool compute_error) {
+	column_shard_ = true;
 	if (prm_.is_masked()) return masked_refuses("w_finish_peers");
 	if (beta_dense_) return beta_refuses("w_finish_peers");
 	if (!direct_w_finish() || count < 1 || count > PEER_SLABS_MAX || exchanges == nullptr) return ST_INVALID;
@@ -1867,6 +1970,7 @@ Status Engine<T>::w_finish_peers(const T* const* exchanges, int count, bool comp
 // ---- row-block form of the W step (one block per rank, see engine.h) -----------------------------------------------
 template <typename T>
 Status Engine<T>::w_update_rows(const T* num_rows, const T* hht, long row0, long rows, bool compute_error, T* colsq) {
+	column_shard_ = true;
 	if (prm_.is_masked()) return masked_refuses("w_update_rows");
 	if (beta_dense_) return beta_refuses("w_update_rows");
 	if (alg_ != ALG_MU && alg_ != ALG_NSNMF) return ST_INVALID;

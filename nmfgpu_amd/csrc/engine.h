@@ -268,6 +268,17 @@ public:
 	Status get_factors_device(T* W, long ldw, int layout_w, T* H, long ldh, int layout_h);
 	// h_first_column: global index of this engine's first column (column shards draw their part of ONE stream)
 	Status randomize_factors(unsigned seed, bool w, bool h, long h_first_column = 0);
+	// Predict and score entries of W H (docs/PREDICT.md), W and H being what get_factors would return now: out[p] = sum_k W(rows[p], k) H(k, cols[p]) over nnz >= 1
+	// coordinates of index base 0 or 1 (unsorted, duplicates counted per copy).  values (or null: out needed) are the entries' values in T; then sums[0 .. 3] =
+	// sum (v_p - out[p])^2, sum d_beta(v_p | out[p] + eps), the sum of the absolute values of the summands of d_beta, and sqrt(sums[0] / nnz); beta = NaN: no
+	// divergence (sums[1], sums[2] = NaN), any finite v; otherwise the value rule of the masked beta engines.  device: every array lies in DEVICE memory of the
+	// engine's device (the pointer checks and the ordering of upload_dense_device; a validation launch over the index arrays -- and the values -- runs first, and the
+	// gather is not launched unless every coordinate lies inside the matrix); else in host memory (checked on the host before any device work, staged into buffers
+	// the engine owns).  One body for both.  ST_INVALID with last_error() for a coordinate outside the matrix (naming the first p), a value that breaks the rule, an
+	// engine with row blocks or one driven through the three-phase (column-sharded) entries, and an engine whose factors were never set.  The effects on the engine
+	// are get_factors' and no more: the error of the last error iteration stays as it was.  Sums: per-entry terms in T, added in double per 16-lane group in entry
+	// order, groups in group order, workgroups in workgroup order on the host; bit-identical between calls and between the two forms.
+	Status predict_entries(const int* rows, const int* cols, const T* values, long nnz, int base, double beta, T* out, double* sums, bool device);
 
 	// The W^T V launch (and its Gram passengers) of the NEXT iteration, enqueued ahead of it: it writes the split-K slabs, G and the column scale -- scratch the
 	// next iterate() would overwrite anyway -- so a caller that is about to block on this iteration's error value (nmfgpu::compute: the threshold test decides
@@ -320,7 +331,7 @@ public:
 	double masked_beta() const { return mbeta_; }      // the beta of a masked divergence engine, in the precision of T
 	bool is_beta_dense() const { return beta_dense_; }
 	// sharded runs: the error terms refer to the whole matrix (sorted tr(V^T V) terms of ALL columns, sum of ALL entries, total column count)
-	void set_error_globals(const std::vector<T>& vtv_sorted_all, double sum_v_all, long total_columns) { h_vtv_ = vtv_sorted_all; sum_v_ = sum_v_all; err_total_columns_ = total_columns; }
+	void set_error_globals(const std::vector<T>& vtv_sorted_all, double sum_v_all, long total_columns) { column_shard_ = true; h_vtv_ = vtv_sorted_all; sum_v_ = sum_v_all; err_total_columns_ = total_columns; }
 	double sum_v() const { return sum_v_; }
 	// Row-block form of w_finish (reduce-scatter by row blocks of W -> every GPU updates its rows -> all-reduce
 	// of the r column-norm partials -> all-gather of the normalised rows).  num_rows: the reduced (V H^T)^T rows
@@ -464,6 +475,16 @@ private:
 	Status refuse(std::string text) { error_text_ = std::move(text); last_error_ = error_text_.c_str(); return ST_INVALID; }
 	std::string error_text_;                          // owns a composed last_error_ text
 	int device_ = -1;                                 // the HIP device the buffers live on (allocate_buffers)
+	// predict_entries: staging of host coordinate lists (pe_rows_, pe_cols_, pe_vals_) and of the predictions (pe_out_), pe_cap_ entries each, grown on demand; the
+	// per-workgroup sums (pe_part_: 3 * PREDICT_MAX_PARTS doubles) and the two words of the validation launch (pe_flags_); pinned landing buffers of the sums and
+	// flags (pe_pin_) and of the predictions (pe_pin_out_, pe_pin_cap_ entries)
+	int *pe_rows_ = nullptr, *pe_cols_ = nullptr;
+	T *pe_vals_ = nullptr, *pe_out_ = nullptr, *pe_pin_out_ = nullptr;
+	double *pe_part_ = nullptr, *pe_pin_ = nullptr;
+	unsigned* pe_flags_ = nullptr;
+	long pe_cap_ = 0, pe_pin_cap_ = 0;
+	bool have_w_ = false, have_h_ = false;            // a W / an H has been set or drawn (set_factors, set_factors_device, randomize_factors)
+	bool column_shard_ = false;                       // the three-phase entries or a sharded run have driven this engine: it holds a column shard of a larger matrix
 	Status fetch_error_terms(int count_n);            // enqueue the copies, do not wait
 	void finalize_error(bool resolve);
 	void record_begin(int kind = 0);

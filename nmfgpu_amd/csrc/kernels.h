@@ -616,6 +616,28 @@ template <typename T>
 hipError_t launch_masked_beta_half_step(const int* ptr, const int* idx, const T* val, T* A, const T* B, int RP, T eps, double beta, T l1, T l2, bool update,
                                         T* t_frob, T* t_div, T* sumsq_part, int rows, hipStream_t stream);
 
+// ---- predict and score entries of W H (kernels_predict.hip, docs/PREDICT.md) ---------------------------------------------------------------------------------
+// Over a coordinate list rows / cols (nnz entries, index base 0 or 1, unsorted, duplicates counted per copy; DEVICE memory) and the padded panels Wt ([.][RP]) and
+// H ([.][RP]): out[p] = sum_{k < r} Wt(rows[p], k) H(cols[p], k), coordinates k >= r selected out.  vals (or null: predictions only, out needed): the values v_p;
+// then part[3 w + {0, 1, 2}] = workgroup w's sums, in double, of (v_p - out[p])^2, of d_beta(v_p | out[p] + eps) and of the absolute values of the summands of
+// d_beta -- predict_entry_parts(nnz) workgroups, which the caller adds in workgroup order; out may be null.  beta is taken in the precision of T (0: the
+// Itakura-Saito map, 1: the KL map, NaN: no divergence -- the two last sums are 0 --, else the general form).  The kernel checks NO index: launch_predict_validate
+// comes first.  hipErrorInvalidValue for a padded rank without an instantiation (predict_rank_instantiated), nnz outside 1 ... PREDICT_MAX_ENTRIES, r outside
+// 1 ... RP, another base, an infinite beta and a launch with nothing to write.
+constexpr int PREDICT_PASS_ENTRIES = 32;        // entries of one workgroup pass: sixteen groups, two entries in flight each
+constexpr int PREDICT_MAX_PARTS = 2048;         // the grid: min(ceil(nnz / PREDICT_PASS_ENTRIES), PREDICT_MAX_PARTS) workgroups that stride over the passes
+constexpr long PREDICT_MAX_ENTRIES = 0x7fffffffl;
+int predict_entry_parts(long nnz);
+bool predict_rank_instantiated(int RP, size_t elem_bytes);      // fp32: 64, 128, 256, 384, 512; fp64: 64 ... 512 in steps of 64
+template <typename T>
+hipError_t launch_predict_entries(const int* rows, const int* cols, const T* vals, long nnz, int base, const T* Wt, const T* H, int RP, int r, T eps, double beta,
+                                  T* out, double* part, hipStream_t stream);
+// first_bad[0] <- min(first_bad[0], the smallest p whose coordinate lies outside [base, base + m) x [base, base + n)); first_bad[1] likewise for the smallest p
+// whose value breaks `rule` (0: vals not read; 1 finite and >= 0, 2 finite, 3 finite and > 0).  The caller fills both words with 0xffffffff first.  Reads the
+// arrays below nnz only.
+template <typename T>
+hipError_t launch_predict_validate(const int* rows, const int* cols, const T* vals, long nnz, int base, int m, int n, int rule, unsigned* first_bad, hipStream_t stream);
+
 // ---- dense beta-divergence NMF: generalised KL (beta = 1), Itakura-Saito (beta = 0) and the general form (any other finite beta), with optional L1 / L2 penalties, on
 // ---- a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) ---------------------------------------------------------------------------------------------------
 // How one half-step is cut: workgroups of `bo` output columns, reduction tiles of `kt` rows, `slabs` slices of the reduction range (tiles_per_slab tiles each, the last

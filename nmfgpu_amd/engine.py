@@ -429,6 +429,77 @@ class Engine:
         hp, hld, hlay = self._dev(H_out, (self.r, self.n), True) if H_out is not None else (None, 0, 0)
         self._check(self._lib.nmfamd_engine_get_factors_device(self._h, C.c_void_p(wp), C.c_long(wld), wlay, C.c_void_p(hp), C.c_long(hld), hlay), "get_factors_device")
 
+    # ---- predict and score entries of W H (docs/PREDICT.md) ----
+    def _entries(self, rows, cols, values):
+        """The coordinate list of predict / score as C arguments: (on_device, rows, cols, values, nnz), host arrays converted to contiguous int32 / the engine's dtype,
+        device arrays (anything with __cuda_array_interface__: all of them or none) as pointers.  ValueError for mismatched lengths."""
+        given = [a for a in (rows, cols, values) if a is not None]
+        on_device = [hasattr(a, "__cuda_array_interface__") for a in given]
+        if any(on_device) != all(on_device):
+            raise TypeError("rows, cols and values: all of them device arrays, or none")
+        if on_device[0]:
+            rp, nnz = device_vector(rows, np.int32)
+            try:
+                cp, _ = device_vector(cols, np.int32, nnz)
+                vp = device_vector(values, self.dtype, nnz)[0] if values is not None else None
+            except ValueError as exc:
+                raise ValueError(f"rows, cols and values must have the same length: {exc}") from None
+            return True, rp, cp, vp, nnz
+        rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
+        if rows.ndim != 1 or cols.shape != rows.shape:
+            raise ValueError(f"rows and cols must be 1-D arrays of the same length, got {rows.shape} and {cols.shape}")
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=self.dtype)
+            if values.shape != rows.shape:
+                raise ValueError(f"values must have the same length as rows and cols ({rows.shape[0]}), got {values.shape}")
+        return False, rows, cols, values, int(rows.shape[0])
+
+    def _device_out(self, like, nnz: int):
+        """(tensor, ptr): a new torch tensor of nnz values of the engine's dtype on the device of `like` (a torch tensor).  Nothing is imported: the library is the
+        one the caller's tensor brought along."""
+        import sys
+        lib = sys.modules[type(like).__module__.partition(".")[0]]
+        out = like.new_empty((int(nnz),), dtype=getattr(lib, self.dtype.name))
+        return out, device_vector(out, self.dtype, int(nnz))[0]
+
+    def predict(self, rows, cols, base: int = 0):
+        """out[p] = sum_k W(rows[p], k) H(k, cols[p]) for W, H = what get_factors() would return now (nsNMF: W S), in the engine's precision (docs/PREDICT.md).  rows,
+        cols: nnz >= 1 coordinates of index base `base` (0 or 1), unsorted, duplicates allowed -- numpy arrays (an ndarray comes back) or int32 device arrays with
+        __cuda_array_interface__ such as torch tensors on the engine's GPU (a device tensor comes back; nothing crosses to the host).  The engine is left as
+        get_factors() leaves it.  EngineError for a coordinate outside the matrix (no kernel gathers with an unchecked index), for an engine with row blocks or of
+        a sharded run, and before the factors were set."""
+        dev, r, c, _, nnz = self._entries(rows, cols, None)
+        if dev:
+            out, op = self._device_out(rows, nnz)
+            self._check(self._lib.nmfamd_engine_predict_device(self._h, C.c_void_p(r), C.c_void_p(c), C.c_long(nnz), int(base), C.c_void_p(op)), "predict_device")
+            return out
+        out = np.empty(nnz, dtype=self.dtype)
+        self._check(self._lib.nmfamd_engine_predict(self._h, _p(r), _p(c), C.c_long(nnz), int(base), _p(out)), "predict")
+        return out
+
+    def score(self, rows, cols, values, beta: Optional[float] = None, base: int = 0, return_predictions: bool = False) -> dict:
+        """The error of W H over the entries (rows[p], cols[p]) with values[p] (docs/PREDICT.md): {"sq": sum (v - p)^2, "rmsd": sqrt(sq / nnz), "div": sum
+        d_beta(v | p + eps), "abs_div": the sum of the absolute values of the summands of d_beta (the scale of div's rounding), "count": nnz} and, with
+        return_predictions, "predictions" (as predict returns them).  beta=None: no divergence wanted -- div and abs_div are NaN, any finite value is taken;
+        otherwise beta <= 0 needs every value finite and > 0 and beta > 0 finite and >= 0 (EngineError).  Arrays as for predict.  Bit-identical between calls and
+        between host and device arrays."""
+        dev, r, c, v, nnz = self._entries(rows, cols, values)
+        b = C.c_double(float("nan") if beta is None else float(beta))
+        sums = (C.c_double * 4)()
+        out = None
+        if dev:
+            out, op = self._device_out(values, nnz) if return_predictions else (None, None)
+            self._check(self._lib.nmfamd_engine_score_device(self._h, C.c_void_p(r), C.c_void_p(c), C.c_void_p(v), C.c_long(nnz), int(base), b, C.c_void_p(op), sums),
+                        "score_device")
+        else:
+            if return_predictions:
+                out = np.empty(nnz, dtype=self.dtype)
+            self._check(self._lib.nmfamd_engine_score(self._h, _p(r), _p(c), _p(v), C.c_long(nnz), int(base), b, _p(out), sums), "score")
+        res = {"sq": sums[0], "rmsd": sums[3], "div": sums[1], "abs_div": sums[2], "count": nnz}
+        if return_predictions:
+            res["predictions"] = out
+        return res
+
     def upload_sparse(self, fmt: int, values: np.ndarray, a: np.ndarray, b: np.ndarray, base: int = 0):
         values = np.ascontiguousarray(values, dtype=self.dtype)
         a = np.ascontiguousarray(a, dtype=np.int32); b = np.ascontiguousarray(b, dtype=np.int32)
@@ -1473,6 +1544,64 @@ def op_masked_beta_half_step(ptr: np.ndarray, idx: np.ndarray, val: np.ndarray, 
     if st != 0:
         raise EngineError(st, "nmfamd_op_masked_beta_half_step")
     return {"A": A, "t_frob": tf, "t_div": td, "sumsq_part": sq}
+
+
+def predict_entry_parts(nnz: int) -> int:
+    """Workgroups -- and per-workgroup partial sums -- of a predict / score launch over nnz entries (nmfamd_predict_entry_parts): a function of nnz only."""
+    return int(library().nmfamd_predict_entry_parts(C.c_long(int(nnz))))
+
+
+def op_predict_entries(rows: np.ndarray, cols: np.ndarray, Wt: np.ndarray, H: np.ndarray, r: int, vals: Optional[np.ndarray] = None, beta: Optional[float] = None,
+                       base: int = 0, want_out: bool = True, out_len: Optional[int] = None, *, fill=np.nan):
+    """One launch of the gather of kernels_predict.hip (launch_predict_entries, docs/PREDICT.md) on caller-built padded panels: Wt (w_rows, RP) and H (h_rows, RP) of
+    one dtype, r the coordinates that count; rows / cols the coordinates (index base `base`), vals the values (None: predictions only), beta as Engine.score (None:
+    no divergence).  Returns a dict: `out` (out_len >= nnz values pre-filled with `fill`, the first nnz written; None without want_out), `part` ((parts, 3) doubles:
+    each workgroup's sums of the squared errors, of d_beta and of its absolute summands; None without vals) and `sq`, `div`, `abs_div`: the parts added in index
+    order, as the engine adds them."""
+    dt = _sparse_dtype(Wt)
+    Wt = np.ascontiguousarray(Wt, dtype=dt); H = np.ascontiguousarray(H, dtype=dt)
+    rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
+    if Wt.ndim != 2 or H.ndim != 2 or Wt.shape[1] != H.shape[1]:
+        raise ValueError("shapes: Wt (w_rows, RP); H (h_rows, RP)")
+    if rows.ndim != 1 or cols.shape != rows.shape:
+        raise ValueError("rows and cols: one coordinate pair per entry")
+    nnz = int(rows.shape[0])
+    if vals is not None:
+        vals = np.ascontiguousarray(vals, dtype=dt)
+        if vals.shape != rows.shape:
+            raise ValueError("vals: one value per entry")
+    out_len = nnz if out_len is None else int(out_len)
+    out = np.full(max(out_len, 1), fill, dt) if want_out else None
+    parts = predict_entry_parts(nnz) if vals is not None else 0
+    part = np.full((parts, 3), fill, np.float64) if vals is not None else None
+    st = _sparse_fn("predict_entries", dt)(_p(rows), _p(cols), _p(vals), C.c_long(nnz), int(base), _p(Wt), C.c_long(Wt.shape[0]), _p(H), C.c_long(H.shape[0]),
+                                           int(Wt.shape[1]), int(r), C.c_double(float("nan") if beta is None else float(beta)), _p(out), C.c_long(out_len), _p(part), parts)
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_predict_entries")
+    res = {"out": out[:out_len] if out is not None else None, "part": part, "sq": None, "div": None, "abs_div": None}
+    if part is not None:
+        s = [0.0, 0.0, 0.0]
+        for w in range(parts):      # in workgroup order, as Engine<T>::predict_entries
+            for k in range(3):
+                s[k] += float(part[w, k])
+        res.update(sq=s[0], div=s[1] if beta is not None else float("nan"), abs_div=s[2] if beta is not None else float("nan"))
+    return res
+
+
+def split_entries(rows, cols, values, fraction: float, seed: int):
+    """Deals the coordinate list (rows[p], cols[p], values[p]) into a training part and a held-out part for Engine.score (docs/PREDICT.md): round(fraction * nnz)
+    entries, drawn without replacement by numpy's PCG64 seeded with `seed`, are held out; both parts keep the order of the input.  The same arguments give the same
+    split.  Returns ((rows, cols, values) of the training part, (rows, cols, values) of the held-out part); the parts are disjoint as positions of the list and
+    their union is the list (a coordinate stored twice may land once in each)."""
+    rows, cols, values = np.asarray(rows), np.asarray(cols), np.asarray(values)
+    if rows.ndim != 1 or cols.shape != rows.shape or values.shape != rows.shape:
+        raise ValueError("rows, cols and values: 1-D arrays of one length")
+    if not 0.0 <= float(fraction) <= 1.0:
+        raise ValueError("fraction must lie in [0, 1]")
+    nnz = rows.shape[0]
+    held = np.zeros(nnz, dtype=bool)
+    held[np.random.Generator(np.random.PCG64(int(seed))).permutation(nnz)[:int(round(float(fraction) * nnz))]] = True
+    return (rows[~held], cols[~held], values[~held]), (rows[held], cols[held], values[held])
 
 
 def op_kl_update(P: np.ndarray, num_parts: np.ndarray, den: np.ndarray, scale: Optional[np.ndarray] = None, want_sumsq: bool = False, want_sum: bool = True,
