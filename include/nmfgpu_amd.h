@@ -267,6 +267,25 @@ NMFAMD_API int nmfamd_engine_predict_device(nmfamd_engine* e, const int* rows, c
 NMFAMD_API int nmfamd_engine_score_device(nmfamd_engine* e, const int* rows, const int* cols, const void* values, long nnz, int base, double beta, void* out_or_NULL,
                                           double sums[4]);
 
+/* ---- the k best candidates of W H per query (docs/TOPK.md) -------------------------------------
+ * queries: nq >= 1 indices, 32-bit, index base 0 or 1, unsorted, duplicates allowed.  axis 0: a query is a row i of V and the candidates are the n columns,
+ * s(i, j) = sum_{k < r} W(i, k) H(k, j); axis 1: a query is a column and the candidates are the m rows.  1 <= k <= nmfamd_top_k_max() (64).  W, H and the effects
+ * on the engine as for nmfamd_engine_predict.  Scores in the engine's precision, no eps.
+ * Per query the candidates are ordered by score descending, equal scores (numerically: -0 = +0) by ascending index; out_idx [nq][k] (int32, in the caller's base)
+ * and out_scores [nq][k] hold the first k ELIGIBLE candidates in that order, and index -1 / score -inf in the remaining slots when fewer than k are eligible.
+ * excl_ptr [nq + 1] (64-bit, excl_ptr[0] = 0, non-decreasing) and excl_idx [excl_ptr[nq]] (32-bit candidate indices in the caller's base; unsorted, duplicates
+ * allowed), or both NULL: a candidate listed for query q is not eligible for q.
+ * NMFAMD_INVALID_ARGUMENT with a last_error, before any device work, for the engines nmfamd_engine_predict refuses, nq < 1, k outside its range, another base or
+ * axis, a malformed excl_ptr and a query or excluded index outside its range (the first bad one is named).
+ * _device: every array in device memory, with the pointer check and the ordering of the entries above; excl_nnz is the extent of excl_idx and has to equal
+ * excl_ptr[nq].  A validation launch reads the index arrays first; the product is not launched unless it found everything inside. */
+NMFAMD_API int nmfamd_top_k_max(void);
+NMFAMD_API int nmfamd_top_k_slabs(long nq, long count);   /* slices of the candidate range that one workgroup each walks: a function of the two numbers only */
+NMFAMD_API int nmfamd_engine_top_k(nmfamd_engine* e, const int* queries, long nq, int k, int axis, int base, const long* excl_ptr, const int* excl_idx, int* out_idx,
+                                   void* out_scores);
+NMFAMD_API int nmfamd_engine_top_k_device(nmfamd_engine* e, const int* queries, long nq, int k, int axis, int base, const long* excl_ptr, const int* excl_idx,
+                                          long excl_nnz, int* out_idx, void* out_scores);
+
 /* Uniform (0,1] fill, the same seed for both factors (source/init/RandomValueStrategy.cpp:29-70). */
 NMFAMD_API int nmfamd_engine_randomize(nmfamd_engine* e, unsigned seed, int w, int h);
 
@@ -748,6 +767,14 @@ NMFAMD_API int nmfamd_op_predict_entries_f32(const int* rows, const int* cols, c
                                              long h_rows, int RP, int r, double beta, float* out, long out_len, double* part, int parts);
 NMFAMD_API int nmfamd_op_predict_entries_f64(const int* rows, const int* cols, const double* vals, long nnz, int base, const double* Wt, long w_rows, const double* H,
                                              long h_rows, int RP, int r, double beta, double* out, long out_len, double* part, int parts);
+/* top_k: the two launches of kernels_topk.hip (docs/TOPK.md) on caller-built padded panels: the query panel A [a_rows][RP] and the candidate panel B [b_rows][RP]
+ * (RP as predict_entries), r in 1 ... RP the coordinates that count, candidates 0 ... count - 1 (count <= b_rows).  queries, k, base, excl_ptr / excl_idx (or both
+ * NULL) and the outputs as nmfamd_engine_top_k; every index is checked here, on the host (NMFAMD_INVALID_ARGUMENT).  slabs: 0 for nmfamd_top_k_slabs(nq, count),
+ * or 1 ... 256 to override it; the result does not depend on it. */
+NMFAMD_API int nmfamd_op_top_k_f32(const int* queries, long nq, int k, int base, const float* A, long a_rows, const float* B, long b_rows, long count, int RP, int r,
+                                   const long* excl_ptr, const int* excl_idx, int slabs, int* out_idx, float* out_scores);
+NMFAMD_API int nmfamd_op_top_k_f64(const int* queries, long nq, int k, int base, const double* A, long a_rows, const double* B, long b_rows, long count, int RP, int r,
+                                   const long* excl_ptr, const int* excl_idx, int slabs, int* out_idx, double* out_scores);
 /* kl_update: P(y, c) <- (P(y, c) * scale(c)) * (sum over the parts of num) / (den(c) + eps) on P [len_pad][RP] (scale NULL: ones); num holds `parts` panels
  * part_stride values apart (a multiple of 4, >= len_pad * RP when parts > 1; what lies between two panels is not read).  sumsq_part / sum_part (each optional,
  * [len_pad / 128][RP]): per 128 rows the sums of squares / the sums of the new values.  len_pad a multiple of 128. */

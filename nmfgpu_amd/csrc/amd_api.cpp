@@ -406,6 +406,17 @@ int nmfamd_engine_score_device(nmfamd_engine* e, const int* rows, const int* col
 	                   [&](Engine<double>& g) { return g.predict_entries(rows, cols, (const double*)values, nnz, base, beta, (double*)out, sums, true); });
 }
 
+int nmfamd_engine_top_k(nmfamd_engine* e, const int* queries, long nq, int k, int axis, int base, const long* excl_ptr, const int* excl_idx, int* out_idx, void* out_scores) {
+	return dispatch(e, [&](Engine<float>& g) { return g.top_k(queries, nq, k, axis, base, excl_ptr, excl_idx, 0, out_idx, (float*)out_scores, false); },
+	                   [&](Engine<double>& g) { return g.top_k(queries, nq, k, axis, base, excl_ptr, excl_idx, 0, out_idx, (double*)out_scores, false); });
+}
+
+int nmfamd_engine_top_k_device(nmfamd_engine* e, const int* queries, long nq, int k, int axis, int base, const long* excl_ptr, const int* excl_idx, long excl_nnz,
+                               int* out_idx, void* out_scores) {
+	return dispatch(e, [&](Engine<float>& g) { return g.top_k(queries, nq, k, axis, base, excl_ptr, excl_idx, excl_nnz, out_idx, (float*)out_scores, true); },
+	                   [&](Engine<double>& g) { return g.top_k(queries, nq, k, axis, base, excl_ptr, excl_idx, excl_nnz, out_idx, (double*)out_scores, true); });
+}
+
 int nmfamd_device_pointer_info(const void* p, int* kind, int* device, unsigned long long* bytes_from_p) {
 	if (!kind || !device || !bytes_from_p) return NMFAMD_INVALID_ARGUMENT;
 	if (nmfamd_device_count() <= 0) { *kind = 0; *device = -1; *bytes_from_p = 0; return NMFAMD_NO_DEVICE; }
@@ -1571,6 +1582,46 @@ int op_predict_entries(const int* rows, const int* cols, const T* vals, long nnz
 	return NMFAMD_OK;
 }
 
+// The two launches of kernels_topk.hip on caller-built padded panels (docs/TOPK.md).  Every index is checked here, on the host: the kernels check none.
+template <typename T>
+int op_top_k(const int* queries, long nq, int k, int base, const T* A, long a_rows, const T* B, long b_rows, long count, int RP, int r, const long* excl_ptr,
+             const int* excl_idx, int slabs, int* out_idx, T* out_scores) {
+	if (!queries || !A || !B || !out_idx || !out_scores || nq < 1 || nq > TOPK_MAX_QUERIES || k < 1 || k > TOPK_MAX_K || (base != 0 && base != 1) || a_rows < 1 ||
+	    b_rows < 1 || count < 1 || count > b_rows || count > TOPK_MAX_CANDIDATES || !predict_rank_instantiated(RP, sizeof(T)) || r < 1 || r > RP || slabs < 0 ||
+	    slabs > TOPK_MAX_SLABS || (!excl_ptr && excl_idx))
+		return NMFAMD_INVALID_ARGUMENT;
+	for (long q = 0; q < nq; ++q) {
+		const long i = (long)queries[q] - base;
+		if (i < 0 || i >= a_rows) return NMFAMD_INVALID_ARGUMENT;
+	}
+	long excl_nnz = 0;
+	if (excl_ptr) {
+		if (excl_ptr[0] != 0) return NMFAMD_INVALID_ARGUMENT;
+		for (long q = 1; q <= nq; ++q)
+			if (excl_ptr[q] < excl_ptr[q - 1]) return NMFAMD_INVALID_ARGUMENT;
+		excl_nnz = excl_ptr[nq];
+		if (excl_nnz > 0 && !excl_idx) return NMFAMD_INVALID_ARGUMENT;
+		for (long e = 0; e < excl_nnz; ++e) {
+			const long c = (long)excl_idx[e] - base;
+			if (c < 0 || c >= count) return NMFAMD_INVALID_ARGUMENT;
+		}
+	}
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const size_t part = (size_t)nq * (size_t)(slabs > 0 ? slabs : topk_slabs(nq, count)) * k, outs = (size_t)nq * k;
+	DevBuf dQ, dA, dB, dP, dE, dPs, dPi, dOi, dOs;
+	if (upload(dQ, queries, (size_t)nq) != hipSuccess || upload(dA, A, (size_t)a_rows * RP) != hipSuccess || upload(dB, B, (size_t)b_rows * RP) != hipSuccess ||
+	    (excl_nnz > 0 && (upload(dP, excl_ptr, (size_t)nq + 1) != hipSuccess || upload(dE, excl_idx, (size_t)excl_nnz) != hipSuccess)) ||
+	    dPs.alloc(sizeof(T) * part) != hipSuccess || dPi.alloc(sizeof(int) * part) != hipSuccess || dOi.alloc(sizeof(int) * outs) != hipSuccess ||
+	    dOs.alloc(sizeof(T) * outs) != hipSuccess)
+		return NMFAMD_NO_DEVICE_MEMORY;
+	const int st = op_status(launch_topk<T>((const int*)dQ.p, nq, k, base, (const T*)dA.p, (const T*)dB.p, count, RP, r, (const long*)dP.p, (const int*)dE.p, slabs,
+	                                        (T*)dPs.p, (int*)dPi.p, (int*)dOi.p, (T*)dOs.p, nullptr));
+	if (st != NMFAMD_OK) return st;
+	if (hipMemcpy(out_idx, dOi.p, sizeof(int) * outs, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out_scores, dOs.p, sizeof(T) * outs, hipMemcpyDeviceToHost) != hipSuccess)
+		return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
+
 template <typename T>
 int op_kl_update(T* P, const T* num, int parts, long part_stride, const T* den, const T* scale, int RP, int len_pad, T* sumsq_part, T* sum_part) {
 	// num: `parts` panels of len_pad * RP values, part_stride values apart (what lies between them is uploaded too, and must not be read)
@@ -1809,6 +1860,19 @@ int nmfamd_op_hals_normalize_f64(double* Wt, int RP, int mpad, double* H, int np
 int nmfamd_masked_norm_parts(int rows) { return rows > 0 ? masked_norm_parts(rows) : 0; }
 
 int nmfamd_predict_entry_parts(long nnz) { return nnz > 0 ? predict_entry_parts(nnz) : 0; }
+
+int nmfamd_top_k_max(void) { return TOPK_MAX_K; }
+int nmfamd_top_k_slabs(long nq, long count) { return topk_slabs(nq, count); }
+
+int nmfamd_op_top_k_f32(const int* queries, long nq, int k, int base, const float* A, long a_rows, const float* B, long b_rows, long count, int RP, int r,
+                        const long* excl_ptr, const int* excl_idx, int slabs, int* out_idx, float* out_scores) {
+	return op_top_k<float>(queries, nq, k, base, A, a_rows, B, b_rows, count, RP, r, excl_ptr, excl_idx, slabs, out_idx, out_scores);
+}
+
+int nmfamd_op_top_k_f64(const int* queries, long nq, int k, int base, const double* A, long a_rows, const double* B, long b_rows, long count, int RP, int r,
+                        const long* excl_ptr, const int* excl_idx, int slabs, int* out_idx, double* out_scores) {
+	return op_top_k<double>(queries, nq, k, base, A, a_rows, B, b_rows, count, RP, r, excl_ptr, excl_idx, slabs, out_idx, out_scores);
+}
 
 int nmfamd_op_predict_entries_f32(const int* rows, const int* cols, const float* vals, long nnz, int base, const float* Wt, long w_rows, const float* H, long h_rows, int RP,
                                   int r, double beta, float* out, long out_len, double* part, int parts) {

@@ -1307,6 +1307,137 @@ Status Engine<T>::predict_entries(const int* rows, const int* cols, const T* val
 	return ST_OK;
 }
 
+// The k best candidates of W H per query (docs/TOPK.md; kernels_topk.hip).  One body for host and device arrays, shaped like predict_entries: the refusals that need no
+// array, the pointer checks (device) or the host check of every index (host: before any device work), the staging of host arrays, the validation launch (device: no
+// product runs unless it found everything inside), export_panel_w -- get_factors' effects -- and the two launches; host results come down through pinned memory.
+template <typename T>
+Status Engine<T>::top_k(const int* queries, long nq, int k, int axis, int base, const long* excl_ptr, const int* excl_idx, long excl_nnz, int* out_idx, T* out_scores,
+                        bool device) {
+	if (row_blocks_ > 1) return refuse("top_k: an engine with row blocks holds a column shard of a sharded run (its export is a collective); top_k on a single engine");
+	if (column_shard_ || w_gather_hook_) return refuse("top_k: the engine is bound to a sharded run and holds a column shard; top_k on a single engine");
+	if (!have_w_ || !have_h_) return refuse("top_k: the engine has no factors yet (set_factors or randomize first)");
+	if (nq < 1 || nq > TOPK_MAX_QUERIES) return refuse("top_k: nq has to be 1 ... 2^30 queries");
+	if (k < 1 || k > TOPK_MAX_K) return refuse("top_k: k has to be 1 ... " + std::to_string(TOPK_MAX_K));
+	if (base != 0 && base != 1) return refuse("top_k: the index base has to be 0 or 1");
+	if (axis != 0 && axis != 1) return refuse("top_k: axis has to be 0 (queries are rows) or 1 (queries are columns)");
+	if (queries == nullptr || out_idx == nullptr || out_scores == nullptr) return refuse("top_k: null query or output array");
+	if (excl_ptr == nullptr && excl_idx != nullptr) return refuse("top_k: excl_idx without excl_ptr");
+	if (!predict_rank_instantiated(RP_, sizeof(T))) return refuse("top_k: no kernel for padded rank " + std::to_string(RP_));
+	const long a_rows = axis == 0 ? m_ : n_, count = axis == 0 ? n_ : m_;
+	const std::string where = device ? "; found by the validation launch, the product was not launched" : "; found on the host, before any device work";
+	auto bad_query = [&](unsigned long q) {
+		return refuse("top_k: query " + std::to_string(q) + " is outside [base, base + " + std::to_string(a_rows) + ")" + where);
+	};
+	auto bad_ptr = [&](unsigned long q) {
+		return refuse("top_k: excl_ptr is malformed at " + std::to_string(q) + " (it starts at 0, does not decrease" + (device ? ", and ends at excl_nnz)" : ")") + where);
+	};
+	auto bad_excluded = [&](unsigned long e) {
+		return refuse("top_k: excluded index " + std::to_string(e) + " is outside [base, base + " + std::to_string(count) + ")" + where);
+	};
+	if (device) {
+		if (excl_nnz < 0) return refuse("top_k: excl_nnz is negative");
+		if (Status st = check_device_vector("queries", queries, sizeof(int), nq)) return st;
+		if (excl_ptr) {
+			if (Status st = check_device_vector("excl_ptr", excl_ptr, sizeof(long), nq + 1)) return st;
+			if (Status st = check_device_vector("excl_idx", excl_idx, sizeof(int), excl_nnz)) return st;
+		}
+		if (Status st = check_device_vector("indices", out_idx, sizeof(int), nq * k)) return st;
+		if (Status st = check_device_vector("scores", out_scores, sizeof(T), nq * k)) return st;
+		HIPX(hipDeviceSynchronize());      // whatever stream produced the arrays has finished
+	} else {
+		for (long q = 0; q < nq; ++q) {
+			const long i = (long)queries[q] - base;
+			if (i < 0 || i >= a_rows) return bad_query((unsigned long)q);
+		}
+		excl_nnz = 0;
+		if (excl_ptr) {
+			if (excl_ptr[0] != 0) return bad_ptr(0);
+			for (long q = 1; q <= nq; ++q)
+				if (excl_ptr[q] < excl_ptr[q - 1]) return bad_ptr((unsigned long)q);
+			excl_nnz = excl_ptr[nq];
+			if (excl_nnz > 0 && excl_idx == nullptr) return refuse("top_k: excl_ptr names entries and excl_idx is null");
+			for (long e = 0; e < excl_nnz; ++e) {
+				const long c = (long)excl_idx[e] - base;
+				if (c < 0 || c >= count) return bad_excluded((unsigned long)e);
+			}
+		}
+	}
+	// the engine's own buffers
+	if (tk_flags_ == nullptr) {
+		HIPX(buffers_.device(&tk_flags_, sizeof(unsigned) * 3, false, stream_));
+		HIPX(buffers_.pinned(&tk_pin_flags_, sizeof(unsigned) * 3));
+	}
+	const int slabs = topk_slabs(nq, count);
+	const long part = nq * slabs * k, outs = nq * k;
+	if (part > tk_part_cap_) {
+		buffers_.release(tk_part_s_, tk_part_i_);
+		tk_part_cap_ = 0;
+		const long cap = std::max(part, 4096l);
+		HIPX(buffers_.device(&tk_part_s_, sizeof(T) * (size_t)cap, false, stream_));
+		HIPX(buffers_.device(&tk_part_i_, sizeof(int) * (size_t)cap, false, stream_));
+		tk_part_cap_ = cap;
+	}
+	const int* d_q = queries; const long* d_eptr = excl_ptr; const int* d_eidx = excl_idx; int* d_oi = out_idx; T* d_os = out_scores;
+	if (!device) {
+		if (nq > tk_q_cap_) {
+			buffers_.release(tk_q_, tk_eptr_);
+			tk_q_cap_ = 0;
+			const long cap = std::max(nq, 1024l);
+			HIPX(buffers_.device(&tk_q_, sizeof(int) * (size_t)cap, false, stream_));
+			HIPX(buffers_.device(&tk_eptr_, sizeof(long) * (size_t)(cap + 1), false, stream_));
+			tk_q_cap_ = cap;
+		}
+		if (excl_nnz > tk_e_cap_) {
+			buffers_.release(tk_eidx_);
+			tk_e_cap_ = 0;
+			const long cap = std::max(excl_nnz, 1024l);
+			HIPX(buffers_.device(&tk_eidx_, sizeof(int) * (size_t)cap, false, stream_));
+			tk_e_cap_ = cap;
+		}
+		if (outs > tk_out_cap_) {
+			buffers_.release(tk_out_i_, tk_out_s_, tk_pin_i_, tk_pin_s_);
+			tk_out_cap_ = 0;
+			const long cap = std::max(outs, 1024l);
+			HIPX(buffers_.device(&tk_out_i_, sizeof(int) * (size_t)cap, false, stream_));
+			HIPX(buffers_.device(&tk_out_s_, sizeof(T) * (size_t)cap, false, stream_));
+			HIPX(buffers_.pinned(&tk_pin_i_, sizeof(int) * (size_t)cap));
+			HIPX(buffers_.pinned(&tk_pin_s_, sizeof(T) * (size_t)cap));
+			tk_out_cap_ = cap;
+		}
+		HIPX(hipMemcpyAsync(tk_q_, queries, sizeof(int) * (size_t)nq, hipMemcpyHostToDevice, stream_));
+		d_q = tk_q_; d_oi = tk_out_i_; d_os = tk_out_s_;
+		d_eptr = nullptr; d_eidx = nullptr;
+		if (excl_nnz > 0) {      // (lists that are all empty exclude nothing)
+			HIPX(hipMemcpyAsync(tk_eptr_, excl_ptr, sizeof(long) * (size_t)(nq + 1), hipMemcpyHostToDevice, stream_));
+			HIPX(hipMemcpyAsync(tk_eidx_, excl_idx, sizeof(int) * (size_t)excl_nnz, hipMemcpyHostToDevice, stream_));
+			d_eptr = tk_eptr_; d_eidx = tk_eidx_;
+		}
+	} else {
+		// no index of a device array has been looked at yet: the validation launch reads the index arrays only, inside the extents checked above
+		HIPX(hipMemsetAsync(tk_flags_, 0xff, sizeof(unsigned) * 3, stream_));
+		HIPX(launch_topk_validate(d_q, nq, base, a_rows, count, d_eptr, d_eidx, excl_nnz, tk_flags_, stream_));
+		HIPX(hipMemcpyAsync(tk_pin_flags_, tk_flags_, sizeof(unsigned) * 3, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipStreamSynchronize(stream_));
+		if (tk_pin_flags_[0] != 0xffffffffu) return bad_query(tk_pin_flags_[0]);      // (no product was launched)
+		if (tk_pin_flags_[1] != 0xffffffffu) return bad_ptr(tk_pin_flags_[1]);
+		if (tk_pin_flags_[2] != 0xffffffffu) return bad_excluded(tk_pin_flags_[2]);
+		if (excl_nnz == 0) { d_eptr = nullptr; d_eidx = nullptr; }      // (every list is empty)
+	}
+	const T* src = nullptr;
+	if (Status s = export_panel_w(true, &src)) return s;
+	HIPX(launch_topk<T>(d_q, nq, k, base, axis == 0 ? src : H_, axis == 0 ? H_ : src, count, RP_, r_, d_eptr, d_eidx, slabs, tk_part_s_, tk_part_i_, d_oi, d_os, stream_));
+	if (!device) {
+		HIPX(hipMemcpyAsync(tk_pin_i_, tk_out_i_, sizeof(int) * (size_t)outs, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipMemcpyAsync(tk_pin_s_, tk_out_s_, sizeof(T) * (size_t)outs, hipMemcpyDeviceToHost, stream_));
+	}
+	HIPX(hipStreamSynchronize(stream_));
+	if (!device) {
+		std::memcpy(out_idx, tk_pin_i_, sizeof(int) * (size_t)outs);
+		std::memcpy(out_scores, tk_pin_s_, sizeof(T) * (size_t)outs);
+	}
+	return ST_OK;
+}
+
 template <typename T>
 Status Engine<T>::randomize_factors(unsigned seed, bool w, bool h, long h_first_column) {
 	// The reference seeds W's and H's generators identically (RandomValueStrategy.cpp:53-69).

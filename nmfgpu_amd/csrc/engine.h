@@ -279,6 +279,15 @@ public:
 	// are get_factors' and no more: the error of the last error iteration stays as it was.  Sums: per-entry terms in T, added in double per 16-lane group in entry
 	// order, groups in group order, workgroups in workgroup order on the host; bit-identical between calls and between the two forms.
 	Status predict_entries(const int* rows, const int* cols, const T* values, long nnz, int base, double beta, T* out, double* sums, bool device);
+	// The k best candidates of W H per query (docs/TOPK.md), W and H being what get_factors would return now.  axis 0: a query is a row of V and the candidates are
+	// the n columns; axis 1: a query is a column and the candidates are the m rows.  queries: nq >= 1 indices of base 0 or 1 (unsorted, duplicates allowed);
+	// 1 <= k <= TOPK_MAX_K.  out_idx [nq][k] (int32, in the caller's base) and out_scores [nq][k]: per query the first k eligible candidates by (score descending,
+	// index ascending), -1 / -inf where fewer than k are eligible.  excl_ptr [nq + 1] (64-bit, starts at 0, non-decreasing) and excl_idx [excl_ptr[nq]] (candidate
+	// indices of the same base, unsorted, duplicates allowed), or both null: the candidates that are not eligible for a query.  device: every array lies in DEVICE
+	// memory (the pointer checks and the ordering of upload_dense_device, excl_idx over excl_nnz elements; a validation launch reads the index arrays first and the
+	// product is not launched unless it found everything inside); else in host memory (checked on the host before any device work -- excl_nnz is not read --, staged
+	// into buffers the engine owns).  One body for both.  Refusals and effects as predict_entries.  Bit-identical between calls and between the two forms.
+	Status top_k(const int* queries, long nq, int k, int axis, int base, const long* excl_ptr, const int* excl_idx, long excl_nnz, int* out_idx, T* out_scores, bool device);
 
 	// The W^T V launch (and its Gram passengers) of the NEXT iteration, enqueued ahead of it: it writes the split-K slabs, G and the column scale -- scratch the
 	// next iterate() would overwrite anyway -- so a caller that is about to block on this iteration's error value (nmfgpu::compute: the threshold test decides
@@ -483,6 +492,14 @@ private:
 	double *pe_part_ = nullptr, *pe_pin_ = nullptr;
 	unsigned* pe_flags_ = nullptr;
 	long pe_cap_ = 0, pe_pin_cap_ = 0;
+	// top_k: staging of host queries and exclusion lists (tk_q_, tk_eptr_: tk_q_cap_ queries; tk_eidx_: tk_e_cap_ entries), the slabs' partial lists (tk_part_s_,
+	// tk_part_i_: tk_part_cap_ entries), the results of host calls (tk_out_i_, tk_out_s_ and their pinned landing buffers tk_pin_i_, tk_pin_s_: tk_out_cap_ entries),
+	// the three words of the validation launch (tk_flags_) and their pinned landing buffer (tk_pin_flags_)
+	int *tk_q_ = nullptr, *tk_eidx_ = nullptr, *tk_part_i_ = nullptr, *tk_out_i_ = nullptr, *tk_pin_i_ = nullptr;
+	long* tk_eptr_ = nullptr;
+	T *tk_part_s_ = nullptr, *tk_out_s_ = nullptr, *tk_pin_s_ = nullptr;
+	unsigned *tk_flags_ = nullptr, *tk_pin_flags_ = nullptr;
+	long tk_q_cap_ = 0, tk_e_cap_ = 0, tk_part_cap_ = 0, tk_out_cap_ = 0;
 	bool have_w_ = false, have_h_ = false;            // a W / an H has been set or drawn (set_factors, set_factors_device, randomize_factors)
 	bool column_shard_ = false;                       // the three-phase entries or a sharded run have driven this engine: it holds a column shard of a larger matrix
 	Status fetch_error_terms(int count_n);            // enqueue the copies, do not wait

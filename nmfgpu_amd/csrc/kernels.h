@@ -638,6 +638,32 @@ hipError_t launch_predict_entries(const int* rows, const int* cols, const T* val
 template <typename T>
 hipError_t launch_predict_validate(const int* rows, const int* cols, const T* vals, long nnz, int base, int m, int n, int rule, unsigned* first_bad, hipStream_t stream);
 
+// ---- the k best candidates of W H per query: fused product and selection (kernels_topk.hip, docs/TOPK.md) -----------------------------------------------------
+// queries (nq indices of base 0 or 1 into the rows of the query panel A [.][RP]) against the candidates 0 ... count - 1 (rows of the candidate panel B [.][RP]):
+// s(q, j) = sum_{k < r} A(queries[q], k) B(j, k), coordinates k >= r selected to zero in both operands.  Per query the first k candidates by (score descending,
+// index ascending) that its exclusion list (excl_ptr [nq + 1], 64-bit, and excl_idx, candidate indices of the same base; both null: none) does not name:
+// out_idx [nq][k] (in the caller's base; -1 where fewer than k are eligible) and out_scores [nq][k] (-inf there).  slabs: slices of the candidate range that one
+// workgroup each walks (0: topk_slabs(nq, count)); the result does not depend on it.  part_s / part_i: room for nq * slabs * k partial entries (slabs as given, or
+// the plan's).  Everything in DEVICE memory.  The kernels check NO index: launch_topk_validate, or the host, comes first.  hipErrorInvalidValue for a padded rank
+// outside predict_rank_instantiated's list, k outside 1 ... TOPK_MAX_K, r outside 1 ... RP, another base, slabs outside 0 ... TOPK_MAX_SLABS.
+constexpr int TOPK_MAX_K = 64;
+constexpr int TOPK_MAX_SLABS = 256;
+constexpr int TOPK_SEGMENT_TILES = 32;           // tiles of a slab that share one clearing of the exclusion bitmap
+constexpr int TOPK_TARGET_WORKGROUPS = 1024;     // topk_slabs: four workgroups per CU when the queries alone give fewer
+constexpr int TOPK_LDS_LIMIT = 160 * 1024;
+constexpr long TOPK_MAX_QUERIES = 1l << 30, TOPK_MAX_CANDIDATES = 1l << 30;
+int topk_slabs(long nq, long count);
+template <typename T>
+int topk_waves(long nq, int RP, int k);          // waves (of 32 fp32 / 16 fp64 queries) per workgroup: the most, up to 4, whose LDS fits; 0: none fits
+template <typename T>
+hipError_t launch_topk(const int* queries, long nq, int k, int base, const T* A, const T* B, long count, int RP, int r, const long* excl_ptr, const int* excl_idx,
+                       int slabs, T* part_s, int* part_i, int* out_idx, T* out_scores, hipStream_t stream);
+// first_bad[0] <- the smallest q whose query lies outside [base, base + a_rows); first_bad[1] <- the smallest q in 0 ... nq at which excl_ptr breaks its rule
+// (excl_ptr[0] = 0, non-decreasing, excl_ptr[nq] = excl_nnz); first_bad[2] <- the smallest e whose excl_idx[e] lies outside [base, base + count).  The caller fills
+// the three words with 0xffffffff first.  Reads queries below nq, excl_ptr below nq + 1, excl_idx below excl_nnz only.
+hipError_t launch_topk_validate(const int* queries, long nq, int base, long a_rows, long count, const long* excl_ptr, const int* excl_idx, long excl_nnz,
+                                unsigned* first_bad, hipStream_t stream);
+
 // ---- dense beta-divergence NMF: generalised KL (beta = 1), Itakura-Saito (beta = 0) and the general form (any other finite beta), with optional L1 / L2 penalties, on
 // ---- a dense resident V (kernels_beta.hip, docs/DIVERGENCE.md) ---------------------------------------------------------------------------------------------------
 // How one half-step is cut: workgroups of `bo` output columns, reduction tiles of `kt` rows, `slabs` slices of the reduction range (tiles_per_slab tiles each, the last

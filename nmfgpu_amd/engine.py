@@ -454,13 +454,14 @@ class Engine:
                 raise ValueError(f"values must have the same length as rows and cols ({rows.shape[0]}), got {values.shape}")
         return False, rows, cols, values, int(rows.shape[0])
 
-    def _device_out(self, like, nnz: int):
-        """(tensor, ptr): a new torch tensor of nnz values of the engine's dtype on the device of `like` (a torch tensor).  Nothing is imported: the library is the
-        one the caller's tensor brought along."""
+    def _device_out(self, like, nnz: int, dtype=None):
+        """(tensor, ptr): a new torch tensor of nnz values of the engine's dtype (or `dtype`) on the device of `like` (a torch tensor).  Nothing is imported: the
+        library is the one the caller's tensor brought along."""
         import sys
+        dt = self.dtype if dtype is None else np.dtype(dtype)
         lib = sys.modules[type(like).__module__.partition(".")[0]]
-        out = like.new_empty((int(nnz),), dtype=getattr(lib, self.dtype.name))
-        return out, device_vector(out, self.dtype, int(nnz))[0]
+        out = like.new_empty((int(nnz),), dtype=getattr(lib, dt.name))
+        return out, device_vector(out, dt, int(nnz))[0]
 
     def predict(self, rows, cols, base: int = 0):
         """out[p] = sum_k W(rows[p], k) H(k, cols[p]) for W, H = what get_factors() would return now (nsNMF: W S), in the engine's precision (docs/PREDICT.md).  rows,
@@ -499,6 +500,46 @@ class Engine:
         if return_predictions:
             res["predictions"] = out
         return res
+
+    # ---- the k best candidates of W H per query (docs/TOPK.md) ----
+    def top_k(self, queries, k: int, axis: int = 0, exclude=None, base: int = 0):
+        """(indices, scores), each (nq, k): per query the k candidates with the highest score of W H, W and H being what get_factors() would return now
+        (docs/TOPK.md).  axis=0: a query is a row of V and the candidates are the n columns; axis=1: a query is a column and the candidates are the m rows.
+        Candidates are ordered by score descending, equal scores by ascending index; indices are int32 in the caller's base, scores in the engine's precision.
+        exclude: a pair (excl_ptr, excl_idx) -- int64 offsets of nq + 1 entries and int32 candidate indices, as exclusion_lists builds them -- of candidates that are
+        not eligible for a query; where fewer than k are eligible the remaining slots hold index -1 and score -inf.  1 <= k <= TOPK_MAX_K.  queries: a numpy array
+        (ndarrays come back) or an int32 device array with __cuda_array_interface__ such as a torch tensor on the engine's GPU (device tensors come back, exclude
+        is then a pair of device arrays, and nothing crosses to the host).  The engine is left as get_factors() leaves it.  EngineError for a query or an excluded
+        index outside its range, a malformed excl_ptr, and the engines predict refuses."""
+        k = int(k)
+        if hasattr(queries, "__cuda_array_interface__"):
+            qp, nq = device_vector(queries, np.int32)
+            ep = ip = None
+            ennz = 0
+            if exclude is not None:
+                ep, np1 = device_vector(exclude[0], np.int64)
+                if np1 != nq + 1:
+                    raise ValueError(f"exclude[0] must hold nq + 1 = {nq + 1} offsets, got {np1}")
+                ip, ennz = device_vector(exclude[1], np.int32)
+            idx, xp = self._device_out(queries, max(nq * k, 0), np.int32)
+            sc, sp = self._device_out(queries, max(nq * k, 0))
+            self._check(self._lib.nmfamd_engine_top_k_device(self._h, C.c_void_p(qp), C.c_long(nq), k, int(axis), int(base), C.c_void_p(ep), C.c_void_p(ip), C.c_long(ennz),
+                                                             C.c_void_p(xp), C.c_void_p(sp)), "top_k_device")
+            return idx.view(nq, k), sc.view(nq, k)
+        q = np.ascontiguousarray(queries, dtype=np.int32)
+        if q.ndim != 1:
+            raise ValueError(f"queries must be a 1-D array, got {q.shape}")
+        nq = int(q.shape[0])
+        ep = ip = None
+        if exclude is not None:
+            ep = np.ascontiguousarray(exclude[0], dtype=np.int64); ip = np.ascontiguousarray(exclude[1], dtype=np.int32)
+            if ep.shape != (nq + 1,) or ip.ndim != 1:
+                raise ValueError(f"exclude: (excl_ptr of nq + 1 = {nq + 1} offsets, excl_idx), got {ep.shape} and {ip.shape}")
+            if ep[0] == 0 and (np.diff(ep) >= 0).all() and ep[-1] > ip.shape[0]:
+                raise ValueError(f"exclude: excl_ptr names {int(ep[-1])} entries, excl_idx holds {ip.shape[0]}")
+        idx = np.empty((nq, max(k, 0)), dtype=np.int32); sc = np.empty((nq, max(k, 0)), dtype=self.dtype)
+        self._check(self._lib.nmfamd_engine_top_k(self._h, _p(q), C.c_long(nq), k, int(axis), int(base), _p(ep), _p(ip), _p(idx), _p(sc)), "top_k")
+        return idx, sc
 
     def upload_sparse(self, fmt: int, values: np.ndarray, a: np.ndarray, b: np.ndarray, base: int = 0):
         values = np.ascontiguousarray(values, dtype=self.dtype)
@@ -1602,6 +1643,66 @@ def split_entries(rows, cols, values, fraction: float, seed: int):
     held = np.zeros(nnz, dtype=bool)
     held[np.random.Generator(np.random.PCG64(int(seed))).permutation(nnz)[:int(round(float(fraction) * nnz))]] = True
     return (rows[~held], cols[~held], values[~held]), (rows[held], cols[held], values[held])
+
+
+def exclusion_lists(queries, rows, cols, axis: int = 0, base: int = 0):
+    """The exclusion lists of Engine.top_k (docs/TOPK.md) from a coordinate list (rows[p], cols[p]) -- the training entries: "the items this user has already
+    rated".  axis=0: query q is row queries[q] and its list holds the columns of the entries of that row; axis=1: the rows of the entries of that column.  queries,
+    rows and cols share the index base `base`, and so does the result.  Returns (excl_ptr, excl_idx): int64 offsets of nq + 1 entries and int32 candidate indices,
+    a query's candidates in the order of the coordinate list (duplicates stay); a query listed twice gets its list twice."""
+    queries = np.asarray(queries); rows = np.asarray(rows); cols = np.asarray(cols)
+    if queries.ndim != 1 or rows.ndim != 1 or cols.shape != rows.shape:
+        raise ValueError("queries: a 1-D array; rows and cols: 1-D arrays of one length")
+    if axis not in (0, 1):
+        raise ValueError("axis must be 0 or 1")
+    if base not in (0, 1):
+        raise ValueError("base must be 0 or 1")
+    key, other = (rows, cols) if axis == 0 else (cols, rows)
+    order = np.argsort(key, kind="stable")
+    sorted_key = key[order]
+    lo = np.searchsorted(sorted_key, queries, side="left"); hi = np.searchsorted(sorted_key, queries, side="right")
+    counts = (hi - lo).astype(np.int64)
+    ptr = np.zeros(queries.shape[0] + 1, dtype=np.int64)
+    np.cumsum(counts, out=ptr[1:])
+    within = np.arange(int(ptr[-1]), dtype=np.int64) - np.repeat(ptr[:-1], counts)
+    idx = other[order][np.repeat(lo.astype(np.int64), counts) + within].astype(np.int32)
+    return ptr, idx
+
+
+def top_k_slabs(nq: int, count: int) -> int:
+    """Slices of the candidate range that one workgroup each walks in a top_k launch of nq queries over `count` candidates (nmfamd_top_k_slabs): a function of the
+    two numbers only."""
+    return int(library().nmfamd_top_k_slabs(C.c_long(int(nq)), C.c_long(int(count))))
+
+
+TOPK_MAX_K = 64      # nmfamd_top_k_max(); tests/test_gpu_topk_kernel.py compares the two
+
+
+def op_top_k(queries: np.ndarray, k: int, A: np.ndarray, B: np.ndarray, count: int, r: int, exclude=None, base: int = 0, slabs: int = 0):
+    """The two launches of kernels_topk.hip (launch_topk, docs/TOPK.md) on caller-built padded panels: the query panel A (a_rows, RP) and the candidate panel B
+    (b_rows, RP) of one dtype, r the coordinates that count, candidates 0 ... count - 1; queries (index base `base`) name rows of A; exclude: None or (excl_ptr,
+    excl_idx) as Engine.top_k; slabs: 0 for the plan's top_k_slabs(nq, count), or 1 ... 256.  Returns (indices (nq, k) int32, scores (nq, k))."""
+    dt = _sparse_dtype(A)
+    A = np.ascontiguousarray(A, dtype=dt); B = np.ascontiguousarray(B, dtype=dt)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1]:
+        raise ValueError("shapes: A (a_rows, RP); B (b_rows, RP)")
+    q = np.ascontiguousarray(queries, dtype=np.int32)
+    if q.ndim != 1:
+        raise ValueError("queries: a 1-D array")
+    nq, k = int(q.shape[0]), int(k)
+    ep = ip = None
+    if exclude is not None:
+        ep = np.ascontiguousarray(exclude[0], dtype=np.int64); ip = np.ascontiguousarray(exclude[1], dtype=np.int32)
+        if ep.shape != (nq + 1,) or ip.ndim != 1:
+            raise ValueError("exclude: (excl_ptr of nq + 1 offsets, excl_idx)")
+        if ep[0] == 0 and (np.diff(ep) >= 0).all() and ep[-1] > ip.shape[0]:
+            raise ValueError("exclude: excl_ptr names more entries than excl_idx holds")
+    idx = np.empty((nq, max(k, 0)), dtype=np.int32); sc = np.empty((nq, max(k, 0)), dtype=dt)
+    st = _sparse_fn("top_k", dt)(_p(q), C.c_long(nq), k, int(base), _p(A), C.c_long(A.shape[0]), _p(B), C.c_long(B.shape[0]), C.c_long(int(count)), int(A.shape[1]),
+                                 int(r), _p(ep), _p(ip), int(slabs), _p(idx), _p(sc))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_top_k")
+    return idx, sc
 
 
 def op_kl_update(P: np.ndarray, num_parts: np.ndarray, den: np.ndarray, scale: Optional[np.ndarray] = None, want_sumsq: bool = False, want_sum: bool = True,
