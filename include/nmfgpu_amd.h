@@ -313,6 +313,20 @@ NMFAMD_API int nmfamd_engine_set_hals_penalties(nmfamd_engine* e, double l1W, do
  * Valid any time between iterations; takes effect at the next nmfamd_engine_iterate.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error) for a count
  * outside 1 ... 64, and for a count other than 1 on any other engine. */
 NMFAMD_API int nmfamd_engine_set_hals_sweeps(nmfamd_engine* e, int sweeps_h, int sweeps_w);
+/* Missing-value engines under the Frobenius objective (missing_values = 1, missing_divergence = 0; docs/MISSING.md, "Coordinate descent"): the solver of the
+ * iterations that follow.  solver 0, the default: the multiplicative update; it takes only the neutral extras (sweeps 1, penalties 0).  solver 1: coordinate
+ * descent over the observed entries -- the H step solves every column of H against its own Gram matrix sum_{i in Omega_j} w_i w_i^T with sweeps_h HALS sweeps
+ * (docs/HALS.md) and the penalties (l1_h, l2_h), the W step every row of W likewise with sweeps_w and (l1_w, l2_w), which minimises
+ *   1/2 sum_Omega (v - W H)^2 + l1_w ||W||_1 + l1_h ||H||_1 + 1/2 l2_w ||W||^2 + 1/2 l2_h ||H||^2;
+ * no normalisation; the reported error stays the direct residual sum over the observed entries for (W_{k-1}, H_k); constant W runs the H step only.  Rank <= 128.
+ * Valid any time between iterations; takes effect at the next nmfamd_engine_iterate; no factor changes.  NMFAMD_INVALID_ARGUMENT (with nmfamd_engine_last_error)
+ * on any other engine, for another solver, a count outside 1 ... 64, a negative or non-finite penalty, extras with solver 0, and solver 1 at a rank above 128.
+ * nmfamd_engine_set_hals_penalties and nmfamd_engine_set_hals_sweeps keep refusing such an engine. */
+/* The rule nmfamd_engine_set_missing_solver and nmfgpu::compute's "missingSolver" apply, without an engine or a device: NULL where an engine of elem_bytes (4 or 8)
+ * and rank r with these missing_values / missing_divergence would take the setting, else the text of the refusal (a static string). */
+NMFAMD_API const char* nmfamd_missing_solver_fault(double solver, double sweeps_h, double sweeps_w, double l1_w, double l1_h, double l2_w, double l2_h, int elem_bytes,
+                                                   double missing_values, double missing_divergence, int r);
+NMFAMD_API int nmfamd_engine_set_missing_solver(nmfamd_engine* e, int solver, int sweeps_h, int sweeps_w, double l1_w, double l1_h, double l2_w, double l2_h);
 /* HALS engines: per-column dynamic stopping of the inner sweeps (docs/HALS.md, "Dynamic stopping").  With delta in (0, 1) the counts of
  * nmfamd_engine_set_hals_sweeps become maximum counts: within one step a column of the swept panel is frozen after its sweep t when the squared step of that
  * sweep is at most delta^2 times the squared step of its first sweep, and is not stepped again.  0, the default, runs the static counts, bit for bit.  Valid any
@@ -757,6 +771,15 @@ NMFAMD_API int nmfamd_op_masked_beta_half_step_f32(const int* ptr, const int* id
 NMFAMD_API int nmfamd_op_masked_beta_half_step_f64(const int* ptr, const int* idx, const double* val, long nnz, double* A, long a_rows, const double* B, long b_rows, int RP,
                                                    int rows, int divergence, double beta, double l1, double l2, int update, double* t_frob, double* t_div,
                                                    double* sumsq_part, int sumsq_parts);
+/* masked_cd_half_step: one launch of the coordinate-descent half-step over the observed entries (kernels_masked_cd.hip, docs/MISSING.md "Coordinate descent").
+ * A [a_rows][RP] (a_rows >= rows; rows < `rows` are updated in place, the others come back as they were), B [b_rows][RP], RP 64 or 128, r in 1 ... RP the
+ * coordinates that count (the others may hold anything in A and B and come out 0 in the updated rows); ptr / idx / val as above with rows + 1 offsets, every index
+ * inside B (checked here, on the host).  sweeps in 1 ... 64; l1, l2 the penalties of the half-step, finite and >= 0.  G_out [rows][RP][RP] and c_out [rows][RP]
+ * (both or neither): the normal equations G_i = sum_p b_p b_p^T, c_i = sum_p val[p] b_p the launch formed for each row. */
+NMFAMD_API int nmfamd_op_masked_cd_half_step_f32(const int* ptr, const int* idx, const float* val, long nnz, float* A, long a_rows, const float* B, long b_rows, int RP, int r,
+                                                 int rows, int sweeps, double l1, double l2, float* G_out, float* c_out);
+NMFAMD_API int nmfamd_op_masked_cd_half_step_f64(const int* ptr, const int* idx, const double* val, long nnz, double* A, long a_rows, const double* B, long b_rows, int RP, int r,
+                                                 int rows, int sweeps, double l1, double l2, double* G_out, double* c_out);
 /* predict_entries: one launch of the gather of kernels_predict.hip (docs/PREDICT.md) on caller-built padded panels Wt [w_rows][RP] and H [h_rows][RP] (fp32: RP 64,
  * 128, 256, 384, 512; fp64: 64 ... 512 in steps of 64), r in 1 ... RP the coordinates that count.  rows / cols: nnz >= 1 coordinates of index base 0 or 1, each
  * inside the panels (checked here, on the host: NMFAMD_INVALID_ARGUMENT).  vals (or NULL) and beta as nmfamd_engine_score, without its value rule.  out (or NULL

@@ -264,6 +264,8 @@ def compute(V, W: np.ndarray, H: np.ndarray, *, algorithm: NmfAlgorithm = NmfAlg
     ``parameters={"missingValues": 1}`` fits the observed entries only (docs/MISSING.md): the stored entries of a sparse V
     (explicit zeros included), the non-NaN entries of a dense V.  Multiplicative algorithm, CopyExisting or AllRandomValues
     start, one GPU, at most 256 features; the reported Frobenius error / RMSD are those over the observed entries.
+    ``"missingSolver": 1`` beside it fits them by coordinate descent instead of the multiplicative update (docs/MISSING.md, "Coordinate descent"; at most 128
+    features, the Frobenius objective only), and "sweepsH", "sweepsW", "l1W", "l1H", "l2W", "l2H" are then that solver's.
 
     ``parameters={"sweepsH": 3, "sweepsW": 2}`` with the HALS algorithm: accelerated HALS, that many sweeps per product in the H and in the W
     step (integers in 1 ... 64, absent = 1; docs/HALS.md, "Inner sweeps"), next to the penalties "l1W", "l1H", "l2W", "l2H".  ``"sweepsTolerance": 0.1``

@@ -293,13 +293,33 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 			return ResultType::ErrorInvalidArgument;
 		}
 	}
+	// "missingSolver" = 0 | 1 beside "missingValues" = 1 with the Multiplicative algorithm (docs/MISSING.md, "Coordinate descent"): 1 fits the observed entries by
+	// coordinate descent.  With it "sweepsH", "sweepsW" and "l1W" ... "l2H" are the solver's (Engine::set_missing_solver) and not the HALS engines': they are read
+	// here and the two blocks below leave them alone.
+	nmfamd::MissingSolver missing_solver;
+	const bool have_missing_solver = parameter_index(d.parameters, d.numParameters, "missingSolver") >= 0;
+	if (have_missing_solver) {
+		auto value = [&](const char* name, double absent) {
+			const int idx = parameter_index(d.parameters, d.numParameters, name);
+			return idx >= 0 ? d.parameters[idx].value : absent;
+		};
+		const double solver = value("missingSolver", 0), sh = value("sweepsH", 1), sw = value("sweepsW", 1);
+		const double l1W = value("l1W", 0), l1H = value("l1H", 0), l2W = value("l2W", 0), l2H = value("l2H", 0);
+		// (the engine's own rule, asked here so that a refusal comes before any device work)
+		if (const char* why = nmfamd::missing_solver_fault(solver, sh, sw, l1W, l1H, l2W, l2H, sizeof(T) == 4, prm.missing_values == 1, prm.missing_divergence == 0, (int)d.features)) {
+			log_error((std::string("[ERROR] ") + why).c_str());
+			return ResultType::ErrorInvalidArgument;
+		}
+		missing_solver.solver = (int)solver; missing_solver.sweeps_h = (int)sh; missing_solver.sweeps_w = (int)sw;
+		missing_solver.l1W = l1W; missing_solver.l1H = l1H; missing_solver.l2W = l2W; missing_solver.l2H = l2H;
+	}
 	{
 		// "l1W", "l1H", "l2W", "l2H": the penalties of scikit-learn's coordinate descent on the HALS sweeps (docs/HALS.md) and of its multiplicative update on the
 		// dense divergence updates (docs/DIVERGENCE.md: "divergence" 2, 3, and 1 with "denseCompute") and on the masked divergence update ("missingDivergence"); absent = 0
 		struct { const char* name; double* slot; } pen[] = {{"l1W", &prm.l1W}, {"l1H", &prm.l1H}, {"l2W", &prm.l2W}, {"l2H", &prm.l2H}};
 		for (auto& p : pen) {
 			const int idx = parameter_index(d.parameters, d.numParameters, p.name);
-			if (idx < 0) continue;
+			if (idx < 0 || have_missing_solver) continue;
 			*p.slot = d.parameters[idx].value;
 		}
 		// (the engine's own rule, asked here so that a refusal comes before any device work)
@@ -311,9 +331,9 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 	{
 		// "sweepsH", "sweepsW": sweeps per product of accelerated HALS (docs/HALS.md, "Inner sweeps"); absent = 1, integers in 1 ... 64, other than 1 only with HALS
 		int idx = parameter_index(d.parameters, d.numParameters, "sweepsH");
-		if (idx >= 0) prm.sweeps_h = d.parameters[idx].value;
+		if (idx >= 0 && !have_missing_solver) prm.sweeps_h = d.parameters[idx].value;
 		idx = parameter_index(d.parameters, d.numParameters, "sweepsW");
-		if (idx >= 0) prm.sweeps_w = d.parameters[idx].value;
+		if (idx >= 0 && !have_missing_solver) prm.sweeps_w = d.parameters[idx].value;
 		// (the engine's own rule, asked here so that a refusal comes before any device work)
 		if (const char* why = nmfamd::hals_sweeps_fault(prm.sweeps_h, prm.sweeps_w, d.algorithm == NmfAlgorithm::HALS)) {
 			log_error((std::string("[ERROR] ") + why).c_str());
@@ -451,7 +471,7 @@ ResultType compute_impl(NmfDescription<T>& d, ISummary* summary_iface) {
 
 	std::unique_ptr<runner::Runner<T>> run_ptr;
 	if (num_gpus > 1) run_ptr.reset(new runner::TeamRunner<T>(d, prm, num_gpus, g_context->deviceID, shard_mode));
-	else run_ptr.reset(new runner::SingleRunner<T>(d, prm, g_context->stream));
+	else run_ptr.reset(new runner::SingleRunner<T>(d, prm, g_context->stream, missing_solver));
 	runner::Runner<T>& engine = *run_ptr;
 	nmfamd::Status st = engine.setup(d);
 	if (st != nmfamd::ST_OK) {

@@ -452,6 +452,18 @@ int nmfamd_engine_set_hals_sweeps(nmfamd_engine* e, int sweeps_h, int sweeps_w) 
 	return dispatch(e, set, set);
 }
 
+const char* nmfamd_missing_solver_fault(double solver, double sweeps_h, double sweeps_w, double l1_w, double l1_h, double l2_w, double l2_h, int elem_bytes,
+                                        double missing_values, double missing_divergence, int r) {
+	return nmfamd::missing_solver_fault(solver, sweeps_h, sweeps_w, l1_w, l1_h, l2_w, l2_h, elem_bytes == 4, missing_values == 1, missing_divergence == 0, r);
+}
+
+int nmfamd_engine_set_missing_solver(nmfamd_engine* e, int solver, int sweeps_h, int sweeps_w, double l1_w, double l1_h, double l2_w, double l2_h) {
+	nmfamd::MissingSolver s;
+	s.solver = solver; s.sweeps_h = sweeps_h; s.sweeps_w = sweeps_w; s.l1W = l1_w; s.l1H = l1_h; s.l2W = l2_w; s.l2H = l2_h;
+	auto set = [&](auto& g) { return g.set_missing_solver(s); };
+	return dispatch(e, set, set);
+}
+
 int nmfamd_engine_set_hals_sweep_tolerance(nmfamd_engine* e, double delta) {
 	auto set = [&](auto& g) { return g.set_hals_sweep_tolerance(delta); };
 	return dispatch(e, set, set);
@@ -1555,6 +1567,29 @@ int op_masked_beta_half_step(const int* ptr, const int* idx, const T* val, long 
 	return NMFAMD_OK;
 }
 
+// One launch of the coordinate-descent half-step over the observed entries (kernels_masked_cd.hip) on a caller-built image and caller-built padded panels.  A
+// [a_rows][RP] comes back as the launch left it; G_out / c_out (both or neither) receive the normal equations of every row.
+template <typename T>
+int op_masked_cd_half_step(const int* ptr, const int* idx, const T* val, long nnz, T* A, long a_rows, const T* B, long b_rows, int RP, int r, int rows, int sweeps, double l1,
+                           double l2, T* G_out, T* c_out) {
+	if (!ptr || !idx || !val || !A || !B || nnz < 0 || nnz > 0x7fffffffl || b_rows < 1 || rows < 1 || a_rows < rows || !masked_cd_rank_instantiated(RP) || r < 1 || r > RP ||
+	    (G_out == nullptr) != (c_out == nullptr) || !sparse_image_ok(ptr, idx, nnz, rows, 1, b_rows))
+		return NMFAMD_INVALID_ARGUMENT;
+	if (nmfamd_device_count() <= 0) return NMFAMD_NO_DEVICE;
+	const size_t panel = (size_t)a_rows * RP, ng = G_out ? (size_t)rows * RP * RP : 0, nc = G_out ? (size_t)rows * RP : 0;
+	DevBuf dPtr, dIdx, dVal, dA, dB, dG, dC;
+	if (upload(dPtr, ptr, (size_t)rows + 1) != hipSuccess || upload(dIdx, idx, (size_t)nnz) != hipSuccess || upload(dVal, val, (size_t)nnz) != hipSuccess ||
+	    upload(dA, A, panel) != hipSuccess || upload(dB, B, (size_t)b_rows * RP) != hipSuccess || (G_out && (upload(dG, G_out, ng) != hipSuccess || upload(dC, c_out, nc) != hipSuccess)))
+		return NMFAMD_NO_DEVICE_MEMORY;
+	const int st = op_status(launch_masked_cd_half_step<T>((const int*)dPtr.p, (const int*)dIdx.p, (const T*)dVal.p, (T*)dA.p, (const T*)dB.p, RP, r, rows, sweeps, (T)l1, (T)l2,
+	                                                       (T*)dG.p, (T*)dC.p, nullptr));
+	if (st != NMFAMD_OK) return st;
+	if (hipMemcpy(A, dA.p, sizeof(T) * panel, hipMemcpyDeviceToHost) != hipSuccess) return NMFAMD_HIP_ERROR;
+	if (G_out && (hipMemcpy(G_out, dG.p, sizeof(T) * ng, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(c_out, dC.p, sizeof(T) * nc, hipMemcpyDeviceToHost) != hipSuccess))
+		return NMFAMD_HIP_ERROR;
+	return NMFAMD_OK;
+}
+
 // One launch of the gather of kernels_predict.hip on caller-built padded panels (docs/PREDICT.md).  Every coordinate is checked here, on the host: the kernel
 // checks none.  out and part are uploaded as the caller filled them.
 template <typename T>
@@ -1882,6 +1917,16 @@ int nmfamd_op_predict_entries_f32(const int* rows, const int* cols, const float*
 int nmfamd_op_predict_entries_f64(const int* rows, const int* cols, const double* vals, long nnz, int base, const double* Wt, long w_rows, const double* H, long h_rows, int RP,
                                   int r, double beta, double* out, long out_len, double* part, int parts) {
 	return op_predict_entries<double>(rows, cols, vals, nnz, base, Wt, w_rows, H, h_rows, RP, r, beta, out, out_len, part, parts);
+}
+
+int nmfamd_op_masked_cd_half_step_f32(const int* ptr, const int* idx, const float* val, long nnz, float* A, long a_rows, const float* B, long b_rows, int RP, int r, int rows,
+                                      int sweeps, double l1, double l2, float* G_out, float* c_out) {
+	return op_masked_cd_half_step<float>(ptr, idx, val, nnz, A, a_rows, B, b_rows, RP, r, rows, sweeps, l1, l2, G_out, c_out);
+}
+
+int nmfamd_op_masked_cd_half_step_f64(const int* ptr, const int* idx, const double* val, long nnz, double* A, long a_rows, const double* B, long b_rows, int RP, int r, int rows,
+                                      int sweeps, double l1, double l2, double* G_out, double* c_out) {
+	return op_masked_cd_half_step<double>(ptr, idx, val, nnz, A, a_rows, B, b_rows, RP, r, rows, sweeps, l1, l2, G_out, c_out);
 }
 
 int nmfamd_op_masked_beta_half_step_f32(const int* ptr, const int* idx, const float* val, long nnz, float* A, long a_rows, const float* B, long b_rows, int RP, int rows,

@@ -2646,6 +2646,18 @@ Status Engine<T>::set_hals_sweeps(int h, int w) {
 }
 
 template <typename T>
+Status Engine<T>::set_missing_solver(const MissingSolver& s) {
+	if (const char* why = missing_solver_fault(s.solver, s.sweeps_h, s.sweeps_w, s.l1W, s.l1H, s.l2W, s.l2H, sizeof(T) == 4, prm_.is_masked(), !prm_.is_masked_beta(), r_)) {
+		last_error_ = why;
+		return ST_INVALID;
+	}
+	// (nothing derived from a factor outlives a launch of either solver: PanelState has no flag to clear, and the factors stay as they are)
+	cd_ = s;
+	cd_.l1W = (double)(T)s.l1W; cd_.l1H = (double)(T)s.l1H; cd_.l2W = (double)(T)s.l2W; cd_.l2H = (double)(T)s.l2H;
+	return ST_OK;
+}
+
+template <typename T>
 Status Engine<T>::set_hals_sweep_tolerance(double delta) {
 	if (const char* why = hals_sweep_tolerance_fault(delta, alg_ == ALG_HALS)) { last_error_ = why; return ST_INVALID; }
 	prm_.sweep_tolerance = delta;
@@ -3110,6 +3122,7 @@ Status Engine<T>::iterate_kl(bool compute_error) {
 template <typename T>
 Status Engine<T>::iterate_masked(bool compute_error, bool constant_w) {
 	if (!sparse_ || nnz_ <= 0) { last_error_ = "missing values: no stored entry has been uploaded"; return ST_INVALID; }
+	if (cd_.solver == 1) return iterate_masked_cd(compute_error, constant_w);
 	const T eps = std::numeric_limits<T>::epsilon();
 	record_begin();
 	HIPX(launch_masked_half_step<T>(csc_ptr_, csc_idx_, csc_val_, H_, Wt_, RP_, eps, true, (T*)nullptr, (T*)nullptr, n_, stream_));
@@ -3127,6 +3140,31 @@ Status Engine<T>::iterate_masked(bool compute_error, bool constant_w) {
 		masked_pending_ = true;
 	}
 	if (!constant_w) HIPX(launch_normalize_panel<T>(Wt_, RP_, (int)mpad_, msq_part_, masked_norm_parts(m_), stream_));
+	return ST_OK;
+}
+
+// Missing-value NMF by coordinate descent (docs/MISSING.md, "Coordinate descent"; set_missing_solver): HALS on sum_Omega (v - W H)^2 with scikit-learn's penalties,
+// every row of a factor against its own Gram matrix over its observed entries -- one launch per half-step (kernels_masked_cd.hip):
+//   H step over the CSC image (sweeps_h, l1H, l2H), W step with the new H over the CSR image (sweeps_w, l1W, l2W); no normalisation
+// The error is iterate_masked's: the residual terms of the pair (W_{k-1}, H_k), from the terms-only form of the multiplicative launch between the two half-steps.
+// As there, nothing derived from a factor outlives a launch: PanelState has no flag of this iteration.
+template <typename T>
+Status Engine<T>::iterate_masked_cd(bool compute_error, bool constant_w) {
+	record_begin();
+	HIPX(launch_masked_cd_half_step<T>(csc_ptr_, csc_idx_, csc_val_, H_, Wt_, RP_, r_, n_, cd_.sweeps_h, (T)cd_.l1H, (T)cd_.l2H, (T*)nullptr, (T*)nullptr, stream_));
+	record_end();
+	if (compute_error) {
+		HIPX(launch_masked_half_step<T>(csr_ptr_, csr_idx_, csr_val_, Wt_, H_, RP_, std::numeric_limits<T>::epsilon(), false, t_vwh_, (T*)nullptr, m_, stream_));
+		finalize_error(false);      // (the pinned buffer is about to be reused; an older copy is long complete)
+		HIPX(hipMemcpyAsync(pin_kl_, t_vwh_, sizeof(T) * m_, hipMemcpyDeviceToHost, stream_));
+		HIPX(hipEventRecord(err_event_, stream_));
+		masked_pending_ = true;
+	}
+	if (!constant_w) {
+		record_begin(1);
+		HIPX(launch_masked_cd_half_step<T>(csr_ptr_, csr_idx_, csr_val_, Wt_, H_, RP_, r_, m_, cd_.sweeps_w, (T)cd_.l1W, (T)cd_.l2W, (T*)nullptr, (T*)nullptr, stream_));
+		record_end();
+	}
 	return ST_OK;
 }
 

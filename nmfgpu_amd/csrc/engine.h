@@ -162,6 +162,33 @@ inline const char* masked_beta_fault(const AlgorithmParams& p, bool is_mu, int r
 	return nullptr;
 }
 
+// The solver of a Frobenius missing-value engine (docs/MISSING.md, "Coordinate descent"): 0 the multiplicative update, 1 coordinate descent over the observed entries
+// with sweeps_h / sweeps_w sweeps per half-step and scikit-learn's penalties.  A setting of the engine (Engine::set_missing_solver), not a field of AlgorithmParams.
+struct MissingSolver {
+	int solver = 0, sweeps_h = 1, sweeps_w = 1;
+	double l1W = 0, l1H = 0, l2W = 0, l2H = 0;
+};
+constexpr int MISSING_CD_MAX_RANK = 128;      // (the padded ranks kernels_masked_cd.hip instantiates: 64 and 128)
+// What such a setting must satisfy, stated once for Engine::set_missing_solver and nmfgpu::compute (which reads it from Parameters, as doubles): nullptr, or why not.
+// masked / frobenius: the engine fits the observed entries only / under the Frobenius objective; r: its rank.
+inline const char* missing_solver_fault(double solver, double sweeps_h, double sweeps_w, double l1W, double l1H, double l2W, double l2H, bool fp32, bool masked, bool frobenius,
+                                        int r) {
+	if (!(solver == 0 || solver == 1)) return "missing-value solver: 'missingSolver' has to be 0 (multiplicative update) or 1 (coordinate descent)";
+	if (!masked) return "missing-value solver: needs 'missingValues' = 1 (an engine that fits the observed entries only)";
+	if (!frobenius) return "missing-value solver: the Frobenius objective only ('missingDivergence' = 0)";
+	for (double x : {sweeps_h, sweeps_w})
+		if (!(x >= 1 && x <= 64) || x != (double)(int)x) return "missing-value solver: sweepsH and sweepsW must be integers in 1 ... 64";
+	bool any = sweeps_h != 1 || sweeps_w != 1;
+	for (double x : {l1W, l1H, l2W, l2H}) {
+		if (!(x >= 0) || x > 1.7976931348623157e308) return "missing-value solver: l1W, l1H, l2W and l2H must be finite and >= 0";
+		if (fp32 && x > 3.4028234663852886e38) return "missing-value solver: penalty out of the range of the engine's precision";
+		any = any || x != 0;
+	}
+	if (solver == 0 && any) return "missing-value solver: the multiplicative update takes sweeps 1 and penalties 0 only";
+	if (solver == 1 && r > MISSING_CD_MAX_RANK) return "missing-value solver: coordinate descent supports 1 ... 128 features";
+	return nullptr;
+}
+
 // What 'weighted' (nmfamd_params_v4) must satisfy, after beta_dense_fault: nullptr, or why not.
 inline const char* weighted_fault(const AlgorithmParams& p) {
 	if (!(p.weighted == 0 || p.weighted == 1)) return "weighted NMF: 'weighted' has to be 0 or 1";
@@ -302,6 +329,11 @@ public:
 	// HALS: sweeps per product of the iterations that follow, h in the H step and w in the W step (1 ... 64; (1, 1): the plain iteration).  Valid any time between
 	// iterations.  ST_INVALID with last_error() for a count out of range, and for a count other than 1 on an engine of another algorithm.
 	Status set_hals_sweeps(int h, int w);
+	// Missing values, Frobenius: the solver of the iterations that follow (docs/MISSING.md, "Coordinate descent") -- 0 the multiplicative update (sweeps 1 and
+	// penalties 0 only), 1 coordinate descent over the observed entries (kernels_masked_cd.hip; rank <= 128).  Valid any time between iterations; a setting, no
+	// factor changes.  ST_INVALID with last_error() for whatever missing_solver_fault names, every other engine included.
+	Status set_missing_solver(const MissingSolver& s);
+	const MissingSolver& missing_solver() const { return cd_; }
 	// HALS: the tolerance delta of the per-column dynamic stopping rule for the iterations that follow (docs/HALS.md, "Dynamic stopping"); 0: the static counts,
 	// bit for bit.  Valid any time between iterations.  ST_INVALID with last_error() for a value outside [0, 1), NaN included, and for a non-zero one on an engine
 	// of another algorithm.
@@ -470,6 +502,7 @@ private:
 	Status iterate_kl(bool compute_error);            // KL-divergence multiplicative update (sparse mode)
 	Status iterate_masked(bool compute_error, bool constant_w);   // multiplicative update over the stored entries only (kernels_masked.hip)
 	Status iterate_masked_beta(bool compute_error, bool constant_w);   // ... under the beta-divergence (kernels_masked_beta.hip)
+	Status iterate_masked_cd(bool compute_error, bool constant_w);     // ... by coordinate descent (kernels_masked_cd.hip; cd_.solver == 1)
 	Status masked_refuses(const char* what);          // ST_INVALID with last_error_ set: no three-phase / sharded form of the masked update
 	const char* masked_value_fault() const;           // the text of a stored value that breaks the rule of a masked divergence engine's beta
 	Status iterate_beta_minibatch(bool compute_error);            // ... its minibatch (online) form: one pass over the batches (kernels_beta_online.hip)
@@ -585,6 +618,7 @@ private:
 	// masked update: per-workgroup sums of squares of the new W rows ([MASKED_NORM_PARTS + 16][RP]); the per-row residual terms travel through pin_kl_ (first m)
 	T* msq_part_ = nullptr;
 	bool masked_pending_ = false, masked_unresolved_ = false;
+	MissingSolver cd_;      // set_missing_solver: the penalties rounded to T
 	// ... under the beta-divergence (prm_.is_masked_beta()): mbeta_ = prm_.masked_beta() rounded to T, what the launches take; the two per-row terms travel like the
 	// dense divergence engines' (t_vwh_ / t_kl_ -> pin_kl_, beta_pending_), rmsd over the stored entries
 	bool masked_beta_ = false;

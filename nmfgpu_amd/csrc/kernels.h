@@ -615,6 +615,16 @@ hipError_t launch_masked_half_step(const int* ptr, const int* idx, const T* val,
 template <typename T>
 hipError_t launch_masked_beta_half_step(const int* ptr, const int* idx, const T* val, T* A, const T* B, int RP, T eps, double beta, T l1, T l2, bool update,
                                         T* t_frob, T* t_div, T* sumsq_part, int rows, hipStream_t stream);
+// ... by coordinate descent (kernels_masked_cd.hip, docs/MISSING.md "Coordinate descent"): per row its own normal equations G_i = sum_p b_p b_p^T, c_i = sum_p val[p] b_p
+// (b_p = B(idx[p], :) with the coordinates >= r selected to 0, p in stored order, on the matrix pipe), then `sweeps` penalised HALS sweeps (docs/HALS.md) of the old row
+// in place; a row without an entry becomes 0, coordinates >= r come out 0.  G_out [rows][RP][RP] and c_out [rows][RP] (both or neither): the normal equations as formed.
+// hipErrorInvalidValue for a padded rank other than 64 / 128, r outside 1 ... RP, sweeps outside 1 ... MASKED_CD_MAX_SWEEPS, a negative or non-finite penalty.
+constexpr int MASKED_CD_MAX_SWEEPS = 64;
+constexpr int MASKED_CD_MAX_GRID = 2048;        // the workgroups stride over the rows
+constexpr bool masked_cd_rank_instantiated(int RP) { return RP == 64 || RP == 128; }
+template <typename T>
+hipError_t launch_masked_cd_half_step(const int* ptr, const int* idx, const T* val, T* A, const T* B, int RP, int r, int rows, int sweeps, T l1, T l2, T* G_out, T* c_out,
+                                      hipStream_t stream);
 
 // ---- predict and score entries of W H (kernels_predict.hip, docs/PREDICT.md) ---------------------------------------------------------------------------------
 // Over a coordinate list rows / cols (nnz entries, index base 0 or 1, unsorted, duplicates counted per copy; DEVICE memory) and the padded panels Wt ([.][RP]) and

@@ -100,8 +100,10 @@ Status upload_shard(nmfamd::Engine<T>& engine, const MatrixDescription<T>& V, lo
 template <typename T>
 class SingleRunner : public Runner<T> {
 public:
-	SingleRunner(const NmfDescription<T>& d, const nmfamd::AlgorithmParams& prm, hipStream_t stream) : prm_(prm), stream_(stream) { create(d); }
+	SingleRunner(const NmfDescription<T>& d, const nmfamd::AlgorithmParams& prm, hipStream_t stream, const nmfamd::MissingSolver& missing_solver = nmfamd::MissingSolver())
+		: prm_(prm), missing_solver_(missing_solver), stream_(stream) { create(d); }
 	Status setup(const NmfDescription<T>& d) override {
+		if (created_ != nmfamd::ST_OK) return created_;
 		if (Status st = engine_->allocate()) return st;
 		Status st = upload_input(*engine_, d.inputMatrix);
 		if (st == nmfamd::ST_VALUE_RANGE) {
@@ -109,6 +111,7 @@ public:
 			// take the native fp32 MFMA instructions (what Parameter "precision" = -1 selects)
 			prm_.precision = -1;
 			create(d);
+			if (created_ != nmfamd::ST_OK) return created_;
 			if (Status s2 = engine_->allocate()) return s2;
 			st = upload_input(*engine_, d.inputMatrix);
 		}
@@ -150,8 +153,12 @@ private:
 	void create(const NmfDescription<T>& d) {
 		engine_.reset(new nmfamd::Engine<T>((int)d.inputMatrix.rows, (int)d.inputMatrix.columns, (int)d.features, static_cast<int>(d.algorithm), prm_));
 		engine_->set_stream(stream_);
+		// (a setting of the engine, not of its parameters: an engine that is created again takes it again)
+		created_ = missing_solver_.solver != 0 ? engine_->set_missing_solver(missing_solver_) : nmfamd::ST_OK;
 	}
 	nmfamd::AlgorithmParams prm_;
+	nmfamd::MissingSolver missing_solver_;
+	Status created_ = nmfamd::ST_OK;
 	hipStream_t stream_;
 	std::unique_ptr<nmfamd::Engine<T>> engine_;
 };

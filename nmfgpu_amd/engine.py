@@ -9,6 +9,7 @@ import numpy as np
 from ._lib import library
 
 ALGORITHMS = {"mu": 0, "gdcls": 1, "als": 2, "acls": 3, "ahcls": 4, "nsnmf": 5, "hals": 6, "nenmf": 7}
+MISSING_SOLVERS = {"mu": 0, "cd": 1}      # Engine.set_missing_solver (docs/MISSING.md, "Coordinate descent")
 _STATUS = {0: "ok", 1: "invalid argument", 2: "out of device memory", 3: "out of host memory", 4: "HIP error", 5: "no HIP device",
            6: "values outside the exact range of the split-operand product"}
 
@@ -226,7 +227,7 @@ class Engine:
                  l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, dense_compute: bool = False, beta=None, weighted: bool = False, mixed_precision: bool = False,
                  batch_size=None, forget_factor=0.7, sweeps_h: int = 1, sweeps_w: int = 1, sweep_tolerance: float = 0.0,
                  steps_h: Optional[int] = None, steps_w: Optional[int] = None, step_tolerance: Optional[float] = None,
-                 missing_divergence: str = "frobenius", missing_beta=None):
+                 missing_divergence: str = "frobenius", missing_beta=None, missing_solver: Optional[str] = None, missing_sweeps_h: int = 1, missing_sweeps_w: int = 1):
         """divergence: "frobenius", "kl" (generalised KL over the stored entries of a sparse image of V; with dense_compute=True on a dense resident V),
         "is" (Itakura-Saito, always dense: every entry of V > 0) or "beta" (the beta-divergence at `beta`, any finite value, always dense: scikit-learn's
         solver="mu" with beta_loss=beta; beta=0.0 and beta=1.0 are the "is" and the dense "kl" engines; beta <= 0 needs every entry of V > 0) --
@@ -238,6 +239,10 @@ class Engine:
         weighted update at 0 / 1 weights in O(nnz r) per iteration.  beta <= 0 needs every stored value > 0, beta > 0 takes stored zeros as observations; such an
         engine takes l1_w ... l2_h (set_penalties) and constant_w, and divergence_value reports its objective.  `divergence` itself stays refused beside
         missing_values.
+
+        missing_solver ("mu" or "cd"; missing_values=True with the "frobenius" objective only; None = never set, the multiplicative update): "cd" fits the observed
+        entries by coordinate descent (docs/MISSING.md, "Coordinate descent") with missing_sweeps_h / missing_sweeps_w sweeps (1 ... 64) per half-step; rank <= 128.
+        With a missing_solver the penalties l1_w ... l2_h are the solver's (set_missing_solver), not set_penalties'.
 
         l1_w, l1_h, l2_w, l2_h: the L1 / L2 penalties on W and H of scikit-learn's coordinate descent ("hals", docs/HALS.md) and of its multiplicative update
         (the dense divergence engines, docs/DIVERGENCE.md); see set_penalties.  sparse_compute=True is available for "mu" and "hals" (rank <= 256).
@@ -268,7 +273,13 @@ class Engine:
         step_tolerance ("nenmf" only; in [0, 1), None = 0): per-column dynamic stopping of those steps, with steps_h / steps_w as maximum counts (docs/NENMF.md,
         "Dynamic stopping"); 0 keeps the static counts; see set_step_tolerance."""
         self._bind(m, n, r, dtype)
-        self._ctor = dict(algorithm=algorithm, stream=stream, row_blocks=row_blocks,
+        solver = None
+        if missing_solver is not None:
+            solver = [missing_solver, _count(missing_sweeps_h), _count(missing_sweeps_w), float(l1_w), float(l1_h), float(l2_w), float(l2_h)]
+            l1_w = l1_h = l2_w = l2_h = 0.0
+        elif missing_sweeps_h != 1 or missing_sweeps_w != 1:
+            raise ValueError("missing_sweeps_h / missing_sweeps_w need a missing_solver")
+        self._ctor = dict(algorithm=algorithm, stream=stream, row_blocks=row_blocks, missing_solver=solver,
                           params=_param_values(lam, lambda_w, lambda_h, alpha_w, alpha_h, theta, divergence, sparse_compute, precision, missing_values, dense_compute, beta,
                                                weighted, mixed_precision, batch_size, forget_factor, missing_divergence, missing_beta),
                           penalties=[float(l1_w), float(l1_h), float(l2_w), float(l2_h)], sweeps=[_count(sweeps_h), _count(sweeps_w)],
@@ -325,6 +336,8 @@ class Engine:
                 self.set_steps(*c["steps"])
             if c.get("step_tolerance") is not None:      # (likewise)
                 self.set_step_tolerance(c["step_tolerance"])
+            if c.get("missing_solver") is not None:      # (likewise)
+                self.set_missing_solver(*c["missing_solver"])
         except EngineError:
             self.close()
             raise
@@ -588,6 +601,22 @@ class Engine:
         self._check(self._lib.nmfamd_engine_set_hals_penalties(self._h, *(C.c_double(v) for v in vals)), "set_hals_penalties")
         if self._ctor is not None:
             self._ctor["penalties"] = vals
+
+    def set_missing_solver(self, solver: str = "cd", sweeps_h: int = 1, sweeps_w: int = 1, l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0):
+        """Missing values under the Frobenius objective: the solver of the iterations that follow (nmfamd_engine_set_missing_solver; docs/MISSING.md, "Coordinate
+        descent").  "mu": the multiplicative update, which takes sweeps 1 and penalties 0 only.  "cd": coordinate descent over the observed entries -- every column
+        of H, then every row of W, against its own Gram matrix with sweeps_h / sweeps_w HALS sweeps (1 ... 64) and the penalties of set_penalties' objective, the
+        squared error summed over the observed entries; no normalisation; rank <= 128.  Valid between iterations; the factors stay as they are.  frobenius / rmsd
+        keep reporting the unpenalised error over the observed entries."""
+        if solver not in MISSING_SOLVERS:
+            raise ValueError(f'missing_solver: "mu" or "cd", got {solver!r}')
+        vals = [solver, _count(sweeps_h), _count(sweeps_w), float(l1_w), float(l1_h), float(l2_w), float(l2_h)]
+        if not hasattr(self._lib, "nmfamd_engine_set_missing_solver"):
+            raise EngineError(1, "set_missing_solver", "the loaded library has no missing-value solver setting")
+        self._check(self._lib.nmfamd_engine_set_missing_solver(self._h, MISSING_SOLVERS[solver], C.c_int(vals[1]), C.c_int(vals[2]), *(C.c_double(v) for v in vals[3:])),
+                    "set_missing_solver")
+        if self._ctor is not None:
+            self._ctor["missing_solver"] = vals
 
     def set_sweeps(self, h: int = 1, w: int = 1):
         """HALS: the iterations that follow run h sweeps per H step and w sweeps per W step against one set of products each (accelerated HALS,
@@ -1585,6 +1614,41 @@ def op_masked_beta_half_step(ptr: np.ndarray, idx: np.ndarray, val: np.ndarray, 
     if st != 0:
         raise EngineError(st, "nmfamd_op_masked_beta_half_step")
     return {"A": A, "t_frob": tf, "t_div": td, "sumsq_part": sq}
+
+
+def missing_solver_fault(solver=1, sweeps_h=1, sweeps_w=1, l1_w=0.0, l1_h=0.0, l2_w=0.0, l2_h=0.0, *, dtype=np.float32, missing_values=True, missing_divergence=0, r=1):
+    """Why Engine.set_missing_solver (and compute's "missingSolver") would refuse these values on an engine of this dtype, rank and missing-value setting -- the
+    library's own rule, asked without an engine or a device (nmfamd_missing_solver_fault) -- or None where it would take them.  solver: 0 / 1 as the C interface
+    numbers them; the counts travel as doubles, as compute reads them."""
+    fn = library().nmfamd_missing_solver_fault
+    fn.restype = C.c_char_p
+    why = fn(*(C.c_double(float(v)) for v in (solver, sweeps_h, sweeps_w, l1_w, l1_h, l2_w, l2_h)), int(np.dtype(dtype).itemsize), C.c_double(float(missing_values)),
+             C.c_double(float(missing_divergence)), int(r))
+    return why.decode() if why else None
+
+
+def op_masked_cd_half_step(ptr: np.ndarray, idx: np.ndarray, val: np.ndarray, A: np.ndarray, B: np.ndarray, rows: int, r: int, sweeps: int = 1, l1: float = 0.0,
+                           l2: float = 0.0, normal: bool = False, *, fill=np.nan):
+    """One launch of the coordinate-descent half-step over the observed entries (launch_masked_cd_half_step, docs/MISSING.md "Coordinate descent"): A (>= rows, RP)
+    the output rows' own factor rows, B (b_rows, RP) the gathered panel, RP 64 or 128, r the coordinates that count, ptr / idx / val the image (rows + 1 offsets).
+    Returns a dict: `A` (a new array; rows >= `rows` as given) and, with normal=True, `G` ((rows, RP, RP)) and `c` ((rows, RP)): the normal equations the launch
+    formed, pre-filled with `fill` -- else None."""
+    dt = _sparse_dtype(val)
+    ptr, idx, val = _sparse_image(ptr, idx, val, dt)
+    A = np.array(A, dtype=dt, order="C"); B = np.ascontiguousarray(B, dtype=dt)
+    rows = int(rows)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1] or A.shape[0] < rows:
+        raise ValueError("shapes: A (>= rows, RP); B (b_rows, RP)")
+    if ptr.shape != (rows + 1,):
+        raise ValueError("ptr: rows + 1 offsets")
+    RP = A.shape[1]
+    G = np.full((rows, RP, RP), fill, dt) if normal else None
+    c = np.full((rows, RP), fill, dt) if normal else None
+    st = _sparse_fn("masked_cd_half_step", dt)(_p(ptr), _p(idx), _p(val), C.c_long(len(val)), _p(A), C.c_long(A.shape[0]), _p(B), C.c_long(B.shape[0]), RP, int(r), rows,
+                                               _count(sweeps), C.c_double(float(l1)), C.c_double(float(l2)), _p(G), _p(c))
+    if st != 0:
+        raise EngineError(st, "nmfamd_op_masked_cd_half_step")
+    return {"A": A, "G": G, "c": c}
 
 
 def predict_entry_parts(nnz: int) -> int:
